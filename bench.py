@@ -15,12 +15,6 @@ torch.cuda.synchronize() on both sides of exactly K steps, max over ranks; rank 
 """
 from __future__ import annotations
 
-import os as _os
-# HIP maps streams onto GPU_MAX_HW_QUEUES hardware queues (default 4).  The library runs three streams (main, prep, aux);
-# with RCCL's own streams on top two of them end up sharing a queue and the prep / main overlap is lost (measured: 158 ->
-# 254 us per step as soon as an RCCL communicator exists before the handle is created).  Must be set before HIP initialises.
-_os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
-
 import argparse
 import json
 import os
@@ -68,6 +62,35 @@ def compulsory_gather_bytes(Kp, num_items, examples, units):
     per example, and one partial row per (work unit, item partition) is written."""
     rows = num_items * (1.0 - np.exp(-examples / num_items))
     return rows * 4.0 * Kp + examples * 12.0 + 8.0 * units * 4.0 * Kp
+
+
+DUMP_BUDGET_BYTES = 60 << 20     # --dump-outputs: all arrays together, .npy headers included, stay under 64 MB
+
+
+def dump_outputs(model, out_dir):
+    """--dump-outputs: the parameters the last timed step left on the device, as a caller of the training path reads them back
+    (`get`), written as <out_dir>/<name>.npy in float32.  Smaller arrays are written whole; an array larger than its even share of
+    what is left of DUMP_BUDGET_BYTES keeps a fixed sample of its rows instead (np.random.default_rng(0), ascending, so the same
+    rows for every run of the same shape and for a parameter and its accumulator)."""
+    from cdae_amd import binding as b
+    names = [("W", b.P_W), ("W_ag", b.P_W_AG), ("b", b.P_B), ("b_ag", b.P_B_AG), ("bp", b.P_BP), ("bp_ag", b.P_BP_AG),
+             ("Wu", b.P_WU), ("Wu_ag", b.P_WU_AG)]
+    if model.cfg.asymmetric:
+        names += [("V", b.P_V), ("V_ag", b.P_V_AG)]
+    if model.cfg.linear_function:
+        names += [("Uu", b.P_UU), ("Uu_ag", b.P_UU_AG)]
+    arrays = sorted(((name, model.get(which)) for name, which in names), key=lambda na: na[1].nbytes)
+    os.makedirs(out_dir, exist_ok=True)
+    left, picks = DUMP_BUDGET_BYTES, {}      # picks: shape -> rows kept (a later array of that shape never has a smaller share)
+    for n, (name, a) in enumerate(arrays):
+        share = left // (len(arrays) - n) - 128                     # (an .npy header is 128 bytes)
+        if a.shape not in picks and a.nbytes > share:
+            rows = share // (a.itemsize * int(np.prod(a.shape[1:])))
+            picks[a.shape] = np.sort(np.random.default_rng(0).choice(a.shape[0], rows, replace=False))
+        if a.shape in picks:
+            a = a[picks[a.shape]]
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+        left -= a.nbytes + 128
 
 
 class Watchdog:
@@ -168,6 +191,9 @@ def main():
     ap.add_argument("--combine", choices=["sum", "global-acc"], default="global-acc",
                     help="--layout users: how the all-reduced deltas are folded in (cdae_hip_delta_set_combine).  global-acc (default): one step "
                          "with the AdaGrad accumulator that has seen every rank; sum: the ranks' accumulated steps are added (rounds 1-4)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the parameters the last of them left (rank 0's model) as DIR/<name>.npy, float32, "
+                         "under 64 MB in all (larger arrays as a fixed sample of their rows); same arguments, same inputs")
     args = ap.parse_args()
 
     rank = int(os.environ.get("RANK", 0))
@@ -360,6 +386,8 @@ def main():
     t_queued = time.perf_counter()
     sync()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(model, args.dump_outputs)
     if os.environ.get("CDAE_BENCH_PHASES"):      # developer aid: where the host spends the timed region
         t_a = time.perf_counter(); model.synchronize(); t_b = time.perf_counter(); torch.cuda.synchronize(); t_c = time.perf_counter()
         print(f"[phases] enqueue {1e6 * (t_queued - t0):.0f} us, wait {1e6 * (elapsed - (t_queued - t0)):.0f} us; on an idle device: "
@@ -608,6 +636,8 @@ def bench_item_rows(args, rank, world):
     users = run(args.warmup, args.steps)
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_outputs(model, args.dump_outputs)
     if dist is not None:
         dist.barrier()
     # per-kernel record (untimed pass behind the timed region): HIP events around shard 0's decode / row launches of a few batches
@@ -765,6 +795,8 @@ def bench_certified(args, rank, world):
         users = run(args.warmup, args.steps)
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_outputs(model, args.dump_outputs)
     if dist is not None:
         dist.barrier()
     n_gpus = len(set(devices))

@@ -4,6 +4,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -44,6 +45,23 @@ def test_default_line_with_cpu_baseline(built):
     assert d["dtype"] == "f32" and d["roofline"]["bound"] == "hbm"
     c = d["cpu_baseline"]
     assert c["kind"] == "port" and c["cores"] == 1 and c["value"] > 0 and c["unit"] == "users/s" and isinstance(c["sample"], str)
+
+
+def test_dump_outputs_are_what_the_timed_steps_left(built, tmp_path):
+    """--dump-outputs: the parameters after the last timed step, float32 .npy.  Training is bit-deterministic
+    (tests/test_gpu_parity.py::test_training_is_bit_deterministic_and_handles_reload), so the same arguments write the same arrays, also
+    without the untimed profiling pass that follows the timed steps; one more timed step writes other arrays."""
+    dumps = []
+    for name, extra in (("a", []), ("b", ["--profile-every", "0"]), ("c", ["--steps", "7"])):
+        d = run_bench(["--no-cpu-baseline", "--dump-outputs", str(tmp_path / name)] + extra)
+        assert d["steps"] == (7 if name == "c" else 6) and d["ms_per_step"] > 0
+        dumps.append({f[:-4]: np.load(tmp_path / name / f) for f in os.listdir(tmp_path / name)})
+    a, b, c = dumps
+    assert set(a) == {"W", "W_ag", "b", "b_ag", "bp", "bp_ag", "Wu", "Wu_ag"}
+    assert sum(os.path.getsize(tmp_path / "a" / (k + ".npy")) for k in a) <= 64e6
+    for k in a:
+        assert a[k].dtype == np.float32 and np.isfinite(a[k]).all() and np.array_equal(a[k], b[k]), k
+    assert not np.array_equal(a["W"], c["W"])
 
 
 def test_full_output_line(built):

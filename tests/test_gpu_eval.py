@@ -131,11 +131,9 @@ def test_set_test_rows_rejects_bad_rows(built):
 def test_reference_yelp_app_prints_the_same_topn_columns_from_the_device(built, tmp_path):
     """TOPN_Evaluation<CDAE>::evaluate of the host layer takes the device path when the model was reset with `train`
     (src/model/evaluation.hpp); CDAE_HOST_TOPN=1 keeps the host loop.  Same seed -> the printed columns are identical strings."""
-    from tests.test_host_cpp import write_ratings, run
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    yelp = os.path.join(root, "build", "yelp")
+    from tests.test_host_cpp import write_ratings, run, YELP as yelp, NO_YELP
     if not os.path.exists(yelp):
-        pytest.skip("no build/yelp (reference sources were not present at build time)")
+        pytest.skip(NO_YELP)
     write_ratings(tmp_path / "yelp_10core.txt")
     for task in ("prepare", "split"):
         assert run([yelp, f"--task={task}"], tmp_path)[0] == 255

@@ -1,7 +1,7 @@
 """The host C++ layer (src/): libcf-shaped headers over the C ABI.
 
-CPU: the headers compile; the reference's apps/yelp/yelp.cpp builds UNMODIFIED and IN PLACE against them
-(only where /root/reference exists — nothing of it is copied here) and runs BASELINE config 1's plumbing
+CPU: the headers compile; the reference's apps/yelp/yelp.cpp, built UNMODIFIED and IN PLACE against them by build() as
+oracle/_ref/yelp (only where the reference tree exists — nothing of its source is copied here), runs BASELINE config 1's plumbing
 prepare -> split -> test up to the Popularity row.
 GPU: the same binaries train CDAE through Solver<CDAE> on the device.
 """
@@ -16,7 +16,8 @@ from cdae_amd import synth
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BUILD = os.path.join(ROOT, "build")
-REF_YELP = "/root/reference/apps/yelp/yelp.cpp"
+YELP = os.path.join(ROOT, "oracle", "_ref", "yelp")
+NO_YELP = "no oracle/_ref/yelp (the reference tree was not present when build() ran)"
 
 
 def write_ratings(path, seed=5):
@@ -44,8 +45,6 @@ def run(cmd, cwd, env=None):
 @pytest.fixture(scope="module")
 def host_bins(built):
     subprocess.check_call(["make", "-C", os.path.join(ROOT, "src"), "-s", "check"])
-    if os.path.exists(REF_YELP):
-        subprocess.check_call(["make", "-C", os.path.join(ROOT, "src"), "-s", "yelp"])
     return BUILD
 
 
@@ -58,9 +57,9 @@ def test_host_layer_compiles_and_cpu_pieces_work(host_bins, tmp_path):
 
 
 def test_reference_yelp_app_builds_unmodified_and_runs_config1_plumbing(host_bins, tmp_path):
-    yelp = os.path.join(host_bins, "yelp")
+    yelp = YELP
     if not os.path.exists(yelp):
-        pytest.skip("reference sources not present on this box and no prebuilt build/yelp")
+        pytest.skip(NO_YELP)
     write_ratings(tmp_path / "yelp_10core.txt")
     # every task except "test" ends in yelp.cpp:102-104's `else { return -1; }` after doing its work
     assert run([yelp, "--task=prepare"], tmp_path)[0] == 255
@@ -82,18 +81,16 @@ def test_reference_yelp_app_builds_unmodified_and_runs_config1_plumbing(host_bin
     assert rc not in (0, 255) and "truncated" in out, (rc, out[-500:])
 
 
-REF_SAMPLE = "/root/reference/test/test_data/sample_movielens_data.txt"
+REF_SAMPLE = os.path.join(ROOT, "tests", "golden", "sample_movielens_data.txt")      # the reference's test/test_data/ file, as is
 
 
 def test_the_references_own_data_fixture_gives_what_its_data_test_asserts(host_bins, tmp_path):
     """The one data fixture the reference holds (test/test_data/sample_movielens_data.txt) through this repository's ingest, with the
     assertions of the reference's test/data_test.hpp:17-62: the "::" parser yields four fields per line (CHECK_EQ inside host_check),
     every instance has two features, 200 instances, the cache round-trips, random_split(0.3) leaves size * 0.7 and size * 0.3.
-    The expected numbers are committed here; the file itself stays in the reference tree (this test runs where that tree exists).
+    The expected numbers are committed here; the file itself is committed unchanged under tests/golden/.
     Beyond the reference's assertions: 5 users / 175 items / label sum 792 (counted from the file with plain Python below) and the
     per-user split's floor(0.3 n_u) (data-inl.hpp:249-261): 58 of the users' 22 + 20 + 33 + 38 + 87 ratings."""
-    if not os.path.exists(REF_SAMPLE):
-        pytest.skip("the reference tree is not on this box")
     rows = [l.strip().split("::") for l in open(REF_SAMPLE) if l.strip()]
     assert len(rows) == 200 and {len(r) for r in rows} == {4}
     local = tmp_path / "sample_movielens_data.txt"
@@ -173,9 +170,9 @@ def test_reference_yelp_app_table_matches_the_oracle_on_the_same_rows(host_bins,
     from helpers import read_data_cache, csr_of, fnv1a64
     import oracle as orc
     from oracle import binding as ob
-    yelp = os.path.join(host_bins, "yelp")
+    yelp = YELP
     if not os.path.exists(yelp):
-        pytest.skip("no build/yelp (reference sources were not present at build time)")
+        pytest.skip(NO_YELP)
     write_ratings(tmp_path / "yelp_10core.txt")
     for task in ("prepare", "split"):
         assert run([yelp, f"--task={task}"], tmp_path)[0] == 255
@@ -226,9 +223,9 @@ def test_solver_cdae_trains_on_gpu_through_host_layer(host_bins, tmp_path):
 
 @pytest.mark.gpu
 def test_reference_yelp_app_trains_cdae_on_gpu(host_bins, tmp_path):
-    yelp = os.path.join(host_bins, "yelp")
+    yelp = YELP
     if not os.path.exists(yelp):
-        pytest.skip("no build/yelp (reference sources were not present at build time)")
+        pytest.skip(NO_YELP)
     write_ratings(tmp_path / "yelp_10core.txt")
     for task in ("prepare", "split"):
         assert run([yelp, f"--task={task}"], tmp_path)[0] == 255
@@ -245,9 +242,9 @@ def test_reference_yelp_app_trains_cdae_on_gpu(host_bins, tmp_path):
 @pytest.mark.gpu
 def test_reference_yelp_app_trains_cdae_with_linear_function_gate(host_bins, tmp_path):
     """--linear_function=true (the one CDAE flag cdae.sh never switches on): the gate Uu runs on the GPU too."""
-    yelp = os.path.join(host_bins, "yelp")
+    yelp = YELP
     if not os.path.exists(yelp):
-        pytest.skip("no build/yelp (reference sources were not present at build time)")
+        pytest.skip(NO_YELP)
     write_ratings(tmp_path / "yelp_10core.txt")
     for task in ("prepare", "split"):
         assert run([yelp, f"--task={task}"], tmp_path)[0] == 255
@@ -266,9 +263,9 @@ def test_reference_yelp_app_trains_cdae_with_linear_function_gate(host_bins, tmp
 def test_reference_yelp_app_trains_cdae_full_output_k50(host_bins, tmp_path):
     """BASELINE configs[1] through the drop-in boundary: the unmodified yelp app, K=50 sigmoid + CE, with the full-output
     (bf16 MFMA) decode switched on by CDAE_FULL_OUTPUT=1 — every unrated item is a negative, --num_neg is ignored."""
-    yelp = os.path.join(host_bins, "yelp")
+    yelp = YELP
     if not os.path.exists(yelp):
-        pytest.skip("no build/yelp (reference sources were not present at build time)")
+        pytest.skip(NO_YELP)
     write_ratings(tmp_path / "yelp_10core.txt")
     for task in ("prepare", "split"):
         assert run([yelp, f"--task={task}"], tmp_path)[0] == 255
@@ -289,9 +286,9 @@ def test_reference_yelp_app_trains_data_parallel_through_the_c_abi(host_bins, tm
     cdae_hip_multi_* (logical shards of GPU 0 here; distinct ids = one shard per GPU with a library-owned RCCL communicator),
     synchronous and pipelined exchange.  Loss and TOPN rows come from the sharded model; identical seeds give identical tables.
     The user-sharded delta exchange is taken only when asked for BY NAME (round 4: CDAE_DEVICES alone selects the item-rows layout)."""
-    yelp = os.path.join(host_bins, "yelp")
+    yelp = YELP
     if not os.path.exists(yelp):
-        pytest.skip("no build/yelp (reference sources were not present at build time)")
+        pytest.skip(NO_YELP)
     write_ratings(tmp_path / "yelp_10core.txt")
     for task in ("prepare", "split"):
         assert run([yelp, f"--task={task}"], tmp_path)[0] == 255
@@ -316,9 +313,9 @@ def test_reference_yelp_app_trains_data_parallel_through_the_c_abi(host_bins, tm
 def test_reference_yelp_app_trains_full_output_in_the_item_rows_layout(host_bins, tmp_path):
     """CDAE_LAYOUT=item_rows + CDAE_FULL_OUTPUT=1 + CDAE_DEVICES: the unmodified yelp app on the configs[4] layout (logical shards of
     GPU 0).  It is the single-GPU full-output schedule, so its table tracks the single-GPU run's."""
-    yelp = os.path.join(host_bins, "yelp")
+    yelp = YELP
     if not os.path.exists(yelp):
-        pytest.skip("no build/yelp (reference sources were not present at build time)")
+        pytest.skip(NO_YELP)
     write_ratings(tmp_path / "yelp_10core.txt")
     for task in ("prepare", "split"):
         assert run([yelp, f"--task={task}"], tmp_path)[0] == 255
@@ -340,9 +337,9 @@ def test_reference_yelp_app_trains_the_sampled_decode_in_the_item_rows_layout(ho
     """CDAE_DEVICES alone (no CDAE_LAYOUT, no CDAE_FULL_OUTPUT): the unmodified yelp app takes the multi-GPU schedule that carries the
     single-GPU accuracy claim — the sampled decode over item shards (logical shards of GPU 0 here) — BY DEFAULT; CDAE_LAYOUT=item_rows
     names the same thing.  It is the single-GPU schedule, so its `Train Loss` / TOPN table is the single-GPU run's."""
-    yelp = os.path.join(host_bins, "yelp")
+    yelp = YELP
     if not os.path.exists(yelp):
-        pytest.skip("no build/yelp (reference sources were not present at build time)")
+        pytest.skip(NO_YELP)
     write_ratings(tmp_path / "yelp_10core.txt")
     for task in ("prepare", "split"):
         assert run([yelp, f"--task={task}"], tmp_path)[0] == 255
@@ -368,9 +365,9 @@ def test_reference_yelp_app_trains_the_sampled_decode_in_the_item_rows_layout(ho
 def test_reference_yelp_app_trains_the_sibling_models_on_gpu(host_bins, tmp_path, method, loss):
     """--method=MF (libcf::IMF) and --method=BPR through the unmodified yelp app (yelp.cpp:122-165): both run on the GPU behind
     cdae_hip_create_mf.  Train Loss is 0 as in the reference (neither model overrides data_loss); Recall@10 must beat Popularity."""
-    yelp = os.path.join(host_bins, "yelp")
+    yelp = YELP
     if not os.path.exists(yelp):
-        pytest.skip("no build/yelp (reference sources were not present at build time)")
+        pytest.skip(NO_YELP)
     write_ratings(tmp_path / "yelp_10core.txt")
     for task in ("prepare", "split"):
         assert run([yelp, f"--task={task}"], tmp_path)[0] == 255

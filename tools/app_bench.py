@@ -47,7 +47,7 @@ def main():
     df.to_csv(txt, sep=" ", index=False)
     n_users, n_ratings = d.num_users, int(users.size)
     del df, users, items, order
-    yelp = os.path.join(ROOT, "build", "yelp")
+    yelp = os.path.join(ROOT, "oracle", "_ref", "yelp")
     out = {"shape": args.shape, "users": n_users, "ratings": n_ratings, "num_dim": args.num_dim, "threads": args.threads}
     for task in ("prepare", "split"):
         t0 = time.perf_counter()

