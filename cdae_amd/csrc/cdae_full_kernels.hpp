@@ -4,7 +4,7 @@
 // is recommend() (cdae.hpp:176-186).  The north star extends training to "every unrated item is a negative with
 // target 0".  Per block of B users, from the block-start parameters (oracle: Oracle::train_users_full):
 //     Y  = Z D^T + b'            [B x I]    GEMM 1, loss' fused in the epilogue -> G (and G^T), bf16
-//     hg = G D                   [B x K]    GEMM 2, split along the item dimension, fp32 atomics
+//     hg = G D                   [B x K]    GEMM 2, split along the item dimension, partials summed in fixed order
 //     dD = G^T Z                 [I x K]    GEMM 3
 // then one AdaGrad/SGD step per decoder row with dD[j] + lambda D[j] (+ the summed input gradient in tied mode),
 // one per b'[j], and the hidden-layer steps of the sampled path.  With B = 1 this is exactly the reference loop
@@ -15,7 +15,7 @@
 // contraction index contiguous (the per-batch transposed copies D^T, Z^T, G^T make that true), so an MFMA
 // fragment is one 16-byte global load per lane: lane l holds A[m0 + (l & 31)][k0 + 8 (l >> 5) .. +7] and the same
 // slice of Bm's row n0 + (l & 31).  A wavefront owns a 64 x 64 tile of C (2 x 2 MFMA tiles, 64 accumulator
-// VGPRs), a 256-thread workgroup 128 x 128.  Round 1 feeds the fragments straight from L1/L2 (no LDS staging).
+// VGPRs), a 256-thread workgroup 128 x 128.  Round 1 fed the fragments straight from L1/L2 (no LDS staging; removed).
 #pragma once
 #include <type_traits>
 
@@ -121,7 +121,7 @@ to_bf16_transpose_pair_kernel(const float* __restrict__ srcA, uint32_t RA, uint3
   }
 }
 
-enum { EPI_LOSS = 0, EPI_ATOMIC = 1, EPI_STORE = 2 };
+enum { EPI_LOSS = 0, EPI_STORE = 2 };     // (the values name the kernels' instantiations)
 
 struct GemmEpilogue {
   // EPI_LOSS: g = loss'(acc + bp[n], 0) for m < rows_live, n < cols_live, else 0; G[m][n] and GT[n][m] (bf16)
@@ -129,10 +129,10 @@ struct GemmEpilogue {
   __bf16* G; uint32_t ldg;
   __bf16* GT; uint32_t ldgt;
   uint32_t rows_live, cols_live, loss_type;
-  // EPI_ATOMIC / EPI_STORE: fp32 C with row stride ldc (ATOMIC: only rows < rows_live)
+  // EPI_STORE: fp32 C with row stride ldc
   float* Cout; uint32_t ldc;
   // EPI_STORE with a split contraction: split z stores its partial product at Cout + z * split_stride (summed in fixed order
-  // by the consumer: deterministic, unlike EPI_ATOMIC); 0 when the contraction is not split
+  // by the consumer: deterministic); 0 when the contraction is not split
   size_t split_stride;
   // EPI_STORE in gemm_nt_bf16_lds_kernel only (round 4, full-output small shapes on one stream): bias_blocks > 0 = the launch's leading
   // workgroups run the hidden-bias recurrence (hidden_bias_role) over the users whose delta rows start at bias_delta — the first half
@@ -142,7 +142,7 @@ struct GemmEpilogue {
   HyperParams bias_hp;
 };
 
-// Epilogue of one wavefront's 64 x 64 tile (2 x 2 MFMA tiles), shared by the direct and the LDS-staged kernel.
+// Epilogue of one wavefront's 64 x 64 tile (2 x 2 MFMA tiles) of the LDS-staged kernels.
 template <int EPI>
 __device__ __forceinline__ void gemm_tile_epilogue(f32x16 (&acc)[2][2], const uint32_t m_base, const uint32_t n_base, const uint32_t lane,
                                                    const GemmEpilogue& ep) {
@@ -172,56 +172,17 @@ __device__ __forceinline__ void gemm_tile_epilogue(f32x16 (&acc)[2][2], const ui
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
           const uint32_t m = m_base + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-          if constexpr (EPI == EPI_ATOMIC) {
-            if (m < ep.rows_live) unsafeAtomicAdd(ep.Cout + (size_t)m * ep.ldc + n, acc[i][j][r]);
-          } else {
-            ep.Cout[(size_t)m * ep.ldc + n] = acc[i][j][r];
-          }
+          ep.Cout[(size_t)m * ep.ldc + n] = acc[i][j][r];
         }
       }
     }
 }
 
-template <int EPI>
-__global__ void __launch_bounds__(256)
-gemm_nt_bf16_kernel(const __bf16* __restrict__ A, const __bf16* __restrict__ Bm, uint32_t M, uint32_t N, uint32_t Kd,
-                    uint32_t lda, uint32_t ldb, uint32_t k_per_split, GemmEpilogue ep) {
-  const uint32_t lane = threadIdx.x % WAVE, wid = threadIdx.x / WAVE;
-  const uint32_t m_base = blockIdx.y * (blockDim.x / 2) + (wid >> 1) * 64;   // 256 threads: 128 rows per workgroup; 128 threads: 64
-  const uint32_t n_base = blockIdx.x * 128 + (wid & 1) * 64;
-  if (m_base >= M || n_base >= N) return;
-  const uint32_t k_begin = blockIdx.z * k_per_split;
-  const uint32_t k_end = min(Kd, k_begin + k_per_split);
-  f32x16 acc[2][2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-  const uint32_t frag_row = lane & 31, frag_k = (lane >> 5) * 8;
-  const __bf16* a0 = A + (size_t)(m_base + frag_row) * lda + frag_k;
-  const __bf16* a1 = a0 + (size_t)32 * lda;
-  const __bf16* b0 = Bm + (size_t)(n_base + frag_row) * ldb + frag_k;
-  const __bf16* b1 = b0 + (size_t)32 * ldb;
-  for (uint32_t k = k_begin; k < k_end; k += 16) {
-    const bf16x8 fa0 = *reinterpret_cast<const bf16x8*>(a0 + k);
-    const bf16x8 fa1 = *reinterpret_cast<const bf16x8*>(a1 + k);
-    const bf16x8 fb0 = *reinterpret_cast<const bf16x8*>(b0 + k);
-    const bf16x8 fb1 = *reinterpret_cast<const bf16x8*>(b1 + k);
-    acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa0, fb0, acc[0][0], 0, 0, 0);
-    acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa0, fb1, acc[0][1], 0, 0, 0);
-    acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa1, fb0, acc[1][0], 0, 0, 0);
-    acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa1, fb1, acc[1][1], 0, 0, 0);
-  }
-  gemm_tile_epilogue<EPI>(acc, m_base, n_base, lane, ep);
-}
-
-// LDS-staged form of the same NT product for the shapes where it is the whole cost (K > 256: BASELINE configs[4], 1 M items x
+// LDS-staged NT product for the shapes where it is the whole cost (K > 256: BASELINE configs[4], 1 M items x
 // K = 512).  A 256-thread workgroup owns a 128 x 128 tile of C (wavefront: 64 x 64, as above) and walks the contraction in
 // steps of 64: the 128 x 64 slices of A and Bm (16 KiB each) go global -> LDS by 16-byte LDS-DMA (`global_load_lds`: no
 // staging registers, no ds_write pass), double-buffered, and every fragment is one ds_read_b128 shared by the two wavefronts
-// that need it — the direct kernel above moved every fragment through L1 once per wavefront (4 KiB per 4 MFMAs: TA-bound at
+// that need it — round 1's direct kernel moved every fragment through L1 once per wavefront (4 KiB per 4 MFMAs: TA-bound at
 // ~165 TFLOP/s).  LDS image of a slice: row-major, 128-byte rows, lane-linear per DMA instruction (8 rows x 8 sixteen-byte
 // slots); slot c of row r holds source column c ^ ((r >> 1) & 7), which makes the 16-lane groups of ds_read_b128
 // ({0-3,12-15,20-27}, ...: MI355X_MICROARCH.md §LDS) hit 16 distinct slots of the 256-byte bank row.  The permutation is
@@ -719,151 +680,24 @@ gemm_nt_bf16_ldsw_kernel(const __bf16* __restrict__ A, const __bf16* __restrict_
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
           const uint32_t m = m_base + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
-          if constexpr (EPI == EPI_ATOMIC) {
-            if (m < ep.rows_live) unsafeAtomicAdd(C + (size_t)m * ep.ldc + n, acc[i][j][r]);
-          } else {
-            C[(size_t)m * ep.ldc + n] = acc[i][j][r];
-          }
+          C[(size_t)m * ep.ldc + n] = acc[i][j][r];
         }
       }
   }
 }
 
 // ------------------------------------------------------------------------------------------------
-// GEMM 1 of the K = 512 path with the z rows in registers:  G^T[item][user] = loss'(D[item] . z_user + b'[item], 0).
+// GEMM 1 of the K = 512 path:  G^T[item][user] = loss'(D[item] . z_user + b'[item], 0), the two wavefronts of a SIMD in OPPOSITE
+// phases (gemm1_loss_duo_kernel, round 5).
 //
 // The 256 x 256-tile kernel stages BOTH operands of every tile through LDS (512 KiB per tile, 128 flop per staged byte) and is bound
-// by that fill (~32 GB/s per CU), and its loss epilogue runs with nothing else on the CU.  Here a 512-thread workgroup owns 256
-// users for its whole life: wavefront w holds the K = 512 fragments of its 32 users in 128 registers (the MFMA A operand) and the
-// workgroup walks ITEM tiles of 128 — only D is staged (16 KiB slices of 64 k; four stages, three slices in flight: 256 flop per
-// staged byte), and because the stages are a ring of their own the next tile's slices keep arriving while the current tile's loss
-// epilogue runs.  C[user][item] puts four consecutive users of one item into a lane, so bf16(g) goes to a [128 items][256 users]
-// LDS image as 8-byte pieces and leaves as whole 512-byte rows of G^T.  Workgroups that share an item range (the user tiles) sit on
-// ONE XCD, so D comes from HBM once.  Every element is the same sum over k in the same order as gemm_nt_bf16_ldsw_kernel<EPI_LOSS>
-// (16-wide steps ascending): identical G^T (test_gemm1_zreg_changes_no_bit).
-constexpr int G1Z_STAGE_BYTES = 128 * 64 * 2;                    // one D slice: 128 items x 64 k (128-byte rows, swizzled as GEMM_SLICE)
-constexpr uint32_t G1Z_IMG_RS = 528;                             // epilogue image row: 256 users bf16 + 16 B
-constexpr size_t gemm1_zreg_lds_bytes() { return 4 * (size_t)G1Z_STAGE_BYTES + 128 * (size_t)G1Z_IMG_RS; }
-
-template <int LOSS>
-__global__ void __launch_bounds__(512)
-gemm1_loss_zreg_kernel(const __bf16* __restrict__ Zb /* [Bp][512] */, const __bf16* __restrict__ Db /* [Ip][512] */,
-                       const float* __restrict__ bp, __bf16* __restrict__ GT, uint32_t ldgt, uint32_t rows_live, uint32_t cols_live,
-                       uint32_t Ip, uint32_t user_tiles, uint32_t item_groups, uint32_t tiles_per_group) {
-  extern __shared__ __attribute__((aligned(1024))) char smemz[];
-  char* const img = smemz + 4 * G1Z_STAGE_BYTES;
-  const uint32_t lane = threadIdx.x % WAVE, wid = __builtin_amdgcn_readfirstlane(threadIdx.x / WAVE);      // 0..7
-  uint32_t ut, ig;
-  {
-    const uint32_t xcd = blockIdx.x & 7u, j = blockIdx.x >> 3;
-    ut = j % user_tiles; ig = (j / user_tiles) * 8u + xcd;
-    if (ig >= item_groups) return;
-  }
-  const uint32_t n_tiles_all = Ip / 128u;
-  const uint32_t t_begin = ig * tiles_per_group, t_end = min(n_tiles_all, t_begin + tiles_per_group);
-  if (t_begin >= t_end) return;
-  const uint32_t n_tiles = t_end - t_begin, n_slices = n_tiles * 8u;
-  const uint32_t u_tile = ut * 256u;
-  const uint32_t f_row = lane & 31u, f_half = lane >> 5;
-
-  // this wavefront's 32 z rows: fragment kk = k in [16 kk, 16 kk + 16), lane holds the 8 of its half
-  bf16x8 zf[32];
-  {
-    const __bf16* zr = Zb + (size_t)(u_tile + wid * 32u + f_row) * 512u + 8u * f_half;
-#pragma unroll
-    for (int kk = 0; kk < 32; ++kk) zf[kk] = *reinterpret_cast<const bf16x8*>(zr + 16 * kk);
-  }
-  // staging: slice sl = (tile, ks) -> 16 DMA instructions of 1 KiB (8 rows of 128 bytes); wavefront w issues 2 w, 2 w + 1
-  const uint32_t st_row = lane >> 3, st_slot = lane & 7u;
-  auto stage = [&](uint32_t sl) {
-    const uint32_t tile = t_begin + (sl >> 3), ks = sl & 7u;
-    char* base = smemz + (sl & 3u) * G1Z_STAGE_BYTES;
-#pragma unroll
-    for (int q = 0; q < 2; ++q) {
-      const uint32_t r = (wid * 2u + q) * 8u + st_row;
-      const __bf16* src = Db + (size_t)min(tile * 128u + r, Ip - 1u) * 512u + ks * 64u + 8u * (st_slot ^ ((r >> 1) & 7u));
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                       (__attribute__((address_space(3))) void*)(base + (wid * 2u + q) * 1024u), 16, 0, 0);
-    }
-  };
-  uint32_t d_off[4], d_sw[4];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) { const uint32_t r = j * 32u + f_row; d_off[j] = r * 128u; d_sw[j] = (r >> 1) & 7u; }
-
-  stage(0);
-  if (n_slices > 1) stage(1);
-  if (n_slices > 2) stage(2);
-  f32x16 acc[4];
-  uint32_t sl = 0;
-  for (uint32_t t = 0; t < n_tiles; ++t) {
-    const uint32_t item0 = (t_begin + t) * 128u;
-    float bias[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) { const uint32_t n = item0 + j * 32u + f_row; bias[j] = n < cols_live ? bp[n] : 0.f; }
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[j][r] = 0.f;
-#pragma unroll
-    for (int ks = 0; ks < 8; ++ks, ++sl) {
-      // this wavefront's two DMAs of slice sl have landed.  Issued behind them: two per later slice in flight (sl + 1, sl + 2), the
-      // bias loads of this tile (ks == 0: compiler-visible, counted by its own waits) and — for the first three slices of every
-      // tile but the first — the 8 G^T stores of the previous tile's epilogue
-      const uint32_t later = min(2u, n_slices - 1u - sl);
-      const bool stores_behind = t > 0 && ks < 3;
-      if (later == 2u) { if (stores_behind) asm volatile("s_waitcnt vmcnt(12)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); }
-      else if (later == 1u) { if (stores_behind) asm volatile("s_waitcnt vmcnt(10)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(2)" ::: "memory"); }
-      else { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
-      __builtin_amdgcn_s_barrier();                                        // everyone's; the stage slice sl - 1 occupied is free
-      if (sl + 3u < n_slices) stage(sl + 3u);
-      const char* base = smemz + (sl & 3u) * G1Z_STAGE_BYTES;
-#pragma unroll
-      for (int s = 0; s < 4; ++s) {
-        const uint32_t c = 2u * s + f_half;
-        bf16x8 fd[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) fd[j] = *reinterpret_cast<const bf16x8*>(base + d_off[j] + ((c ^ d_sw[j]) << 4));
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(zf[ks * 4 + s], fd[j], acc[j], 0, 0, 0);
-      }
-    }
-    // loss epilogue: lane = item item0 + 32 j + f_row, acc[j][4 q + e] = user u_tile + 32 wid + 8 q + 4 f_half + e
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const bool n_live = item0 + j * 32u + f_row < cols_live;
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const uint32_t ul = wid * 32u + 8u * q + 4u * f_half;
-        float g[4];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const float y = acc[j][4 * q + e] + bias[j];
-          const float v = LOSS == 0 ? 2.f * y : fast_rcp(1.f + fast_exp(-y));
-          g[e] = (n_live && u_tile + ul + e < rows_live) ? v : 0.f;
-        }
-        const bf16x4 hb = {(__bf16)g[0], (__bf16)g[1], (__bf16)g[2], (__bf16)g[3]};
-        *reinterpret_cast<bf16x4*>(img + (j * 32u + f_row) * G1Z_IMG_RS + ul * 2u) = hb;
-      }
-    }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-#pragma unroll
-    for (int q = 0; q < 8; ++q) {
-      const uint32_t pc = threadIdx.x + 512u * q, row = pc >> 5, c16 = pc & 31u;
-      const bf16x8 v = *reinterpret_cast<const bf16x8*>(img + row * G1Z_IMG_RS + c16 * 16u);
-      *reinterpret_cast<bf16x8*>(GT + (size_t)(item0 + row) * ldgt + u_tile + c16 * 8u) = v;      // (nontemporal here: no difference, measured)
-    }
-  }
-}
-
-// ------------------------------------------------------------------------------------------------
-// GEMM 1 of the K = 512 path, round 5: the two wavefronts of a SIMD in OPPOSITE phases (gemm1_loss_duo_kernel; the default).
-//
-// gemm1_loss_zreg_kernel runs its eight wavefronts in lockstep: all contract a tile, then all run its loss epilogue — 64 x (exp, rcp,
-// pack) per lane — with the matrix cores idle (rocprofv3: MFMA busy 42 %; 1.15 ms per launch at 1 M items x 1024 users against 0.52 ms
-// for the contraction and its staging alone).  Round 4 tried the epilogue between the MFMAs of one wavefront (no gain: both wavefronts
-// of a SIMD then want the same issue slots at the same time).  Here the workgroup's two halves — wavefronts 0-3 and 4-7, one of each
-// on every SIMD — alternate roles by PERIOD, one workgroup barrier per period:
+// by that fill (~32 GB/s per CU).  Here a 512-thread workgroup owns 256 users for its whole life: their z rows stay in registers (the
+// MFMA A operand) and only D is staged.  Workgroups that share an item range (the user tiles) sit on ONE XCD, so D comes from HBM once.
+// Round 3's form of this kernel ran its eight wavefronts in lockstep: all contract a tile, then all run its loss epilogue — 64 x (exp,
+// rcp, pack) per lane — with the matrix cores idle (rocprofv3: MFMA busy 42 %; 1.15 ms per launch at 1 M items x 1024 users against
+// 0.52 ms for the contraction and its staging alone; bit-identical, removed).  Round 4 tried the epilogue between the MFMAs of one
+// wavefront (no gain: both wavefronts of a SIMD then want the same issue slots at the same time).  Here the workgroup's two halves —
+// wavefronts 0-3 and 4-7, one of each on every SIMD — alternate roles by PERIOD, one workgroup barrier per period:
 //   period p, t = p / 2:   half (p & 1)      contracts item tile t (64 items, two 32 x 32 accumulators per wavefront: 64 MFMAs back to
 //                                            back, nothing else but their LDS reads in its stream)
 //                          the other half    runs the loss epilogue of the tile it contracted in the period before, stores its G^T
@@ -873,8 +707,8 @@ gemm1_loss_zreg_kernel(const __bf16* __restrict__ Zb /* [Bp][512] */, const __bf
 // is double-buffered WHOLE: tile t is live for periods 2t (first half reads it) and 2t + 1 (second half), tile t + 1 lands meanwhile
 // in the other buffer — no slice-level hand-shake, no image buffer: a lane holds four consecutive users of an item; v_permlane32_swap
 // pairs it with the lane that holds the next four, and G^T leaves in 16-byte pieces (64 contiguous bytes per item row and wavefront).
-// Every element is the same sum over k in the same order (16-wide steps ascending) and the same loss expression as the kernels above:
-// G^T is bit-identical (test_gemm1_zreg_changes_no_bit).
+// Every element is the same sum over k in the same order (16-wide steps ascending) and the same loss expression as
+// gemm_nt_bf16_ldsw_kernel<EPI_LOSS>: G^T is bit-identical (test_gemm1_duo_changes_no_bit).
 __device__ __forceinline__ void wait_vmcnt_at_most(uint32_t n) {     // n is wave-uniform
   switch (n) {
     case 0: __builtin_amdgcn_s_waitcnt(0x0F70); break;
@@ -1152,18 +986,17 @@ __device__ __forceinline__ uint32_t lds_addr_of(const void* p) {
 constexpr uint32_t GTN_RS = 1088;
 // Staging depth and wavefront shape (round 4, measured after the transposing reads became asm — see lds_read_tr16): two 64-row
 // stages 0.94 ms per launch at 1 M items x 1024 users; the same 136 KiB as 32-row stages with two / three of them in flight behind the
-// one being contracted (ROWS = 32, NST = 3 / 4, CDAE_GEMM2_STAGES; counted vmcnt) 0.97 / 0.97; four wavefronts of 128 x 128 outputs (a
-// third fewer LDS reads, built and removed) 1.00.  With parts compiled out (GTN_X_*): no MFMAs 0.83, no fills 0.70, no LDS reads
-// beyond the first sub-step 0.84 — the fills (8.6 GB from the L2s per launch: each G^T piece is staged by two workgroups, each decoder
-// piece by four) and the contraction each take most of the launch and overlap only partly.  All variants bit-identical.
-template <int ROWS, int NST>
-constexpr size_t gemm_tn_lds_bytes() { return (size_t)NST * ROWS * GTN_RS; }
+// one being contracted (counted vmcnt; built, measured and removed) 0.97 / 0.97; four wavefronts of 128 x 128 outputs (a third fewer
+// LDS reads, built and removed) 1.00.  With parts compiled out (GTN_X_*): no MFMAs 0.83, no fills 0.70, no LDS reads beyond the
+// first sub-step 0.84 — the fills (8.6 GB from the L2s per launch: each G^T piece is staged by two workgroups, each decoder piece by
+// four) and the contraction each take most of the launch and overlap only partly.  All variants bit-identical.
+constexpr int GTN_ROWS = 64, GTN_NST = 2;          // contraction rows per stage, stages
+constexpr size_t gemm_tn_lds_bytes() { return (size_t)GTN_NST * GTN_ROWS * GTN_RS; }
 
-template <int ROWS /* contraction rows per stage: 64 or 32 */, int NST /* stages */>
 __global__ void __launch_bounds__(512)
 gemm_tn_bf16_kernel(const __bf16* __restrict__ A, const __bf16* __restrict__ Bm, uint32_t M, uint32_t N, uint32_t Kd,
                     uint32_t lda, uint32_t ldb, uint32_t k_per_split, GemmEpilogue ep, GemmGrid gg) {
-  static_assert(ROWS % 16 == 0 && ROWS % 8 == 0 && NST >= 2 && NST <= 4, "stage shape");
+  constexpr int ROWS = GTN_ROWS, NST = GTN_NST;
   constexpr int STAGE_BYTES = ROWS * (int)GTN_RS;
   constexpr int PER_WAVE = ROWS / 8;                                       // DMA instructions per wavefront and stage
   extern __shared__ __attribute__((aligned(1024))) char smemt[];
@@ -1239,9 +1072,8 @@ gemm_tn_bf16_kernel(const __bf16* __restrict__ A, const __bf16* __restrict__ Bm,
     if ((uint32_t)p < n_steps) stage((uint32_t)p, (uint32_t)p);
   uint32_t slot = 0;
   for (uint32_t step = 0; step < n_steps; ++step) {
-    // this wavefront's DMAs of slice `step` have landed: the stages behind it (at most NST - 2 of them) stay in flight
-    const uint32_t behind = min((uint32_t)(NST - 2), n_steps - 1u - step);
-    wait_vmcnt_at_most(behind * (uint32_t)PER_WAVE);
+    // this wavefront's DMAs of slice `step` have landed (two stages: nothing else is in flight)
+    wait_vmcnt_at_most(0u);
     asm volatile("" ::: "memory");
     __builtin_amdgcn_s_barrier();                                          // ... and everyone else's; the stage of slice step-1 is free
     if (step + (uint32_t)(NST - 1) < n_steps && !(GTN_X_NODMA && step > 2u)) stage(step + (uint32_t)(NST - 1), (slot + (uint32_t)(NST - 1)) % (uint32_t)NST);
@@ -1255,18 +1087,16 @@ gemm_tn_bf16_kernel(const __bf16* __restrict__ A, const __bf16* __restrict__ Bm,
     __builtin_amdgcn_sched_barrier(0);
     GTN_MFMA(fa0, fb0);
     __builtin_amdgcn_sched_barrier(0);
-    if constexpr (ROWS == 64) {
-      lgkm_wait<0>(fa1, fb1);
-      GTN_READ(fa0, fb0, 2);
-      __builtin_amdgcn_sched_barrier(0);
-      GTN_MFMA(fa1, fb1);
-      __builtin_amdgcn_sched_barrier(0);
-      lgkm_wait<0>(fa0, fb0);
-      GTN_READ(fa1, fb1, 3);
-      __builtin_amdgcn_sched_barrier(0);
-      GTN_MFMA(fa0, fb0);
-      __builtin_amdgcn_sched_barrier(0);
-    }
+    lgkm_wait<0>(fa1, fb1);
+    GTN_READ(fa0, fb0, 2);
+    __builtin_amdgcn_sched_barrier(0);
+    GTN_MFMA(fa1, fb1);
+    __builtin_amdgcn_sched_barrier(0);
+    lgkm_wait<0>(fa0, fb0);
+    GTN_READ(fa1, fb1, 3);
+    __builtin_amdgcn_sched_barrier(0);
+    GTN_MFMA(fa0, fb0);
+    __builtin_amdgcn_sched_barrier(0);
     lgkm_wait<0>(fa1, fb1);                                                // (all of this stage's reads are done before the next barrier)
     GTN_MFMA(fa1, fb1);
     slot = slot + 1u == (uint32_t)NST ? 0u : slot + 1u;

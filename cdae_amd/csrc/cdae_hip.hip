@@ -76,6 +76,9 @@ int fail(const char* fmt, ...) {
   } while (0)
 
 constexpr uint32_t MF_SEQ_USERS = 256;     // IMF / BPR sequential default: users per launch window (cdae_hip::mf_seq)
+// batches above this many users take the two-launch encode (a workgroup of 16 wavefronts per user is mostly idle wavefronts;
+// full-output: 512 users -7 % per step with one launch, 1024 +2 %, 2048 +11 %; sampled: equal at 1024, +4 % at 2048)
+constexpr uint32_t ENCODE_USERS_MAX = 768;
 enum Family { F_SAMPLE = 0, F_SORT, F_ENCODE, F_DECODE, F_HIDDEN, F_INPUT, F_COUNT };
 
 struct Span { int family; hipEvent_t a, b; };
@@ -111,8 +114,6 @@ struct cdae_hip {
   uint32_t* h_err = nullptr;        // host address (a slot of the process-wide pool below: one mapped page per device, not one per handle)
   int err_slot = -1;
   uint32_t* d_fused_err = nullptr;  // the same word as the device sees it
-  uint32_t* d_hot_cnt = nullptr;    // [hot workgroups] wavefronts of the popular rows finished so far (the fused launch's blockers wait on it)
-  uint32_t fused_seq = 0;           // fused launches so far (wraps with the counters)
   cdae::FusedGeom fused_geo{};      // geometry of this handle's fused launch (set at the first one)
   bool fused_geo_set = false;
   std::vector<float> h_rank_len;    // [I] expected examples per batch of the row of popularity rank r (fused launch: balancing the four-row groups over the SIMDs)
@@ -121,11 +122,7 @@ struct cdae_hip {
   cdae::DecodeLate decode_late() const { return cdae::DecodeLate{d_Ghot, d_hotdup, late_rows}; }
   cdae::LateFinish late_finish() { return cdae::LateFinish{d_Ghot, d_hotdup, d_item_order, d_D0, d_dup_corr, late_rows}; }
   // developer switches, read once in cdae_hip_create (DESIGN.md lists them)
-  bool one_row_per_wave = false;    // CDAE_DECODE_ONE_ROW_PER_WAVE: every row on the 64-lane decode path
   bool full_unfused = false;        // CDAE_FULL_UNFUSED: full-output decode as three separate GEMMs
-  bool gemm_direct = false;         // CDAE_GEMM_DIRECT: the fragment-from-L1 GEMM kernel instead of the LDS-staged one (A/B switch)
-  bool gemm_two_stage = false;      // CDAE_GEMM_TWO_STAGE: always the 128 x 128 two-stage LDS kernel (A/B switch)
-  bool recommend_per_user = false;  // CDAE_RECOMMEND_PER_USER: recommend_kernel instead of the MFMA path
   std::vector<uint32_t> h_unit_ptr;     // prefix of work units (<= hp.unit_pos positives each) per user
   uint32_t* d_rank_of = nullptr;        // [I] inverse of d_item_order
   uint32_t* d_unit_user = nullptr;      // [total units] user of every unit (kernels' unit -> user look-up)
@@ -195,8 +192,6 @@ struct cdae_hip {
   // 0.055, 512: 0.083 -> 0.067 / 0.124 -> 0.106, 1024: 0.099 -> 0.088 / 0.145 -> 0.132, 2048: - / 0.197 -> 0.188, 4096: - / 0.327 -> 0.327
   // — a hand-off between two streams costs ~15 us, the recurrence 41 ns per user
   uint32_t full_one_stream_max = 2048;
-  bool full_bias_unsplit = false;       // CDAE_FULL_BIAS_UNSPLIT: the whole recurrence beside the row launch (A/B)
-  bool fused_images = true;             // CDAE_FULL_SEPARATE_COPIES turns it off (developer switch: conversion launches as in round 2)
   hipStream_t aux = nullptr;            // full-output path: the hidden-bias recurrence beside GEMM 3
   hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_delta = nullptr;
   bool join_pending = false;            // full-output path: the aux stream's b recurrence of the last batch has not been joined yet
@@ -230,10 +225,6 @@ struct cdae_hip {
   std::atomic<int> worker_failed{0};
   std::string worker_error;             // valid once worker_failed != 0
   std::mutex prof_mu;                   // spans / event pool are touched by both threads when profiling
-  uint32_t gather_halves = 1;           // wavefronts per (unit, item partition) in hidden_gather_kernel (CDAE_GATHER_HALVES = 1 | 2; 2 measured slower)
-  uint32_t encode_users_max = 768;      // batches above this many users take the two-launch encode (a workgroup of 16 wavefronts per user is
-                                        // mostly idle wavefronts; full-output: 512 users -7 % per step with one launch, 1024 +2 %, 2048 +11 %; sampled: equal at 1024, +4 % at 2048); CDAE_ENCODE_USERS_MAX
-  bool full_separate_copies = false;    // CDAE_FULL_SEPARATE_COPIES: D and Z bf16 copies as two launches (developer switch)
   bool encode_two_launches = false;     // CDAE_ENCODE_TWO_LAUNCHES: the training encode as encode_partial + encode_finish (developer switch)
   bool debug_skip_prep = false;         // CDAE_DEBUG_SKIP_PREP (timing experiment only: batches reuse stale example lists -> WRONG results)
   // bucket_sort_kernel (cdae_sort_kernels.hpp): the default item-major ordering — one narrow launch; item ranges cut at set_interactions
@@ -248,13 +239,10 @@ struct cdae_hip {
   bool gemm3_attr_set[8] = {false, false, false, false, false, false, false, false};   // launch_gemm_lds: dynamic-LDS attribute set on this handle's device, per epilogue
   bool gemmw_attr_set[8] = {false, false, false, false, false, false, false, false};   // ... of the 256 x 256-tile kernel
   bool gemm_narrow = false;             // CDAE_GEMM_NARROW: never the 256 x 256-tile kernel (A/B switch)
-  bool gemm1_tiled = false;             // CDAE_GEMM1_TILED: GEMM 1 as the 256 x 256-tile kernel where gemm1_loss_zreg_kernel would run (A/B switch)
-  bool gemm1_zreg_attr_set[2] = {false, false};   // dynamic-LDS attribute of gemm1_loss_zreg_kernel<LOSS> set on this handle's device
-  bool gemm1_zreg = false;              // CDAE_GEMM1_ZREG: round 3's gemm1_loss_zreg_kernel (eight wavefronts in lockstep) where gemm1_loss_duo_kernel runs (A/B switch)
-  bool gemm1_duo_attr_set[2] = {false, false};
+  bool gemm1_tiled = false;             // CDAE_GEMM1_TILED: GEMM 1 as the 256 x 256-tile kernel where gemm1_loss_duo_kernel would run (A/B switch)
+  bool gemm1_duo_attr_set[2] = {false, false};   // dynamic-LDS attribute of gemm1_loss_duo_kernel<LOSS> set on this handle's device
   bool fused_attr_set = false;          // dynamic-LDS attribute of this handle's full_decode_fused_kernel instance set (one K and loss per handle)
   bool gemm2_nt = false;                // CDAE_GEMM2_NT: hg = G D from G and D^T (gemm_nt_bf16_ldsw_kernel) where gemm_tn_bf16_kernel would read G^T and D (A/B switch)
-  int gemm2_stages = 2;                 // CDAE_GEMM2_STAGES: LDS stages of gemm_tn_bf16_kernel (2 = 64-row stages; 3 / 4 = 32-row stages, measured no faster)
   bool gemm_tn_attr_set = false;        // dynamic-LDS attribute of gemm_tn_bf16_kernel set on this handle's device
   bool rows_separate = false;           // CDAE_FULL_ROWS_SEPARATE: GEMM 3 and the row step as two launches where gemm3_rows_fused_kernel would run (A/B switch)
   bool fused_rows_attr_set[2][2] = {};      // dynamic-LDS attribute of gemm3_rows_fused_kernel<ADA, KH> set on this handle's device
@@ -329,7 +317,6 @@ struct cdae_hip {
   float* dec() { return cfg.asymmetric ? P(CDAE_P_V) : P(CDAE_P_W); }
   float* dec_ag() { return cfg.asymmetric ? P(CDAE_P_V_AG) : P(CDAE_P_W_AG); }
   float* delta_rows() { return cfg.linear_function ? d_delta_rows : d_HG; }
-  bool full_unfused_nt() const { return gemm_direct || gemm_two_stage || gemm_narrow; }   // developer switches that select one of the older NT kernels for all three products
 };
 
 namespace {
@@ -455,7 +442,7 @@ void free_all(cdae_hip* h) {
                   h->d_base, h->d_delta, h->d_recv, h->d_snap, h->d_dup_corr, h->d_unit_user, h->d_zeval, h->d_bits, h->d_hpart_eval, h->d_iota, h->d_bits_train,
                   h->d_Uu, h->d_Uu_ag, h->d_Ssum, h->d_delta_rows, h->d_score, h->d_Hsum, h->d_hsum_eval, h->d_iota_eval, h->d_rec_score, h->d_gpos, h->d_ub, h->d_ub_ag, h->d_UVpre, h->d_rank_of,
                   h->d_grow_ptr, h->d_gcol, h->d_gunit_ptr, h->d_gunit_user, h->d_test_ptr, h->d_test_col, h->d_topn_pu, h->d_topn_out, h->d_bucket_cut, h->d_range_of,
-                  h->d_Ghot, h->d_hotdup, h->d_late_bits, h->d_hot_cnt, h->d_cold_map};
+                  h->d_Ghot, h->d_hotdup, h->d_late_bits, h->d_cold_map};
   for (void* p : ptrs) if (p) (void)hipFree(p);
   for (auto& b : h->ex) {
     void* q[] = {b.item, b.val, b.sorted_item, b.sorted_val, b.seg, b.dup_of_pos, b.dup_of_ex, b.dup_count, b.key16, b.sorted_key16,
@@ -498,7 +485,7 @@ int free_interaction_state(cdae_hip* h) {
                    (void**)&h->d_Hsum, (void**)&h->d_hsum_eval, (void**)&h->d_iota_eval, (void**)&h->d_rec_score, (void**)&h->d_gpos, (void**)&h->d_ub, (void**)&h->d_ub_ag, (void**)&h->d_UVpre, (void**)&h->d_rank_of,
                    (void**)&h->d_grow_ptr, (void**)&h->d_gcol, (void**)&h->d_gunit_ptr, (void**)&h->d_gunit_user,
                    (void**)&h->d_test_ptr, (void**)&h->d_test_col, (void**)&h->d_topn_pu, (void**)&h->d_topn_out, (void**)&h->d_bucket_cut, (void**)&h->d_range_of,
-                   (void**)&h->d_Ghot, (void**)&h->d_hotdup, (void**)&h->d_late_bits, (void**)&h->d_hot_cnt, (void**)&h->d_cold_map};
+                   (void**)&h->d_Ghot, (void**)&h->d_hotdup, (void**)&h->d_late_bits, (void**)&h->d_cold_map};
   for (auto& b : h->ex) {
     void** q[] = {(void**)&b.item, (void**)&b.val, (void**)&b.sorted_item, (void**)&b.sorted_val, (void**)&b.seg,
                   (void**)&b.dup_of_pos, (void**)&b.dup_of_ex, (void**)&b.dup_count, (void**)&b.key16, (void**)&b.sorted_key16,
@@ -624,33 +611,17 @@ int prep_batch(cdae_hip* h, int b, const Batch& bt, uint64_t seed, uint32_t epoc
   return 0;
 }
 
-// K3 on the main stream: the decode of example-buffer set `x` over this handle's item rows (shared by the single-handle step and
-// the sampled item-shard step)
-// Geometry of the fused launch, once per handle: how many workgroups of the launch a CU holds decides the blocker rounds.
-template <int NV, int NT>
+// Geometry of the fused launch (decode_gather_kernel), once per handle.
 int fused_geometry(cdae_hip* h, uint32_t hot, uint32_t I) {
   using namespace cdae;
   FusedGeom g{};
   g.hot_wgs = (hot + 3) / 4;
-  g.stride = h->num_cus;
-  g.blocked = std::min<uint32_t>(g.hot_wgs, FUSED_BLOCK_MAX);
-  int per_cu = 0;
-  const bool ce = h->cfg.loss_type == CDAE_LOSS_CROSS_ENTROPY, ada = h->cfg.using_adagrad != 0;
-  if (ce && ada) HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, decode_gather_kernel<NV, NT, 5, true>, 256, 0));
-  else if (ce) HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, decode_gather_kernel<NV, NT, 5, false>, 256, 0));
-  else if (ada) HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, decode_gather_kernel<NV, NT, 0, true>, 256, 0));
-  else HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, decode_gather_kernel<NV, NT, 0, false>, 256, 0));
-  // Blockers are OFF in the shipped launch (rounds = 0): measured, they buy nothing (0.0924 with, 0.0919 without: the long-lived four-row
-  // wavefronts are not the popular rows' neighbours), and a blocker that waits in vain is the one wait of this launch that costs time
-  // without raising an error.  CDAE_FUSED_BLOCK_ROUNDS = n (developer switch) brings them back; -1 = one round per resident workgroup.
-  g.rounds = 0;
-  if (const char* ev = DEV_ENV("CDAE_FUSED_BLOCK_ROUNDS")) g.rounds = std::atoi(ev) < 0 ? (uint32_t)std::max(0, std::min(per_cu, 8) - 1) : (uint32_t)std::atoi(ev);
   // The four-row groups are dealt to (CU, SIMD) bins so that every SIMD gets about the same number of example steps (longest group first,
   // each to the lightest bin): a group lasts as long as its longest row, the SIMDs are VALU-bound on these wavefronts, and in index
   // order (round 5) the SIMDs that held the most popular groups finished 10-15 us after the others — which every gather wavefront of
   // this launch then waits for.  Workgroup b's wavefront w runs on SIMD w of CU b mod S (observed placement: only the balance depends
-  // on it): the k-th group of bin (cu, w) goes to workgroup cu + k S.  The popular rows' CUs (and their blockers') take no group.
-  const uint32_t n_groups = (I - hot + 3) / 4, S = g.stride;
+  // on it): the k-th group of bin (cu, w) goes to workgroup cu + k S.  The popular rows' CUs take no group.
+  const uint32_t n_groups = (I - hot + 3) / 4, S = h->num_cus;
   std::vector<float> len(n_groups, 0.f);
   for (uint32_t q = 0; q < n_groups; ++q)
     for (uint32_t j = 0; j < 4 && hot + 4 * q + j < I; ++j) len[q] = std::max(len[q], h->h_rank_len[hot + 4 * q + j]);
@@ -667,10 +638,8 @@ int fused_geometry(cdae_hip* h, uint32_t hot, uint32_t I) {
     for (uint32_t i = 0; i < n_bins; ++i) heap.push_back({0.f, i});
     auto cmp = [](const Ent& a, const Ent& b2) { return a.first > b2.first || (a.first == b2.first && a.second > b2.second); };
     std::make_heap(heap.begin(), heap.end(), cmp);
-    const bool balance = DEV_ENV("CDAE_FUSED_INDEX_ORDER") == nullptr;                   // (developer switch: round 5's index order)
     for (uint32_t k = 0; k < n_groups; ++k) {
-      const uint32_t q = balance ? by_len[k] : k;
-      if (!balance) { bin[k % n_bins].push_back(q); continue; }
+      const uint32_t q = by_len[k];
       std::pop_heap(heap.begin(), heap.end(), cmp);
       Ent e = heap.back();
       bin[e.second].push_back(q);
@@ -681,7 +650,7 @@ int fused_geometry(cdae_hip* h, uint32_t hot, uint32_t I) {
   }
   size_t rounds_cold = 0;
   for (auto& v : bin) rounds_cold = std::max(rounds_cold, v.size());
-  // cold round k of CU cu is workgroup index cu + k S, except that on the popular CUs' indices there are blockers in rounds 1..rounds
+  // cold round k of CU cu is workgroup index cu + k S
   g.decode_wgs = (uint32_t)std::max<size_t>(rounds_cold, 1) * S;
   std::vector<uint32_t> map((size_t)g.decode_wgs * 4, 0xFFFFFFFFu);
   for (uint32_t i = 0; i < n_bins; ++i) {
@@ -697,6 +666,8 @@ int fused_geometry(cdae_hip* h, uint32_t hot, uint32_t I) {
   return 0;
 }
 
+// K3 on the main stream: the decode of example-buffer set `x` over this handle's item rows (shared by the single-handle step and
+// the sampled item-shard step)
 // fused != nullptr: the fused launch (decode_gather_kernel) with these gather arguments; the caller then launches no hidden_gather_kernel
 int launch_decode(cdae_hip* h, cdae_hip::ExBuf& x, const cdae::GatherArgs* fused = nullptr) {
   using namespace cdae;
@@ -722,8 +693,6 @@ int launch_decode(cdae_hip* h, cdae_hip::ExBuf& x, const cdae::GatherArgs* fused
   // K <= 256: hot rows one per wavefront, all others four per wavefront (NV float4 pieces + NT tail scalars per lane)
 #define DECODE_HY(NV_, NT_)                                                                                           \
   do {                                                                                                                \
-    if (fused && !h->fused_geo_set) { CHK((fused_geometry<NV_, NT_>(h, hot, I))); geo = h->fused_geo; geo.hot_target = 4u * h->fused_seq; geo.hot_cnt = h->d_hot_cnt; \
-                                      grid_fu = dim3(geo.decode_wgs + gather_wgs); }                                  \
     if (fused) {                                                                                                       \
       if (ce && ada) hipLaunchKernelGGL((decode_gather_kernel<NV_, NT_, 5, true>), grid_fu, blk, 0, st, h->hp, hot, geo, late, *fused, DECODE_TAIL);   \
       else if (ce) hipLaunchKernelGGL((decode_gather_kernel<NV_, NT_, 5, false>), grid_fu, blk, 0, st, h->hp, hot, geo, late, *fused, DECODE_TAIL);    \
@@ -742,19 +711,15 @@ int launch_decode(cdae_hip* h, cdae_hip::ExBuf& x, const cdae::GatherArgs* fused
   {
     const bool ce = h->cfg.loss_type == CDAE_LOSS_CROSS_ENTROPY, ada = h->cfg.using_adagrad != 0, pad = h->K < h->Kp;
     const uint32_t K = h->K;
-    if (K <= 256 && !h->one_row_per_wave) {
+    if (K <= 256) {
       const uint32_t hot = std::min<uint32_t>(h->hot_rows, I);
       const uint32_t waves = hot + (I - hot + 3) / 4;
       const dim3 grid_hy((waves + 3) / 4);
       const DecodeLate late = h->decode_late();
-      // fused launch (decode_gather_kernel): [popular rows] [the other rows, with the blockers' indices among them] [gather]
-      FusedGeom geo = h->fused_geo;
-      if (fused) {
-        geo.hot_target = 4u * ++h->fused_seq;
-        geo.hot_cnt = h->d_hot_cnt;
-      }
-      const uint32_t gather_wgs = fused ? 8u * ((fused->n_units + 3u) / 4u) : 0u;
-      dim3 grid_fu(geo.decode_wgs + gather_wgs);
+      // fused launch (decode_gather_kernel): [popular rows] [the other rows] [gather]
+      if (fused && !h->fused_geo_set) CHK(fused_geometry(h, hot, I));
+      const FusedGeom geo = h->fused_geo;
+      const dim3 grid_fu(geo.decode_wgs + (fused ? 8u * ((fused->n_units + 3u) / 4u) : 0u));
       const uint32_t nv = K / 64, tail = K % 64;
       const uint32_t nt = tail == 0 ? 0u : (tail < 16 ? 1u : (tail < 32 ? 2u : 4u));   // 16 nt > tail: room for b'
       if (nt == 0) {
@@ -797,12 +762,11 @@ int compute_batch(cdae_hip* h, int b, const Batch& bt, uint64_t seed, uint32_t e
   const dim3 grid_units((n_units + 3) / 4);
   // The fused launch (decode + gather, decode_gather_kernel): plain batches of a handle that has late rows.  The batch's encode then
   // fills G with G_PENDING (the gather wavefronts wait on it), whichever encode form runs.
-  const uint32_t halves = h->gather_halves;
-  const bool fused = h->fused_decode && !explicit_in && halves == 1u && n_units > 0u && bt.E > 0u && bt.E < (1ull << 32);
+  const bool fused = h->fused_decode && !explicit_in && n_units > 0u && bt.E > 0u && bt.E < (1ull << 32);
   float* const ghot = h->late_rows ? h->d_Ghot : nullptr;
   uint32_t* const gfill = fused ? reinterpret_cast<uint32_t*>(h->d_G) : nullptr;
   const uint32_t n_fill = fused ? (uint32_t)bt.E : 0u;
-  if (!explicit_in && !h->encode_two_launches && nb <= h->encode_users_max) {
+  if (!explicit_in && !h->encode_two_launches && nb <= ENCODE_USERS_MAX) {
     // one launch: a workgroup per user (encode_users_kernel)
     DISPATCH_NI(h->NI, encode_users_kernel, dim3(nb), dim3(ENC_WAVES * WAVE), 0, st, h->hp, h->d_row_ptr, h->d_col, h->P(CDAE_P_W), uptr, s0, nb,
                 bt.cidx, seed, epoch, h->d_Wu, h->P(CDAE_P_B), h->d_Z, h->d_Dz, h->d_HG, h->d_Uu, h->d_Ssum,
@@ -820,7 +784,7 @@ int compute_batch(cdae_hip* h, int b, const Batch& bt, uint64_t seed, uint32_t e
 
   if (!h->skip_ready_wait) HIPCHK(hipStreamWaitEvent(st, x.ready, 0));
   const GatherArgs ga{h->d_row_ptr, uptr, n_units, s0, nb, x.item, h->d_G, h->d_D0, h->d_HGpart, explicit_in ? (uint32_t)bt.E : 0u, x.dup_of_ex,
-                      h->d_dup_corr, explicit_in ? (const uint32_t*)nullptr : (const uint32_t*)h->d_unit_user, halves,
+                      h->d_dup_corr, explicit_in ? (const uint32_t*)nullptr : (const uint32_t*)h->d_unit_user,
                       h->late_rows ? (const uint32_t*)h->d_late_bits : (const uint32_t*)nullptr, h->late_words, h->d_fused_err};
   CHK(pr.begin(h, F_DECODE, st));
   CHK(launch_decode(h, x, fused ? &ga : nullptr));
@@ -828,11 +792,11 @@ int compute_batch(cdae_hip* h, int b, const Batch& bt, uint64_t seed, uint32_t e
 
   CHK(pr.begin(h, F_HIDDEN, st));
   if (!fused)
-    DISPATCH_NI(h->NI, hidden_gather_kernel, dim3(8 * halves * ((n_units + 3) / 4)), blk, 0, st, h->hp, ga.row_ptr, uptr, n_units, s0, nb,
-                x.item, h->d_G, h->d_D0, h->d_HGpart, ga.explicit_examples, x.dup_of_ex, h->d_dup_corr, ga.unit_user, halves,
+    DISPATCH_NI(h->NI, hidden_gather_kernel, dim3(8 * ((n_units + 3) / 4)), blk, 0, st, h->hp, ga.row_ptr, uptr, n_units, s0, nb,
+                x.item, h->d_G, h->d_D0, h->d_HGpart, ga.explicit_examples, x.dup_of_ex, h->d_dup_corr, ga.unit_user,
                 ga.late_bits, ga.late_words);
   DISPATCH_NI(h->NI, hidden_finish_kernel, dim3(nb), blk, 0, st, h->hp, uptr, n_units, s0, nb, h->d_HGpart, h->d_Dz, h->d_HG,
-              h->d_Wu, h->d_Wu_ag, 8u * halves, h->d_Uu, h->d_Uu_ag, h->d_Ssum, h->d_delta_rows, (const float*)nullptr, h->late_finish());
+              h->d_Wu, h->d_Wu_ag, 8u, h->d_Uu, h->d_Uu_ag, h->d_Ssum, h->d_delta_rows, (const float*)nullptr, h->late_finish());
   CHK(pr.end());
   // input rows + (leading workgroups) the strictly sequential hidden-bias recurrence: both need only delta
   CHK(pr.begin(h, F_INPUT, st));
@@ -854,7 +818,7 @@ int launch_gemm_lds(cdae_hip* h, hipStream_t st, const __bf16* A, const __bf16* 
                     uint32_t ldb, uint32_t kps, const cdae::GemmEpilogue& ep, uint32_t splits, uint32_t mode) {
   using namespace cdae;
   const uint32_t Nt = (N + 127) / 128;
-  if (M % 256 == 0 && N % 256 == 0 && !h->gemm_two_stage && !h->gemm_narrow) {
+  if (M % 256 == 0 && N % 256 == 0 && !h->gemm_narrow) {
     // 256 x 256 tiles (round 3): 128 flop per byte staged into LDS instead of 85
     if (!h->gemmw_attr_set[EPI]) {
       HIPCHK(hipFuncSetAttribute((const void*)gemm_nt_bf16_ldsw_kernel<EPI>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)gemmw_lds_bytes()));
@@ -865,7 +829,7 @@ int launch_gemm_lds(cdae_hip* h, hipStream_t st, const __bf16* A, const __bf16* 
                        kps, ep, gg);
     return 0;
   }
-  if (M % 256 == 0 && !h->gemm_two_stage) {
+  if (M % 256 == 0) {
     if (!h->gemm3_attr_set[EPI]) {     // per handle: the attribute belongs to the (function, device) pair
       HIPCHK(hipFuncSetAttribute((const void*)gemm_nt_bf16_lds3_kernel<EPI>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)gemm3s_lds_bytes()));
       h->gemm3_attr_set[EPI] = true;
@@ -880,11 +844,6 @@ int launch_gemm_lds(cdae_hip* h, hipStream_t st, const __bf16* A, const __bf16* 
   }
   return 0;
 }
-// does launch_gemm_lds take the 128 x 128 kernel — the one that can host a bias role (GemmEpilogue::bias_blocks) — for this shape?
-bool gemm_lds_is_128(const cdae_hip* h, uint32_t M, uint32_t N) {
-  if (M % 256 == 0 && N % 256 == 0 && !h->gemm_two_stage && !h->gemm_narrow) return false;
-  return !(M % 256 == 0 && !h->gemm_two_stage);
-}
 
 // contraction split of GEMM 2 (hg = G D, K > 256 / unfused path): about 2048 workgroups in all, splits a multiple of 64 items
 uint32_t gemm2_k_per_split(const cdae_hip* h) {
@@ -896,11 +855,11 @@ uint32_t gemm2_k_per_split(const cdae_hip* h) {
 // GEMM 2 of the K > 256 path from G^T and the row-major decoder image (gemm_tn_bf16_kernel): then GEMM 1 writes no G and nothing reads D^T
 bool gemm2_tn_path(const cdae_hip* h) {
   // (rows and columns of GEMM 1 in multiples of 256: it is then the 256 x 256-tile kernel, whose loss epilogue knows how to leave G out)
-  return h->Kp > 256 && h->Kp % 256 == 0 && h->Bp % 256 == 0 && h->Ip % 256 == 0 && !h->full_unfused_nt() && !h->gemm2_nt;
+  return h->Kp > 256 && h->Kp % 256 == 0 && h->Bp % 256 == 0 && h->Ip % 256 == 0 && !h->gemm_narrow && !h->gemm2_nt;
 }
 // GEMM 3 + row step in one launch (gemm3_rows_fused_kernel): Kp = 512 over item spaces >= 32768, i.e. BASELINE configs[4]'s path
 bool rows_fused_path(const cdae_hip* h) {
-  return h->Kp == 512 && h->I >= 32768 && h->Ip % cdae::FR_ITEMS == 0 && h->fused_images && !h->gemm_direct && !h->rows_separate;
+  return h->Kp == 512 && h->I >= 32768 && h->Ip % cdae::FR_ITEMS == 0 && !h->rows_separate;
 }
 int launch_rows_fused(cdae_hip* h, hipStream_t st, const cdae_hip::ExBuf& x, uint32_t nb, __bf16* Db) {
   using namespace cdae;
@@ -929,8 +888,7 @@ int launch_rows_fused(cdae_hip* h, hipStream_t st, const cdae_hip::ExBuf& x, uin
 
 // The unfused (K > 256, or CDAE_FULL_UNFUSED) forward product with its loss epilogue, the positive fix-up and the hidden-gradient
 // product of one block — shared by the single-handle step (compute_batch_full) and the item shard's phase 1 (fs_phase1: the same
-// launches over the shard's own item rows).  *parts / *rows: the slabs of HGpart holding the partial hg and their row count
-// (0 parts: accumulated into d_HG by atomics, the CDAE_GEMM_DIRECT developer path).
+// launches over the shard's own item rows).  *parts / *rows: the slabs of HGpart holding the partial hg and their row count.
 int full_products_k512(cdae_hip* h, hipStream_t st, cdae_hip::ExBuf& x, const Batch& bt, uint32_t nb, uint32_t* parts, uint32_t* rows) {
   using namespace cdae;
   const uint32_t I = (uint32_t)h->I, Kp = h->Kp, Bp = h->Bp, Ip = h->Ip;
@@ -940,42 +898,25 @@ int full_products_k512(cdae_hip* h, hipStream_t st, cdae_hip::ExBuf& x, const Ba
   ep.bp = h->P(CDAE_P_BP); ep.G = tn2 ? (__bf16*)nullptr : h->d_Gb; ep.ldg = Ip; ep.GT = h->d_GTb; ep.ldgt = Bp;
   ep.rows_live = nb; ep.cols_live = I; ep.loss_type = h->cfg.loss_type;
   // GEMM 1: Y = Z D^T (+ b'), g = loss'(y, 0) -> G [Bp x Ip] (unless GEMM 2 reads G^T), G^T [Ip x Bp]
-  if (h->gemm_direct)
-    hipLaunchKernelGGL((gemm_nt_bf16_kernel<EPI_LOSS>), dim3(Ip / 128, Bp / 128, 1), blk, 0, st, h->d_Zb, h->d_Db, Bp, Ip, Kp, Kp, Kp,
-                       Kp, ep);
-  else if (tn2 && Kp == 512 && !h->gemm1_tiled) {
-    // the z rows of 256 users in registers, only D staged (gemm1_loss_zreg_kernel): G^T alone, which is all GEMM 2 (TN) and GEMM 3 read
+  if (tn2 && Kp == 512 && !h->gemm1_tiled) {
+    // the z rows of 256 users in registers, only D staged, the two wavefronts of a SIMD in opposite phases — one contracts while the
+    // other runs its loss epilogue (gemm1_loss_duo_kernel): G^T alone, which is all GEMM 2 (TN) and GEMM 3 read
     const uint32_t user_tiles = Bp / 256, n_tiles = Ip / 128;
     const uint32_t item_groups = std::min<uint32_t>(((std::max<uint32_t>(1u, 256u / user_tiles) + 7u) / 8u) * 8u, ((n_tiles + 7u) / 8u) * 8u);
     const uint32_t tiles_per_group = (n_tiles + item_groups - 1) / item_groups;
     const dim3 grid(8u * user_tiles * ((item_groups + 7u) / 8u));
     const bool ce = h->cfg.loss_type == CDAE_LOSS_CROSS_ENTROPY;
-    if (!h->gemm1_zreg) {
-      // round 5 default: the two wavefronts of a SIMD in opposite phases — one contracts while the other runs its loss epilogue (gemm1_loss_duo_kernel)
-      if (!h->gemm1_duo_attr_set[ce]) {
-        if (ce) HIPCHK(hipFuncSetAttribute((const void*)gemm1_loss_duo_kernel<5>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)gemm1_duo_lds_bytes()));
-        else HIPCHK(hipFuncSetAttribute((const void*)gemm1_loss_duo_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)gemm1_duo_lds_bytes()));
-        h->gemm1_duo_attr_set[ce] = true;
-      }
-      if (ce)
-        hipLaunchKernelGGL(gemm1_loss_duo_kernel<5>, grid, dim3(512), gemm1_duo_lds_bytes(), st, (const __bf16*)h->d_Zb, (const __bf16*)h->d_Db,
-                           (const float*)h->P(CDAE_P_BP), h->d_GTb, Bp, nb, I, Ip, user_tiles, item_groups, tiles_per_group);
-      else
-        hipLaunchKernelGGL(gemm1_loss_duo_kernel<0>, grid, dim3(512), gemm1_duo_lds_bytes(), st, (const __bf16*)h->d_Zb, (const __bf16*)h->d_Db,
-                           (const float*)h->P(CDAE_P_BP), h->d_GTb, Bp, nb, I, Ip, user_tiles, item_groups, tiles_per_group);
-    } else {
-    if (!h->gemm1_zreg_attr_set[ce]) {
-      if (ce) HIPCHK(hipFuncSetAttribute((const void*)gemm1_loss_zreg_kernel<5>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)gemm1_zreg_lds_bytes()));
-      else HIPCHK(hipFuncSetAttribute((const void*)gemm1_loss_zreg_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)gemm1_zreg_lds_bytes()));
-      h->gemm1_zreg_attr_set[ce] = true;
+    if (!h->gemm1_duo_attr_set[ce]) {
+      if (ce) HIPCHK(hipFuncSetAttribute((const void*)gemm1_loss_duo_kernel<5>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)gemm1_duo_lds_bytes()));
+      else HIPCHK(hipFuncSetAttribute((const void*)gemm1_loss_duo_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)gemm1_duo_lds_bytes()));
+      h->gemm1_duo_attr_set[ce] = true;
     }
     if (ce)
-      hipLaunchKernelGGL(gemm1_loss_zreg_kernel<5>, grid, dim3(512), gemm1_zreg_lds_bytes(), st, (const __bf16*)h->d_Zb, (const __bf16*)h->d_Db,
+      hipLaunchKernelGGL(gemm1_loss_duo_kernel<5>, grid, dim3(512), gemm1_duo_lds_bytes(), st, (const __bf16*)h->d_Zb, (const __bf16*)h->d_Db,
                          (const float*)h->P(CDAE_P_BP), h->d_GTb, Bp, nb, I, Ip, user_tiles, item_groups, tiles_per_group);
     else
-      hipLaunchKernelGGL(gemm1_loss_zreg_kernel<0>, grid, dim3(512), gemm1_zreg_lds_bytes(), st, (const __bf16*)h->d_Zb, (const __bf16*)h->d_Db,
+      hipLaunchKernelGGL(gemm1_loss_duo_kernel<0>, grid, dim3(512), gemm1_duo_lds_bytes(), st, (const __bf16*)h->d_Zb, (const __bf16*)h->d_Db,
                          (const float*)h->P(CDAE_P_BP), h->d_GTb, Bp, nb, I, Ip, user_tiles, item_groups, tiles_per_group);
-    }
   } else
     CHK(launch_gemm_lds<EPI_LOSS>(h, st, h->d_Zb, h->d_Db, Bp, Ip, Kp, Kp, Kp, Kp, ep, 1, 0));
   HIPCHK(hipStreamWaitEvent(st, x.ready, 0));
@@ -988,33 +929,16 @@ int full_products_k512(cdae_hip* h, hipStream_t st, cdae_hip::ExBuf& x, const Ba
   // HG, whose order — and therefore rounding — changed from run to run)
   const uint32_t kps = gemm2_k_per_split(h);
   GemmEpilogue e2{};
-  if (h->gemm_direct) {
-    e2.Cout = h->d_HG; e2.ldc = Kp; e2.rows_live = nb;
-    hipLaunchKernelGGL((gemm_nt_bf16_kernel<EPI_ATOMIC>), dim3((Kp + 127) / 128, Bp / 128, (Ip + 2047) / 2048), blk, 0, st, h->d_Gb,
-                       h->d_DTb, Bp, Kp, Ip, Ip, Ip, 2048u, e2);
-    *parts = 0; *rows = nb;
-    return 0;
-  }
   const uint32_t splits = (Ip + kps - 1) / kps;
-  e2.Cout = h->d_HGpart; e2.ldc = Kp; e2.rows_live = nb; e2.split_stride = (size_t)Bp * Kp;
+  e2.Cout = h->d_HGpart; e2.ldc = Kp; e2.split_stride = (size_t)Bp * Kp;
   if (tn2) {                                                     // sum over items of G^T[item][user] D[item][k]: both images as they are
     const GemmGrid gg{Bp / 256, Kp / 256, splits, 2};
-#define GEMM_TN(ROWS_, NST_)                                                                                                              \
-  do {                                                                                                                                    \
-    constexpr size_t lds_ = gemm_tn_lds_bytes<ROWS_, NST_>();                                                                             \
-    if (!h->gemm_tn_attr_set) {                                                                                                           \
-      HIPCHK(hipFuncSetAttribute((const void*)gemm_tn_bf16_kernel<ROWS_, NST_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_));  \
-      h->gemm_tn_attr_set = true;                                                                                                         \
-    }                                                                                                                                     \
-    hipLaunchKernelGGL((gemm_tn_bf16_kernel<ROWS_, NST_>), dim3(gg.workgroups()), dim3(512), lds_, st,                                    \
-                       (const __bf16*)h->d_GTb, (const __bf16*)h->d_Db, Bp, Kp, Ip, Bp, Kp, kps, e2, gg);                                 \
-  } while (0)
-    // two 64-row stages; CDAE_GEMM2_STAGES=3 / 4: the same 136 KiB as 32-row stages with two / three of them in flight behind the one
-    // being contracted — bit-identical, 0.97 against 0.94 ms at 1 M items (A/B switch; cdae_full_kernels.hpp has the table)
-    if (h->gemm2_stages == 3) GEMM_TN(32, 3);
-    else if (h->gemm2_stages == 4) GEMM_TN(32, 4);
-    else GEMM_TN(64, 2);
-#undef GEMM_TN
+    if (!h->gemm_tn_attr_set) {
+      HIPCHK(hipFuncSetAttribute((const void*)gemm_tn_bf16_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)gemm_tn_lds_bytes()));
+      h->gemm_tn_attr_set = true;
+    }
+    hipLaunchKernelGGL(gemm_tn_bf16_kernel, dim3(gg.workgroups()), dim3(512), gemm_tn_lds_bytes(), st,
+                       (const __bf16*)h->d_GTb, (const __bf16*)h->d_Db, Bp, Kp, Ip, Bp, Kp, kps, e2, gg);
   } else {
     CHK(launch_gemm_lds<EPI_STORE>(h, st, h->d_Gb, h->d_DTb, Bp, Kp, Ip, Ip, Ip, kps, e2, splits, 2));
   }
@@ -1036,7 +960,7 @@ int compute_batch_full(cdae_hip* h, int b, const Batch& bt, uint64_t seed, uint3
   Prof pr;
 
   CHK(pr.begin(h, F_ENCODE, st));
-  const bool two_launches = h->encode_two_launches || nb > h->encode_users_max;
+  const bool two_launches = h->encode_two_launches || nb > ENCODE_USERS_MAX;
   if (two_launches) {
     DISPATCH_NI(h->NI, encode_partial_kernel, dim3((n_units + 3) / 4), blk, 0, st, h->hp, h->d_row_ptr, h->d_col, h->P(CDAE_P_W), uptr,
                 n_units, (const uint32_t*)nullptr, s0, nb, 1, CDAE_STREAM_CORRUPT, bt.cidx, seed, epoch, h->d_Hpart,
@@ -1049,14 +973,14 @@ int compute_batch_full(cdae_hip* h, int b, const Batch& bt, uint64_t seed, uint3
   // encode writes those of z: no conversion launch in the steady state.  D is converted here only when something else wrote the
   // parameters (init, set_param, an exchange), Z only when the batch is shorter than the rows the images may hold.
   const bool rows_fused = rows_fused_path(h);                             // GEMM 3 + row step in one launch (Kp = 512, >= 32768 items)
-  const bool rows_write_images = h->fused_images && I < 32768u;
-  const bool rows_write_db = h->fused_images && I >= 32768u && !rows_write_images;   // full_rows_wave_kernel: the row-major image only
+  const bool rows_write_images = I < 32768u;
+  const bool rows_write_db = !rows_write_images;                          // full_rows_wave_kernel: the row-major image only
   const bool need_d = !(rows_write_images && h->db_valid) && !(rows_write_db && h->db_rows_valid);
   const bool tn2 = gemm2_tn_path(h);                                      // GEMM 2 reads G^T and D: no G, no D^T
   if (rows_write_db && h->db_rows_valid && !tn2)                          // D^T from the bf16 rows the row step left (2 GB instead of 4 at 1 M x 512)
     hipLaunchKernelGGL(bf16_transpose_kernel, dim3(Kp / 64, Ip / 64), blk, 0, st, (const __bf16*)h->d_Db, I, Kp, Ip, h->d_DTb);
-  const bool z_in_encode = h->fused_images && h->zb_rows == nb;
-  const bool pair_copy = Ip <= 65536 && !h->full_separate_copies && need_d && !z_in_encode;
+  const bool z_in_encode = h->zb_rows == nb;
+  const bool pair_copy = Ip <= 65536 && need_d && !z_in_encode;
   if (need_d && !pair_copy) hipLaunchKernelGGL(to_bf16_transpose_kernel, dim3(Kp / 64, Ip / 64), blk, 0, st, h->dec(), I, Kp, Kp, Ip, h->d_Db, h->d_DTb);
   CHK(join_aux(h));
   __bf16* zb = z_in_encode ? h->d_Zb : nullptr;
@@ -1079,7 +1003,7 @@ int compute_batch_full(cdae_hip* h, int b, const Batch& bt, uint64_t seed, uint3
     hipLaunchKernelGGL(to_bf16_transpose_kernel, dim3(Kp / 64, Bp / 64), blk, 0, st, h->d_Z, nb, Kp, Kp, Bp, h->d_Zb, h->d_ZTb);
   h->zb_rows = nb;
   const bool fused = Kp <= 256 && !h->full_unfused;
-  uint32_t hg_parts = 0, hg_rows = nb;           // slabs of HGpart holding hg and their row count (0: accumulated into HG by atomics)
+  uint32_t hg_parts = 0, hg_rows = nb;           // slabs of HGpart holding hg and their row count
   if (fused) {
     // targets: one bit per (batch user, item); then forward + loss' + hidden gradient in one launch (cdae_full_kernels.hpp)
     const uint32_t words = (I + 31) / 32, slices = h->full_slices, tiles = Ip / (32 * FUSED_SUB);   // staged steps of 64 items
@@ -1107,13 +1031,13 @@ int compute_batch_full(cdae_hip* h, int b, const Batch& bt, uint64_t seed, uint3
 #undef FUSED_LAUNCH
     hg_parts = slices;
   } else {
-  CHK(full_products_k512(h, st, x, bt, nb, &hg_parts, &hg_rows));
+    CHK(full_products_k512(h, st, x, bt, nb, &hg_parts, &hg_rows));
   }
   // Small item spaces, short blocks (round 4): everything on ONE stream, the b recurrence as the leading workgroups of the row launch
   // (full_rows_kernel's bias role).  A hand-off between two streams through an event costs ~15 us on this part against 2.7 us for
   // a launch boundary (tools/grid_barrier_cost.hip), and at <= one_stream_max users per block the recurrence (41 ns per user) is
   // shorter than the two hand-offs that would put it beside the row step.
-  const bool one_stream = !rows_fused && I < 32768u && nb <= h->full_one_stream_max && hg_parts != 0 && !h->cfg.linear_function;   // (the gate's rows receive Uu (.) delta, b the plain delta)
+  const bool one_stream = !rows_fused && I < 32768u && nb <= h->full_one_stream_max && !h->cfg.linear_function;   // (the gate's rows receive Uu (.) delta, b the plain delta)
   if (one_stream) {
     Prof pa;
     CHK(pa.begin(h, F_HIDDEN, st));
@@ -1125,16 +1049,12 @@ int compute_batch_full(cdae_hip* h, int b, const Batch& bt, uint64_t seed, uint3
     // the b recurrence (41 ns per user, strictly in user order) in two parts: the first half of the block's users as leading workgroups
     // of the GEMM 3 launch, the rest as leading workgroups of the row launch — each launch then lasts about as long as its own work
     uint32_t bias_u0 = 0;
-    if (!h->gemm_direct && gemm_lds_is_128(h, Ip, Kp) && nb >= 64 && !h->full_bias_unsplit) {
+    if (Ip % 256 != 0 && nb >= 64) {     // (launch_gemm_lds then takes the 128 x 128 kernel, the one that can host a bias role)
       bias_u0 = nb / 2;
       e3.bias_blocks = (Kp + 255u) / 256u; e3.bias_nb = bias_u0; e3.bias_delta = h->d_HG; e3.bias_b = h->P(CDAE_P_B); e3.bias_b_ag = h->P(CDAE_P_B_AG);
       e3.bias_hp = h->hp;
     }
-    if (h->gemm_direct)
-      hipLaunchKernelGGL((gemm_nt_bf16_kernel<EPI_STORE>), dim3((Kp + 127) / 128, Ip / 64, 1), dim3(128), 0, st, h->d_GTb, h->d_ZTb, Ip, Kp,
-                         Bp, Bp, Bp, Bp, e3);
-    else
-      CHK(launch_gemm_lds<EPI_STORE>(h, st, h->d_GTb, h->d_ZTb, Ip, Kp, Bp, Bp, Bp, Bp, e3, 1, 1));
+    CHK(launch_gemm_lds<EPI_STORE>(h, st, h->d_GTb, h->d_ZTb, Ip, Kp, Bp, Bp, Bp, Bp, e3, 1, 1));
     CHK(pr.end());
     CHK(pr.begin(h, F_INPUT, st));
     const uint32_t bias_blocks = (Kp + 255u) / 256u;
@@ -1160,9 +1080,8 @@ int compute_batch_full(cdae_hip* h, int b, const Batch& bt, uint64_t seed, uint3
   {
     Prof pa;
     CHK(pa.begin(h, F_HIDDEN, h->aux));
-    DISPATCH_NI(h->NI, hidden_finish_kernel, dim3(nb), blk, 0, h->aux, h->hp, hg_parts ? (const uint32_t*)h->d_iota : uptr,
-                hg_parts ? hg_rows : n_units, s0, nb, h->d_HGpart, h->d_Dz, h->d_HG, h->d_Wu, h->d_Wu_ag, hg_parts,
-                h->d_Uu, h->d_Uu_ag, h->d_Ssum, h->d_delta_rows);
+    DISPATCH_NI(h->NI, hidden_finish_kernel, dim3(nb), blk, 0, h->aux, h->hp, (const uint32_t*)h->d_iota, hg_rows, s0, nb, h->d_HGpart,
+                h->d_Dz, h->d_HG, h->d_Wu, h->d_Wu_ag, hg_parts, h->d_Uu, h->d_Uu_ag, h->d_Ssum, h->d_delta_rows);
     CHK(pa.end());
   }
   HIPCHK(hipEventRecord(h->ev_delta, h->aux));
@@ -1172,14 +1091,7 @@ int compute_batch_full(cdae_hip* h, int b, const Batch& bt, uint64_t seed, uint3
   {
     GemmEpilogue e3{};
     e3.Cout = h->d_dD; e3.ldc = Kp;
-    // 64-row workgroups (two wavefronts): 2 x Ip/64 of them spread over all CUs, 128-row ones would occupy only 166 at ML-10M shape
-    // (developer switch CDAE_GEMM_DIRECT; the default is the LDS-staged kernel: 73 -> 31 us at ML-10M shape, 2048 users)
-    if (rows_fused)
-      ;                                                          // (the product stays in the accumulators of the row-step launch below)
-    else if (h->gemm_direct)
-      hipLaunchKernelGGL((gemm_nt_bf16_kernel<EPI_STORE>), dim3((Kp + 127) / 128, Ip / 64, 1), dim3(128), 0, st, h->d_GTb, h->d_ZTb, Ip, Kp,
-                         Bp, Bp, Bp, Bp, e3);
-    else
+    if (!rows_fused)                                             // (rows_fused: the product stays in the accumulators of the row-step launch below)
       CHK(launch_gemm_lds<EPI_STORE>(h, st, h->d_GTb, h->d_ZTb, Ip, Kp, Bp, Bp, Bp, Bp, e3, 1, 1));
   }
   CHK(pr.end());
@@ -1334,47 +1246,19 @@ int cdae_hip_create(const cdae_hip_config* cfg, int device_id, cdae_hip_t** out)
   h->NI = cfg->num_dim <= 64 ? 1 : (cfg->num_dim <= 128 ? 2 : (cfg->num_dim <= 256 ? 4 : 8));
   h->Kp = 64u * h->NI;
   h->B = cfg->batch_users ? cfg->batch_users : 1024u;
-  h->one_row_per_wave = DEV_ENV("CDAE_DECODE_ONE_ROW_PER_WAVE") != nullptr;
   h->full_unfused = DEV_ENV("CDAE_FULL_UNFUSED") != nullptr;
-  h->gemm_direct = DEV_ENV("CDAE_GEMM_DIRECT") != nullptr;
-  h->gemm_two_stage = DEV_ENV("CDAE_GEMM_TWO_STAGE") != nullptr;
   h->gemm_narrow = DEV_ENV("CDAE_GEMM_NARROW") != nullptr;
   h->rows_separate = DEV_ENV("CDAE_FULL_ROWS_SEPARATE") != nullptr;
   h->gemm2_nt = DEV_ENV("CDAE_GEMM2_NT") != nullptr;
-  if (const char* ev = DEV_ENV("CDAE_GEMM2_STAGES")) h->gemm2_stages = std::max(2, std::min(4, std::atoi(ev)));
   h->gemm1_tiled = DEV_ENV("CDAE_GEMM1_TILED") != nullptr;
   if (const char* e = DEV_ENV("CDAE_FULL_ROWS_KH")) h->rows_fused_kh = std::atoi(e) == 1 ? 1 : 2;
-  h->recommend_per_user = DEV_ENV("CDAE_RECOMMEND_PER_USER") != nullptr;
-  h->full_bias_unsplit = DEV_ENV("CDAE_FULL_BIAS_UNSPLIT") != nullptr;
   if (const char* v = DEV_ENV("CDAE_FULL_ONE_STREAM_MAX")) h->full_one_stream_max = (uint32_t)std::strtoul(v, nullptr, 10);
-  h->gemm1_zreg = DEV_ENV("CDAE_GEMM1_ZREG") != nullptr;
   h->debug_skip_prep = DEV_ENV("CDAE_DEBUG_SKIP_PREP") != nullptr;
   h->encode_two_launches = DEV_ENV("CDAE_ENCODE_TWO_LAUNCHES") != nullptr;
-  h->full_separate_copies = DEV_ENV("CDAE_FULL_SEPARATE_COPIES") != nullptr;
-  h->fused_images = !h->full_separate_copies;
-  if (const char* ev = DEV_ENV("CDAE_ENCODE_USERS_MAX")) h->encode_users_max = (uint32_t)std::atoi(ev);
-  if (const char* ev = DEV_ENV("CDAE_GATHER_HALVES")) h->gather_halves = std::atoi(ev) == 2 ? 2u : 1u;
   if (const char* ev = DEV_ENV("CDAE_PREP_THREAD")) h->prep_threaded = std::atoi(ev) != 0;
   hipError_t e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
   if (e != hipSuccess) { delete h; return fail("hipStreamCreate failed: %s", hipGetErrorString(e)); }
-  if (const char* ev = DEV_ENV("CDAE_STREAM_PAD")) {     // developer experiment: shift which hardware queues the library's other streams get
-    static std::vector<hipStream_t> pads;                 // (kept for the life of the process)
-    static void* padbuf = nullptr;
-    if (!padbuf) (void)hipMalloc(&padbuf, 256);
-    for (int i = 0, n = std::atoi(ev); i < n && padbuf; ++i) {
-      hipStream_t s;
-      if (hipStreamCreateWithFlags(&s, hipStreamNonBlocking) != hipSuccess) break;
-      (void)hipMemsetAsync(padbuf, 0, 256, s);            // (a stream gets its hardware queue when it is first used)
-      (void)hipStreamSynchronize(s);
-      pads.push_back(s);
-    }
-  }
-  {
-    // the prep stream's queue priority (CDAE_PREP_PRIORITY = 1: the device's highest; developer switch)
-    int prio_lo = 0, prio_hi = 0;
-    const bool high = DEV_ENV("CDAE_PREP_PRIORITY") != nullptr && hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi) == hipSuccess;
-    if (e == hipSuccess) e = high ? hipStreamCreateWithPriority(&h->prep, hipStreamNonBlocking, prio_hi) : hipStreamCreateWithFlags(&h->prep, hipStreamNonBlocking);
-  }
+  if (e == hipSuccess) e = hipStreamCreateWithFlags(&h->prep, hipStreamNonBlocking);
   if (e == hipSuccess) e = hipStreamCreateWithFlags(&h->aux, hipStreamNonBlocking);
   {
     // Second prep lane.  Sampling + sorting a batch is a chain of ~12 small launches, ~95 us on the prep stream whatever the
@@ -1456,7 +1340,7 @@ int cdae_hip_create_mf(const cdae_mf_config* mc, int device_id, cdae_hip_t** out
   h->mf = mc->pairwise ? 2u : 1u;
   h->mf_bias = mc->using_bias_term ? 1u : 0u;
   h->mf_auto = mc->batch_users == 0u;
-  if (c.batch_users == 1u && DEV_ENV("CDAE_MF_ONE_LAUNCH_PER_USER") == nullptr) { h->mf_seq = true; h->B = MF_SEQ_USERS; }   // (the switch: round 3's launches, A/B)
+  if (c.batch_users == 1u) { h->mf_seq = true; h->B = MF_SEQ_USERS; }
   h->hp.loss_type = mc->loss_type;
   h->hp.lambda = (float)(2.0 * mc->lambda);                // imf.hpp:92-95, bpr.hpp:78-82: the gradients regularise with 2 * lambda
   return 0;
@@ -1486,7 +1370,7 @@ int cdae_hip_set_decode_fused(cdae_hip_t* h, int allow) {
 int cdae_hip_decode_plan(const cdae_hip_t* h, uint32_t* hot_rows, uint32_t* late_rows, uint32_t* fused) {
   if (!h) return fail("null handle");
   const bool set = h->d_shared != nullptr;
-  if (hot_rows) *hot_rows = set && h->K <= 256 && !h->one_row_per_wave && !h->mf && !h->cfg.full_output ? h->hot_rows : 0u;
+  if (hot_rows) *hot_rows = set && h->K <= 256 && !h->mf && !h->cfg.full_output ? h->hot_rows : 0u;
   if (late_rows) *late_rows = set ? h->late_rows : 0u;
   if (fused) *fused = set && h->fused_decode ? 1u : 0u;
   return 0;
@@ -1520,7 +1404,7 @@ int cdae_hip_set_interactions(cdae_hip_t* h, uint64_t U, uint64_t I, const int64
   if (h->mf && h->mf_auto) {
     const uint32_t b = cdae_hip_mf_default_batch_users(U, h->mf == 2u ? 1u : 0u);
     h->cfg.batch_users = b;
-    h->mf_seq = b == 1u && DEV_ENV("CDAE_MF_ONE_LAUNCH_PER_USER") == nullptr;
+    h->mf_seq = b == 1u;
     h->B = h->mf_seq ? MF_SEQ_USERS : b;
   }
   if (h->mf && !h->mf_seq && h->B > 1 && U > h->B) {
@@ -1585,9 +1469,7 @@ int cdae_hip_set_interactions(cdae_hip_t* h, uint64_t U, uint64_t I, const int64
     // launches are latency-bound per wavefront — a unit's rows are gathered a few at a time — so a batch should offer the chip
     // (256 CUs x 4 SIMDs) several thousand wavefronts: small batches take small units.
     const uint64_t Bu = std::min<uint64_t>(h->B, U);
-    uint32_t up = Bu <= 1024 ? 64u : cdae::UNIT_POS_MAX;          // measured at ML-10M shape, batch_users 256 / 512: 64 best (profiles/r02_unit_size.txt)
-    if (const char* ev = DEV_ENV("CDAE_UNIT_POS")) up = (uint32_t)std::atoi(ev);
-    h->hp.unit_pos = std::max<uint32_t>(1u, std::min<uint32_t>(up, cdae::UNIT_POS_MAX));
+    h->hp.unit_pos = Bu <= 1024 ? 64u : cdae::UNIT_POS_MAX;       // measured at ML-10M shape, batch_users 256 / 512: 64 best (profiles/r02_unit_size.txt)
   }
   h->h_row_ptr.assign(row_ptr, row_ptr + U + 1);
   const size_t nnz = (size_t)row_ptr[U];
@@ -1622,7 +1504,7 @@ int cdae_hip_set_interactions(cdae_hip_t* h, uint64_t U, uint64_t I, const int64
     // added by hidden_finish_kernel / hg_raw_kernel from Ghot, not gathered — in EVERY launch order (so that the fused launch, the
     // separate launches and an item shard of one agree bit for bit); the gather tells them by a bitmap it stages in LDS (item spaces up
     // to 65 536).  CDAE_NO_LATE_ROWS: round 5's arithmetic (developer switch).
-    const bool hybrid = h->K <= 256 && !h->one_row_per_wave && !h->mf && !h->cfg.full_output;
+    const bool hybrid = h->K <= 256 && !h->mf && !h->cfg.full_output;
     h->late_rows = 0;
     if (hybrid && I <= 32u * cdae::LATE_BITS_WORDS && !DEV_ENV("CDAE_NO_LATE_ROWS")) {
       // late: at least CDAE_DECODE_LATE_POS (default 48, i.e. the hot rows: measured 16 / 24 / 32 / 48 -> 0.0915 / 0.0918 / 0.0907 / 0.0898 ms per step) expected positives per batch, at most LATE_MAX rows; all of them take a
@@ -1656,9 +1538,7 @@ int cdae_hip_set_interactions(cdae_hip_t* h, uint64_t U, uint64_t I, const int64
     }
     if (!h->h_err) CHK(err_slot_acquire(h->device, &h->h_err, &h->d_fused_err, &h->err_slot));
     *(volatile uint32_t*)h->h_err = 0u;
-    CHK(dev_alloc(&h->d_hot_cnt, (size_t)h->hot_rows / 4 + 1));
-    HIPCHK(hipMemset(h->d_hot_cnt, 0, ((size_t)h->hot_rows / 4 + 1) * sizeof(uint32_t)));
-    h->fused_seq = 0; h->fused_geo_set = false;
+    h->fused_geo_set = false;
     // The fused launch: needs late rows (else the gather would wait for the longest chains); hot rows take a CU per four of them, so
     // at most half the chip's; the row matrices are addressed through 32-bit buffer offsets.
     hipDeviceProp_t prop;
@@ -1894,7 +1774,7 @@ int cdae_hip_set_interactions(cdae_hip_t* h, uint64_t U, uint64_t I, const int64
   if (h->cfg.linear_function) { CHK(dev_alloc(&h->d_Ssum, BK)); CHK(dev_alloc(&h->d_delta_rows, BK)); }
   if (h->cfg.full_output) {
     h->Bp = (B + 127u) & ~127u;
-    // big item spaces and K > 256: 256-row GEMM tiles (the K > 256 launches of round 3 — gemm1_loss_zreg_kernel, gemm_tn_bf16_kernel — want them)
+    // big item spaces and K > 256: 256-row GEMM tiles (the K > 256 launches — gemm1_loss_duo_kernel, gemm_tn_bf16_kernel — want them)
     h->Ip = (I >= 32768 || h->Kp > 256) ? (((uint32_t)I + 255u) & ~255u) : (((uint32_t)I + 127u) & ~127u);
     CHK(dev_alloc(&h->d_Zb, (size_t)h->Bp * h->Kp)); CHK(dev_alloc(&h->d_ZTb, (size_t)h->Kp * h->Bp));
     CHK(dev_alloc(&h->d_Db, (size_t)h->Ip * h->Kp)); CHK(dev_alloc(&h->d_DTb, (size_t)h->Kp * h->Ip));
@@ -1917,7 +1797,6 @@ int cdae_hip_set_interactions(cdae_hip_t* h, uint64_t U, uint64_t I, const int64
       // slice adds a [B x Kp] partial of hg)
       const uint32_t tiles = h->Ip / (32 * cdae::FUSED_SUB), ublocks = h->Bp / 128;
       h->full_slices = std::max<uint32_t>(1, std::min<uint32_t>({32u, tiles, (256u + ublocks - 1) / ublocks}));
-      if (const char* ev = DEV_ENV("CDAE_FULL_SLICES")) h->full_slices = std::max<uint32_t>(1, std::min<uint32_t>(tiles, (uint32_t)std::atoi(ev)));
     }
   }
   if (h->cfg.full_output || h->item_shard) {
@@ -1929,7 +1808,7 @@ int cdae_hip_set_interactions(cdae_hip_t* h, uint64_t U, uint64_t I, const int64
     if (h->item_shard) CHK(dev_alloc(&h->d_Hsum, (size_t)SHARD_BLOCKS * B * h->Kp));
   }
   {
-    size_t rows = 8 * (size_t)h->gather_halves * h->unit_cap;
+    size_t rows = 8 * (size_t)h->unit_cap;
     if (h->cfg.full_output) {
       rows = std::max(rows, (size_t)h->full_slices * B);
       const uint32_t kps = gemm2_k_per_split(h);                                 // unfused path: one [Bp x Kp] slab per contraction split
@@ -2605,7 +2484,7 @@ int cdae_hip_recommend_all(cdae_hip_t* h, uint64_t u_begin, uint64_t u_end, uint
       std::copy(all.begin() + (size_t)h->user_inv[u] * topk, all.begin() + ((size_t)h->user_inv[u] + 1) * topk, out + (u - u_begin) * topk);
     return 0;
   }
-  if (topk <= (uint32_t)cdae::REC_TOPK_MAX && h->K <= 256 && !h->recommend_per_user) {
+  if (topk <= (uint32_t)cdae::REC_TOPK_MAX && h->K <= 256) {
     // matrix-core path: all users of a chunk in one launch (cdae_recommend_kernels.hpp)
     const uint32_t nch = h->K <= 32 ? 4 : (h->K <= 64 ? 8 : (h->K <= 128 ? 16 : (h->K <= 200 ? 25 : 32)));
     const uint32_t words = (uint32_t)((h->I + 31) / 32);
@@ -3068,7 +2947,7 @@ int fs_phase0(cdae_hip_t* h, uint64_t seed, uint32_t epoch, uint64_t s0, uint32_
   CHK(fs_batch(h, s0, nb, cidx, &bt));
   const uint32_t n_units = units_of(h, bt);
   const uint32_t* uptr = h->d_unit_ptr + s0;
-  if (!h->encode_two_launches && nb <= h->encode_users_max) {
+  if (!h->encode_two_launches && nb <= ENCODE_USERS_MAX) {
     // one launch (round 4): the training encode's workgroup-per-user kernel, stopped at the raw input sum of the local rows, with the
     // owner's private rows staged behind it — the same sums in the same order as the single handle's encode for every user
     const float* ta = h->cfg.user_factor ? h->d_Wu : (h->cfg.linear_function ? h->d_Uu : nullptr);
@@ -3113,13 +2992,13 @@ int fs_phase1(cdae_hip_t* h, uint64_t s0, uint32_t nb) {
     CHK(launch_decode(h, x));
     CHK(pr.end());
     // local hidden gradient: the user's examples on THIS shard's rows (the others are VOID), partial rows per unit of the whole rows
-    const uint32_t n_gunits = gunits_of(h, bt), halves = h->gather_halves;
+    const uint32_t n_gunits = gunits_of(h, bt);
     const uint32_t* guptr = h->d_gunit_ptr + s0;
     if (n_gunits)
-      DISPATCH_NI(h->NI, hidden_gather_kernel, dim3(8 * halves * ((n_gunits + 3) / 4)), blk, 0, st, h->hp, h->d_grow_ptr, guptr, n_gunits, s0, nb,
-                  x.item, h->d_G, h->d_D0, h->d_HGpart, 0u, x.dup_of_ex, h->d_dup_corr, (const uint32_t*)h->d_gunit_user, halves,
+      DISPATCH_NI(h->NI, hidden_gather_kernel, dim3(8 * ((n_gunits + 3) / 4)), blk, 0, st, h->hp, h->d_grow_ptr, guptr, n_gunits, s0, nb,
+                  x.item, h->d_G, h->d_D0, h->d_HGpart, 0u, x.dup_of_ex, h->d_dup_corr, (const uint32_t*)h->d_gunit_user,
                   h->late_rows ? (const uint32_t*)h->d_late_bits : (const uint32_t*)nullptr, h->late_words);
-    DISPATCH_NI(h->NI, hg_raw_kernel, dim3(nb), blk, 0, st, h->hp, guptr, n_gunits, nb, h->d_HGpart, 8u * halves, h->d_HG, h->late_finish());
+    DISPATCH_NI(h->NI, hg_raw_kernel, dim3(nb), blk, 0, st, h->hp, guptr, n_gunits, nb, h->d_HGpart, 8u, h->d_HG, h->late_finish());
     HIPCHK(hipGetLastError());
     return 0;
   }

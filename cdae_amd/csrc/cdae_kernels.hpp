@@ -1557,7 +1557,6 @@ struct GatherArgs {
   const uint32_t* ex_item; const float* G; const float* D0; float* HGpart;
   uint32_t explicit_examples;                    // != 0: one user, one unit, that many examples
   const uint32_t* dup_of_ex; const float* dup_corr; const uint32_t* unit_user;
-  uint32_t halves;                               // 1 or 2: wavefronts per (unit, partition), each walking half of the unit's 64-example chunks
   const uint32_t* late_bits; uint32_t late_words;   // bitmap over the items: the late rows (DecodeLate), whose examples are NOT gathered; nullptr: none
   uint32_t* err;                                 // fused launch: raised by a wavefront that gives up waiting for a g
 };
@@ -1573,15 +1572,14 @@ __device__ __forceinline__ void stage_late_bits(uint32_t* lbits, const uint32_t*
   }
 }
 
-// One wavefront: the partial hidden gradient of (unit, item partition `part`[, half]).
+// One wavefront: the partial hidden gradient of (unit, item partition `part`).
 // FUSED (decode_gather_kernel): the decode of the same launch is still writing G — a g that reads G_PENDING is waited for (sc1
 // polls) — and D0 / correction rows are read past the L1 (sc1), since another CU wrote them during this launch.
 template <int NI, bool FUSED>
-__device__ __forceinline__ void hidden_gather_role(const HyperParams& hp, const GatherArgs& ga, const uint32_t part, const uint32_t half,
-                                                   const uint32_t unit, uint32_t* const lrow, float* const lg,
+__device__ __forceinline__ void hidden_gather_role(const HyperParams& hp, const GatherArgs& ga, const uint32_t part, const uint32_t unit,
+                                                   uint32_t* const lrow, float* const lg,
                                                    const uint32_t* const lbits /* LDS late-row bitmap, or nullptr */) {
   const uint32_t lane = threadIdx.x % WAVE;
-  const uint32_t halves = ga.halves;
   const unsigned long long t0 = trace_begin(hp);
   const UnitRef ur = locate_unit(hp.unit_pos, ga.uptr, ga.nb, ga.uptr[0] + unit, ga.unit_user, ga.u0);
   const uint64_t uid = ga.u0 + ur.slot;
@@ -1662,14 +1660,10 @@ __device__ __forceinline__ void hidden_gather_role(const HyperParams& hp, const 
       for (int k = 0; k < NI; ++k) acc[k] = fmaf(gg[t], vv[t][k], acc[k]);          // (a correction row: g = 1, i.e. acc + row exactly)
     head += n_rows;
   };
-  // `halves` = 2: two wavefronts share a (unit, partition), each walking half of its 64-example chunks; measured slower in round 2
-  // (twice the partial sums); default 1.
-  const uint32_t chunks_per = ((n_ex + WAVE - 1) / WAVE + halves - 1) / halves;
-  const uint32_t c_begin = half * chunks_per * WAVE, c_end = min(n_ex, c_begin + chunks_per * WAVE);
   Meta cur, nxt;
-  load_meta(c_begin, c_end, cur);
-  for (uint32_t c0 = c_begin; c0 < c_end; c0 += 2 * WAVE) {
-    load_meta(c0 + 2 * WAVE, c_end, nxt);                        // (past the end: fillers, no loads)
+  load_meta(0u, n_ex, cur);
+  for (uint32_t c0 = 0; c0 < n_ex; c0 += 2 * WAVE) {
+    load_meta(c0 + 2 * WAVE, n_ex, nxt);                        // (past the end: fillers, no loads)
     if constexpr (FUSED) {
       // g of a row the decode has not finished yet: wait for it (bounded), re-reading only the lanes that need it
       for (uint32_t spin = 0;; ++spin) {
@@ -1699,7 +1693,7 @@ __device__ __forceinline__ void hidden_gather_role(const HyperParams& hp, const 
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");       // (the wavefront's own LDS writes, in order)
     __builtin_amdgcn_wave_barrier();
     // full trips go out now — their loads fly while the next pair's (item, g) are still on their way; the remainder waits for more
-    const bool last = c0 + 2 * WAVE >= c_end;
+    const bool last = c0 + 2 * WAVE >= n_ex;
     while (len - head >= (uint32_t)TRIP) trip((uint32_t)TRIP);
     if (last || len + 4u * WAVE > GCAP) {
       if (len > head) trip(len - head);
@@ -1712,8 +1706,8 @@ __device__ __forceinline__ void hidden_gather_role(const HyperParams& hp, const 
 #pragma unroll
     for (int i = 0; i < NI; ++i) acc[i] = 0.f;
   }
-  vstore<NI>(ga.HGpart + ((size_t)(part * halves + half) * ga.n_units + unit) * hp.Kp + lo, acc);
-  trace_end(hp, 5, (unit * 8u + part) * halves + half, t0, n_ex);
+  vstore<NI>(ga.HGpart + ((size_t)part * ga.n_units + unit) * hp.Kp + lo, acc);
+  trace_end(hp, 5, unit * 8u + part, t0, n_ex);
 }
 
 template <int NI>
@@ -1721,11 +1715,10 @@ __global__ void __launch_bounds__(256)
 hidden_gather_kernel(HyperParams hp, const int64_t* __restrict__ row_ptr, const uint32_t* __restrict__ uptr,
                      uint32_t n_units, uint64_t u0, uint32_t nb, const uint32_t* __restrict__ ex_item,
                      const float* __restrict__ G, const float* __restrict__ D0,
-                     float* __restrict__ HGpart /* [8 * halves][n_units][Kp] */,
+                     float* __restrict__ HGpart /* [8][n_units][Kp] */,
                      uint32_t explicit_examples /* != 0: one user, one unit, that many examples */,
                      const uint32_t* __restrict__ dup_of_ex, const float* __restrict__ dup_corr,
                      const uint32_t* __restrict__ unit_user,
-                     uint32_t halves /* 1 or 2: wavefronts per (unit, partition), each walking half of the unit's 64-example chunks */,
                      const uint32_t* __restrict__ late_bits = nullptr /* the late rows (DecodeLate): skipped here, added by hidden_finish_kernel */,
                      uint32_t late_words = 0) {
   __shared__ uint32_t gl_row[4][GATHER_CAP];
@@ -1733,13 +1726,11 @@ hidden_gather_kernel(HyperParams hp, const int64_t* __restrict__ row_ptr, const 
   __shared__ uint32_t lbits[LATE_BITS_WORDS];
   stage_late_bits(lbits, late_bits, late_words);
   const uint32_t part = blockIdx.x & 7u;
-  const uint32_t rest = blockIdx.x >> 3;
-  const uint32_t half = rest % halves;
-  const uint32_t unit = (rest / halves) * (blockDim.x / WAVE) + threadIdx.x / WAVE;
+  const uint32_t unit = (blockIdx.x >> 3) * (blockDim.x / WAVE) + threadIdx.x / WAVE;
   if (unit >= n_units) return;
-  const GatherArgs ga{row_ptr, uptr, n_units, u0, nb, ex_item, G, D0, HGpart, explicit_examples, dup_of_ex, dup_corr, unit_user, halves,
+  const GatherArgs ga{row_ptr, uptr, n_units, u0, nb, ex_item, G, D0, HGpart, explicit_examples, dup_of_ex, dup_corr, unit_user,
                       late_bits, late_words, nullptr};
-  hidden_gather_role<NI, false>(hp, ga, part, half, unit, gl_row[threadIdx.x / WAVE], gl_g[threadIdx.x / WAVE], late_bits ? lbits : nullptr);
+  hidden_gather_role<NI, false>(hp, ga, part, unit, gl_row[threadIdx.x / WAVE], gl_g[threadIdx.x / WAVE], late_bits ? lbits : nullptr);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1749,12 +1740,6 @@ hidden_gather_kernel(HyperParams hp, const int64_t* __restrict__ row_ptr, const 
 // workgroups that are dispatched as the row wavefronts retire and wait, example by example, for the g they need (G_PENDING).
 // Workgroups of four wavefronts, in this order of workgroup index (S = the chip's CU count):
 //   [0, H)                      popular rows (decode_row64), four per workgroup, one per SIMD;
-//   [rS, rS + H), r = 1..rounds BLOCKERS: idle wavefronts that sleep until popular workgroup (index mod S) has finished.  A popular row's
-//                               chain keeps its SIMD's VALU ~80 % busy; through round 5 the four-row wavefronts that shared the SIMD
-//                               lived as long as the launch — harmless then, but here every gather wavefront would end up waiting for
-//                               one of their rows.  Workgroup b runs on the CU that b mod S names while the CUs hold 1 + rounds
-//                               workgroups of this launch each (observed placement, a speed assumption only: wherever a blocker
-//                               lands it just sleeps);
 //   every other index below D   the other rows, four per wavefront (decode_rows16): which group a wavefront takes is the host's table
 //                               (FusedGeom::cold_map: the groups dealt over the SIMDs by expected length, longest first);
 //   [D, ...)                    gather: four (unit, partition) wavefronts each (hidden_gather_role<FUSED>).
@@ -1763,23 +1748,12 @@ hidden_gather_kernel(HyperParams hp, const int64_t* __restrict__ row_ptr, const 
 // agent-scope fence — a walk of the XCD's whole L2 — is needed (MI355X_MICROARCH.md, inter-workgroup visibility).
 struct FusedGeom {
   uint32_t hot_wgs;        // H
-  uint32_t stride;         // S
-  uint32_t blocked;        // popular workgroups [0, blocked) have blockers (at most FUSED_BLOCK_MAX)
-  uint32_t rounds;         // blocker rounds: workgroups of this launch a CU holds, less one
   uint32_t decode_wgs;     // D
-  uint32_t hot_target;     // value every popular workgroup's counter reaches when its four wavefronts of THIS launch are done (wraps)
-  uint32_t* hot_cnt;       // [hot_wgs] wavefronts finished since the handle was created
   const uint32_t* cold_map; // [decode_wgs][4]: the four-row group of every wavefront of a row workgroup, 0xFFFFFFFF = none (balanced by the host)
 };
-constexpr uint32_t FUSED_BLOCK_MAX = 16;         // blockers for the workgroups of the 64 most popular rows
 constexpr uint32_t FUSED_LDS_WORDS = 4u * 2u * GATHER_CAP + LATE_BITS_WORDS;     // gather role: 22 KiB (the row roles need 4 x ROWS16_LDS_WORDS = 20 KiB)
 static_assert(4u * ROWS16_LDS_WORDS <= FUSED_LDS_WORDS, "row roles' LDS");
 static_assert(3u * (FUSED_LDS_WORDS + 8u) * 4u + 90376u <= 160u * 1024u, "three workgroups of this launch + one of bucket_sort_kernel per CU");
-// is workgroup index b a blocker?
-__host__ __device__ inline bool fused_is_blocker(const FusedGeom& g, uint32_t b) {
-  return b >= g.stride && b < (1u + g.rounds) * g.stride && b % g.stride < g.blocked;
-}
-
 #ifndef CDAE_FUSED_WAVES_PER_SIMD
 #define CDAE_FUSED_WAVES_PER_SIMD 3      // (4 = 128 registers: gather wavefronts resident from the start — measured slower, they take issue slots the row roles need)
 #endif
@@ -1802,19 +1776,7 @@ decode_gather_kernel(HyperParams hp, uint32_t hot_rows, FusedGeom geo, DecodeLat
       __builtin_amdgcn_s_setprio(0);
       trace_end(hp, 3, row, t0, hp.trace ? hw_place() : 0u);
     }
-    if (threadIdx.x % WAVE == 0) atomicAdd(geo.hot_cnt + wg, 1u);          // (the blockers of this workgroup)
   } else if (wg < geo.decode_wgs) {
-    if (fused_is_blocker(geo, wg)) {
-      // ---- blocker: hold this CU's slots until the popular workgroup is done ----
-      const uint32_t* cnt = geo.hot_cnt + wg % geo.stride;
-      const unsigned long long t0 = trace_begin(hp);
-      for (uint32_t spin = 0; spin < (1u << 16); ++spin) {
-        if ((int32_t)(__hip_atomic_load(cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) - geo.hot_target) >= 0) break;
-        __builtin_amdgcn_s_sleep(127);
-      }
-      trace_end(hp, 10, wg * 4u + wid, t0, hp.trace ? hw_place() : 0u);
-      return;
-    }
     // ---- all other rows, four per wavefront ----
     if (CDAE_SKIP_ROLE(hp, 8u)) return;
     // the table is by SIMD (the host balanced the SIMDs' loads): a wavefront takes the entry of the SIMD it finds itself on.  The four
@@ -1849,7 +1811,7 @@ decode_gather_kernel(HyperParams hp, uint32_t hot_rows, FusedGeom geo, DecodeLat
     const uint32_t gw = wg - geo.decode_wgs;
     const uint32_t part = gw & 7u, unit = (gw >> 3) * 4u + wid;
     if (unit >= ga.n_units) return;
-    hidden_gather_role<NI, true>(hp, ga, part, 0u, unit, fused_lds + wid * 2u * GATHER_CAP,
+    hidden_gather_role<NI, true>(hp, ga, part, unit, fused_lds + wid * 2u * GATHER_CAP,
                                  reinterpret_cast<float*>(fused_lds + wid * 2u * GATHER_CAP + GATHER_CAP), ga.late_bits ? lbits : nullptr);
   }
 }

@@ -82,6 +82,12 @@ def test_the_shipped_library_names_no_developer_switch(built):
     assert len(names) <= 5, sorted(names)         # (error-message text such as a layout's name; no environment variable)
     dev = open(cdae_amd.DEV_LIB_PATH, "rb").read()
     assert b"CDAE_SORT_TILE" in dev and b"CDAE_GEMM1_TILED" in dev and b"CDAE_DECODE_UNFUSED" in dev and b"CDAE_FULL_B_SUMMED" not in dev
+    # switches retired together with the kernel variants and launch orders they selected: the developer build no longer names them either
+    retired = [b"CDAE_FUSED_BLOCK_ROUNDS", b"CDAE_FUSED_INDEX_ORDER", b"CDAE_GATHER_HALVES", b"CDAE_DECODE_ONE_ROW_PER_WAVE",
+               b"CDAE_ENCODE_USERS_MAX", b"CDAE_UNIT_POS", b"CDAE_STREAM_PAD", b"CDAE_PREP_PRIORITY", b"CDAE_RECOMMEND_PER_USER",
+               b"CDAE_MF_ONE_LAUNCH_PER_USER", b"CDAE_GEMM_DIRECT", b"CDAE_GEMM_TWO_STAGE", b"CDAE_GEMM2_STAGES", b"CDAE_GEMM1_ZREG",
+               b"CDAE_FULL_SLICES", b"CDAE_FULL_SEPARATE_COPIES", b"CDAE_FULL_BIAS_UNSPLIT"]
+    assert not [s for s in retired if s in dev]
 
 
 def test_product_sources_do_not_touch_the_oracle():

@@ -221,7 +221,7 @@ def test_training_is_bit_deterministic_and_handles_reload(tiny, small):
 
 
 @pytest.mark.parametrize("env", [dict(CDAE_PREP_THREAD="0"), dict(CDAE_PREP2="off"), dict(CDAE_PREP2="own"), dict(CDAE_EVENT_SYSTEM_FENCE="1"),
-                                 dict(CDAE_ENCODE_TWO_LAUNCHES="1"), dict(CDAE_SORT_TILE="1"), dict(CDAE_SORT_LIBRARY="1"), dict(CDAE_SORT_SCAN="1"), dict(CDAE_GATHER_HALVES="1", CDAE_PREP2="aux"),
+                                 dict(CDAE_ENCODE_TWO_LAUNCHES="1"), dict(CDAE_SORT_TILE="1"), dict(CDAE_SORT_LIBRARY="1"), dict(CDAE_SORT_SCAN="1"), dict(CDAE_PREP2="aux"),
                                  dict(CDAE_HOST_PACE_US="0"), dict(CDAE_HOST_PACE_US="5")],
                          ids=lambda e: ",".join(f"{k}={v}" for k, v in e.items()))
 def test_scheduling_switches_do_not_change_a_single_bit(small, monkeypatch, devlib, env):
@@ -633,7 +633,7 @@ def test_full_output_three_gemm_path(tiny, small, monkeypatch, devlib, K, B, unf
     tolerance on the parameters is 3e-2 of their range here (measured 2.1e-2 .. 2.5e-2 on b', the smallest-valued
     parameter, at K = 200 .. 512; the fused kernel measures the same at K = 200) against 2e-2 at K = 24.  Since the end of
     round 3 the item count is padded to a multiple of 256 whenever K > 256, so blocks that fill whole 256-user tiles (B = 130 and
-    256 here) take gemm1_loss_zreg_kernel and gemm_tn_bf16_kernel at these small shapes too; B = 48 keeps the tiled kernels."""
+    256 here) take gemm1_loss_duo_kernel and gemm_tn_bf16_kernel at these small shapes too; B = 48 keeps the tiled kernels."""
     if unfused_env:
         monkeypatch.setenv("CDAE_FULL_UNFUSED", "1")
     data = small if B >= 256 else tiny      # (with 256 of tiny's 300 users per block there are two AdaGrad steps per epoch: b' alone is 3.8e-2 off)
@@ -829,11 +829,10 @@ def test_tn_gemm2_changes_no_bit(built, monkeypatch, devlib):
 
 
 @pytest.mark.parametrize("loss", ["ce", "square"])
-def test_gemm1_zreg_changes_no_bit(built, monkeypatch, devlib, loss):
-    """K = 512 full-output path: GEMM 1 with the z rows of 256 users in registers and only D staged through LDS — the round-5 default
+def test_gemm1_duo_changes_no_bit(built, monkeypatch, devlib, loss):
+    """K = 512 full-output path: GEMM 1 with the z rows of 256 users in registers and only D staged through LDS —
     gemm1_loss_duo_kernel (the two wavefronts of a SIMD in opposite phases, whole tiles double-buffered by LDS DMA, 16-byte G^T stores
-    through v_permlane32_swap) and round 3's lockstep gemm1_loss_zreg_kernel (CDAE_GEMM1_ZREG=1) — against the
-    256 x 256-tile kernel (CDAE_GEMM1_TILED=1).  Every G^T element is the same sum over k in the same order and the same loss
+    through v_permlane32_swap) — against the 256 x 256-tile kernel (CDAE_GEMM1_TILED=1).  Every G^T element is the same sum over k in the same order and the same loss
     expression: identical parameters after two epochs, three blocks each (the last one partly filled: users past the block's end and
     items past the last one are zero in G^T)."""
     d = synth.generate(600, 33_000, 36_000, seed=6, min_items=20)
@@ -850,14 +849,10 @@ def test_gemm1_zreg_changes_no_bit(built, monkeypatch, devlib, loss):
         return out
 
     duo = run()                                    # gemm1_loss_duo_kernel
-    monkeypatch.setenv("CDAE_GEMM1_ZREG", "1")
-    zreg = run()                                   # gemm1_loss_zreg_kernel
-    monkeypatch.delenv("CDAE_GEMM1_ZREG")
     monkeypatch.setenv("CDAE_GEMM1_TILED", "1")
     tiled = run()
-    for w in zreg:
+    for w in duo:
         assert np.isfinite(tiled[w]).all()
-        assert np.array_equal(zreg[w], tiled[w]), ("zreg", w)
         assert np.array_equal(duo[w], tiled[w]), ("duo", w, float(np.abs(duo[w] - tiled[w]).max()))
 
 
@@ -899,7 +894,7 @@ def test_k512_path_over_a_large_item_space_matches_oracle(built, variant):
 
 @pytest.mark.parametrize("U,I,B", [(257, 32_768, 256), (700, 40_000, 512), (1030, 65_537, 1024)])
 def test_k512_launches_on_edge_shapes_change_no_bit(built, monkeypatch, devlib, U, I, B):
-    """The three K > 256 launches of round 3 together (gemm1_loss_zreg_kernel, gemm_tn_bf16_kernel, gemm3_rows_fused_kernel +
+    """The three K > 256 launches together (gemm1_loss_duo_kernel, gemm_tn_bf16_kernel, gemm3_rows_fused_kernel +
     full_rows_inputs_kernel) against the launches they replace (CDAE_GEMM1_TILED, CDAE_GEMM2_NT, CDAE_FULL_ROWS_SEPARATE) on edge
     shapes: an item count that is exactly the smallest the fused row step takes / not a multiple of anything / one past 65 536 (32-bit
     sort keys), a last block of ONE user (257 = 256 + 1), of 188 and of 6 users, one / two / four user tiles per block.  Rows and

@@ -23,5 +23,5 @@ for i in range(60):
     for k, v in st.items():
         if k.startswith("ms_"):
             acc[k] = acc.get(k, 0.0) + v
-print(os.path.basename(sys.argv[1]), os.environ.get("CDAE_DECODE_ONE_ROW_PER_WAVE", "-"), os.environ.get("CDAE_DECODE_HOT_POS", "-"),
+print(os.path.basename(sys.argv[1]), os.environ.get("CDAE_DECODE_HOT_POS", "-"),
       {k: round(v / n, 4) for k, v in acc.items()})

@@ -20,7 +20,7 @@ import cdae_amd  # noqa: E402
 from cdae_amd import synth  # noqa: E402
 
 ROLES = {1: "encode_partial", 2: "encode_finish", 3: "decode hot row", 4: "decode 4 rows", 5: "hidden_gather", 6: "hidden_finish",
-         7: "input: bias b", 8: "input: hot row", 9: "input: row", 10: "decode: blocker"}
+         7: "input: bias b", 8: "input: hot row", 9: "input: row"}
 
 
 def main():
