@@ -207,7 +207,12 @@ __device__ __forceinline__ float fast_exp(float x) { return __expf(x); }
 // loss.hpp:53-55 (SQUARE), loss.hpp:141-147 (CROSS_ENTROPY)
 // The reference switches to e^y - t below -18 and to 1 - t above +18 (loss.hpp:142-145).  In fp32 the plain
 // form is already those limits to within 1 ulp (|sigmoid(y) - e^y| <= e^{2y} < 3e-16 for y < -18; 1/(1+e^-y)
-// rounds to 1 for y > 18; e^-y overflowing to +inf gives rcp(inf) = 0), so the hot loop stays branch-free.
+// rounds to 1 for y > 18; e^-y overflowing to +inf gives rcp(inf) = 0), so the hot loop stays branch-free.  Pinned at the switches and
+// the fp32 overflow edges (+-9, +-18, +-44.5, +-88.72, +-1000) by tests/test_gpu_saturation.py: test_loss_gradient_of_the_grid (this
+// function), test_sampled_training_from_saturated_parameters (also the hot rows' copy in decode_row64's fast_group_spec),
+// test_data_loss_of_the_grid (loss_eval), test_hidden_values_of_the_grid and test_training_encode_of_the_grid (activate; the tanh clamp
+// keeps (1 - r) * rcp(1 + r) from inf * 0 below x = -44), and the full-output epilogues' copies by
+// test_full_output_from_saturated_parameters.
 __device__ __forceinline__ float loss_grad(uint32_t loss_type, float pred, float truth) {
   if (loss_type == 0u) return -2.f * (truth - pred);
   return fast_rcp(1.f + fast_exp(-pred)) - truth;

@@ -83,6 +83,38 @@ def test_oracle_reproduces_loss_kat(built):
             np.testing.assert_allclose([o.loss_grad(p, float(t)) for p in g["pred"]], g[f"{name}_grad_t{t}"], rtol=1e-14)
 
 
+def test_oracle_reproduces_saturation_kat(built):
+    """tests/golden/saturation_kat.npz (numpy closed forms of loss.hpp's and cdae.hpp's branches at +-9, +-18, the fp32 overflow
+    edges and HINGE's z = 1): the oracle's CE / SQUARE evaluate and gradient, its IMF / BPR LOG and HINGE gradients, and its
+    sigmoid / tanh / linear hidden layer (encode of a user whose W and Wu are zero and whose b is the grid) reproduce every column.
+    tests/test_gpu_saturation.py holds the device to the same file."""
+    g = G("saturation_kat.npz")
+    grid = g["grid"]
+    assert grid.size >= 50 and grid.min() == -1000 and grid.max() == 1000
+    ptr, col = np.array([0, 2]), np.array([0, 1], dtype=np.uint32)
+    for name, lt in (("sq", ob.LOSS_SQUARE), ("ce", ob.LOSS_CE)):
+        o = orc.Oracle(orc.OracleConfig(loss_type=lt), 1, 2, ptr, col)
+        for t in (0, 1):
+            np.testing.assert_allclose([o.loss_eval(p, float(t)) for p in grid], g[f"{name}_eval_t{t}"], rtol=1e-14, atol=0)
+            np.testing.assert_allclose([o.loss_grad(p, float(t)) for p in grid], g[f"{name}_grad_t{t}"], rtol=1e-14, atol=0)
+    for pairwise in (False, True):
+        mo = orc.MfOracle(orc.MfConfig(loss_type=ob.LOSS_LOG, pairwise=pairwise), 1, 2, ptr, col)
+        for t, key in ((1.0, "log_grad_tp1"), (-1.0, "log_grad_tm1")):
+            np.testing.assert_allclose([mo.loss_grad(p, t) for p in grid], g[key], rtol=1e-14, atol=0)
+        mo = orc.MfOracle(orc.MfConfig(loss_type=ob.LOSS_HINGE, pairwise=pairwise), 1, 2, ptr, col)
+        np.testing.assert_array_equal([mo.loss_grad(p, t) for p, t in zip(g["hinge_pred"], g["hinge_truth"])], g["hinge_grad"])
+    assert list(g["hinge_grad"]) == [-1, -1, 0, 1, 1, 0]           # z = 1 itself takes the gradient; only z > 1 is free
+    K = grid.size
+    for act, kw in (("sigmoid", dict()), ("tanh", dict(tanh=True)), ("linear", dict(linear=True))):
+        o = orc.Oracle(orc.OracleConfig(num_dim=K, loss_type=ob.LOSS_CE, **kw), 1, 2, ptr, col)
+        o.init_params(0)
+        o.set(ob.P_W, np.zeros(2 * K))
+        o.set(ob.P_WU, np.zeros(K))
+        o.set(ob.P_B, grid)
+        z = o.encode(0, 0, 0, [0])[0]
+        np.testing.assert_allclose(z, grid if act == "linear" else g[act], rtol=1e-14, atol=0)
+
+
 # ---------------------------------------------------------------------------------------------------------
 @pytest.mark.gpu
 @pytest.mark.parametrize("name", list(VARIANTS))
