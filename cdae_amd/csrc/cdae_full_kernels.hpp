@@ -1329,20 +1329,38 @@ full_decode_fused_kernel(HyperParams hp, const __bf16* __restrict__ Zb /* [Bp x 
     }
 }
 
-// Targets: GEMM 1 computed every g against target 0.  For a positive, loss'(y, 1) = loss'(y, 0) - c with
-// c = 1 (cross-entropy: sigmoid(y) - t) or 2 (square: -2 (t - y)), so the batch's positives are patched in place.
+// Targets: GEMM 1 computed every g against target 0; the batch's positives are patched in place with g = bf16(loss'(y, 1)), rounded
+// once, y recomputed per positive in fp32 from the fp32 z row and decoder row (y = Z[slot] . D[item] + b'[item]; the padding columns
+// k >= K are zero in both).  Deriving it from the stored bf16(loss'(y, 0)) instead (loss'(y, 1) = loss'(y, 0) - c, c = 1 for CE, 2 for
+// SQUARE) rounded twice, and the subtraction cancels: an absolute error up to 2^-9 (CE) / 2^-8 (SQUARE) on the well-fit positives.
+// The fp32 operands rather than the bf16 images GEMM 1 read: a positive's g is the term that feeds its own row and b' most directly,
+// and from saturated parameters the bf16 operands of y are what dominates b''s error ("Where the decode rounds").
+// Pinned bit for bit against the bf16-faithful oracle (unrounded_positives) by tests/test_gpu_full_exact.py (the unfused, K = 512 and
+// item-rows cases), and against the fp64 oracle by tests/test_gpu_saturation.py::test_full_output_from_saturated_parameters.
+// 16 lanes per positive, each summing Kp / 16 products of float4 fragments, then a butterfly over the 16 lanes.
 __global__ void __launch_bounds__(256)
-full_positive_fixup_kernel(const uint32_t* __restrict__ ex_item, const uint64_t* __restrict__ ex_val, uint32_t n_ex,
-                           float c, __bf16* __restrict__ G, uint32_t ldg, __bf16* __restrict__ GT, uint32_t ldgt,
+full_positive_fixup_kernel(const uint32_t* __restrict__ ex_item, const uint64_t* __restrict__ ex_val, uint32_t n_ex, uint32_t loss_type,
+                           const float* __restrict__ Z, const float* __restrict__ D, uint32_t Kp, const float* __restrict__ bp,
+                           __bf16* __restrict__ G, uint32_t ldg, __bf16* __restrict__ GT, uint32_t ldgt,
                            uint8_t* __restrict__ has_in = nullptr /* [I]: marks the items some user of the block kept as an input (gemm3_rows_fused_kernel) */) {
-  const uint32_t e = blockIdx.x * blockDim.x + threadIdx.x;
-  if (e >= n_ex) return;
+  const uint32_t e = (blockIdx.x * blockDim.x + threadIdx.x) / 16u, l = threadIdx.x % 16u;
+  if (e >= n_ex) return;                                         // (uniform over the 16 lanes of a positive)
   const uint32_t item = ex_item[e];
   const uint32_t slot = (uint32_t)ex_val[e] & SLOT_MASK;
+  const float* zr = Z + (size_t)slot * Kp;
+  const float* dr = D + (size_t)item * Kp;
+  float acc = 0.f;
+  for (uint32_t c = 4u * l; c < Kp; c += 64u) {                  // Kp is a multiple of 64
+    const float4 a = *reinterpret_cast<const float4*>(zr + c), d = *reinterpret_cast<const float4*>(dr + c);
+    acc += a.x * d.x + a.y * d.y + a.z * d.z + a.w * d.w;
+  }
+#pragma unroll
+  for (int m = 8; m >= 1; m >>= 1) acc += __shfl_xor(acc, m, 16);
+  if (l != 0) return;
   if (has_in && ((uint32_t)ex_val[e] & INPUT_BIT)) has_in[item] = 1;
-  const float g = (float)GT[(size_t)item * ldgt + slot] - c;     // (G and G^T hold the same value)
-  if (G) G[(size_t)slot * ldg + item] = (__bf16)g;
-  GT[(size_t)item * ldgt + slot] = (__bf16)g;
+  const __bf16 g = (__bf16)loss_grad(loss_type, acc + bp[item], 1.f);
+  if (G) G[(size_t)slot * ldg + item] = g;
+  GT[(size_t)item * ldgt + slot] = g;
 }
 
 // K4b as a launch of its own: the full-output path runs it on a second stream beside GEMM 3 (2048 users x 58 ns of

@@ -921,9 +921,9 @@ int full_products_k512(cdae_hip* h, hipStream_t st, cdae_hip::ExBuf& x, const Ba
     CHK(launch_gemm_lds<EPI_LOSS>(h, st, h->d_Zb, h->d_Db, Bp, Ip, Kp, Kp, Kp, Kp, ep, 1, 0));
   HIPCHK(hipStreamWaitEvent(st, x.ready, 0));
   if (bt.E)
-    hipLaunchKernelGGL(full_positive_fixup_kernel, dim3((uint32_t)((bt.E + 255) / 256)), blk, 0, st, x.item, x.val, (uint32_t)bt.E,
-                       h->cfg.loss_type == CDAE_LOSS_CROSS_ENTROPY ? 1.f : 2.f, tn2 ? (__bf16*)nullptr : h->d_Gb, Ip, h->d_GTb, Bp,
-                       rows_fused_path(h) ? h->d_has_in : (uint8_t*)nullptr);
+    hipLaunchKernelGGL(full_positive_fixup_kernel, dim3((uint32_t)((bt.E + 15) / 16)), blk, 0, st, x.item, x.val, (uint32_t)bt.E,
+                       (uint32_t)h->cfg.loss_type, (const float*)h->d_Z, (const float*)h->dec(), Kp, (const float*)h->P(CDAE_P_BP),
+                       tn2 ? (__bf16*)nullptr : h->d_Gb, Ip, h->d_GTb, Bp, rows_fused_path(h) ? h->d_has_in : (uint8_t*)nullptr);
   // GEMM 2: hg = G D  (contraction over items, split).  Every split stores its partial [Bp x Kp] product into its own slab of
   // HGpart and the consumer adds the slabs in fixed order: deterministic (the first version accumulated with fp32 atomics into
   // HG, whose order — and therefore rounding — changed from run to run)

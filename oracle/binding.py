@@ -155,6 +155,9 @@ def _load():
     lib.oracle_train_users_literal.argtypes = [vp, u64, u32, u64, u64]
     lib.oracle_train_users_batched.argtypes = [vp, u64, u32, u64, u64, u64]
     lib.oracle_train_users_full.argtypes = [vp, u64, u32, u64, u64, u64]
+    lib.oracle_train_users_full_bf16.argtypes = [vp, u64, u32, u64, u64, u64, u32]
+    lib.oracle_round_bf16.restype = dbl
+    lib.oracle_round_bf16.argtypes = [dbl]
     lib.oracle_step_user.argtypes = [vp, u64, vp, u64, vp, u64, vp, vp, vp, vp]
     lib.oracle_ref_seed.argtypes = [vp, u64, u32]
     lib.oracle_ref_set_insertion_order.argtypes = [vp, vp]
@@ -251,9 +254,17 @@ class Oracle:
     def train_batched(self, seed: int, epoch: int, batch_users: int, u0: int = 0, u1: int | None = None):
         self.lib.oracle_train_users_batched(self.h, seed, epoch, u0, self.U if u1 is None else u1, batch_users)
 
-    def train_full(self, seed: int, epoch: int, batch_users: int, u0: int = 0, u1: int | None = None):
-        """Full-output decode (every unrated item is a negative once), block-summed gradients."""
-        self.lib.oracle_train_users_full(self.h, seed, epoch, u0, self.U if u1 is None else u1, batch_users)
+    def train_full(self, seed: int, epoch: int, batch_users: int, u0: int = 0, u1: int | None = None, bf16: bool = False,
+                   unrounded_positives: bool = False):
+        """Full-output decode (every unrated item is a negative once), block-summed gradients.  bf16=True: the device's rounding
+        (z and D rounded to bf16 in the three products, g = bf16(loss'(y, t)) rounded once; cdae_oracle.cpp train_users_full).
+        unrounded_positives (with bf16): the unfused plans' positive fix-up, a positive's y from the unrounded z and D."""
+        u1 = self.U if u1 is None else u1
+        if bf16:
+            self.lib.oracle_train_users_full_bf16(self.h, seed, epoch, u0, u1, batch_users, int(unrounded_positives))
+        else:
+            assert not unrounded_positives, "unrounded_positives belongs to the bf16-faithful mode"
+            self.lib.oracle_train_users_full(self.h, seed, epoch, u0, u1, batch_users)
 
     # ---- reference-sequenced mode: the reference's own generators in the reference's own order (cdae_oracle.cpp GlibcRand) ----
     def ref_seed(self, mt_seed: int, rand_seed: int = 1):
@@ -337,6 +348,13 @@ class Oracle:
         sc = np.empty((u1 - u0, topk)) if with_scores else None
         self.lib.oracle_recommend(self.h, u0, u1, topk, _p(out), _p(sc) if with_scores else None)
         return (out, sc) if with_scores else out
+
+
+def round_bf16(x):
+    """The oracle's rounding helper, elementwise: fp64 -> fp32 -> bf16, each to nearest even, returned as fp64."""
+    lib = _load()
+    a = np.asarray(x, dtype=np.float64)
+    return np.array([lib.oracle_round_bf16(float(v)) for v in a.ravel()]).reshape(a.shape)
 
 
 def eval_topn(rec: np.ndarray, test_ptr, test_col) -> np.ndarray:

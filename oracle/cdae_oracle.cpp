@@ -45,6 +45,19 @@ namespace {
 
 enum { LOSS_SQUARE = 0, LOSS_CE = 5 };  // loss.hpp:10-18
 
+// x -> fp32 -> bf16, each step to nearest even; the bf16 value returned as a double (the device's (__bf16)(float) conversion,
+// and torch's float32 -> bfloat16 on the CPU).  NaN stays NaN; a finite value past the bf16 range rounds to +-inf like fp32 -> bf16.
+double round_bf16(double x) {
+  const float f = (float)x;
+  uint32_t u;
+  std::memcpy(&u, &f, 4);
+  if ((u & 0x7F800000u) == 0x7F800000u && (u & 0x007FFFFFu)) return x;          // NaN
+  u = (u + 0x7FFFu + ((u >> 16) & 1u)) & 0xFFFF0000u;
+  float r;
+  std::memcpy(&r, &u, 4);
+  return (double)r;
+}
+
 struct Cfg {
   uint32_t num_dim, num_neg, num_corruptions, loss_type;
   uint32_t using_adagrad, asymmetric, user_factor, linear, scaled, tanh_act, linear_function;
@@ -468,7 +481,24 @@ struct Oracle {
   //   b and Wu[u] steps in user order as in the sampled schedule.
   // With B = 1 every row is touched once per user and this IS the reference loop (tests compare it with
   // train_user_literal fed all unrated items as negatives).
-  void train_users_full(uint64_t seed, uint32_t epoch, size_t u0, size_t u1, size_t B) {
+  //
+  // bf16-faithful mode (bf16 = true; oracle_train_users_full_bf16): the same schedule, rounded where the device rounds, each
+  // rounding fp64 -> fp32 -> bf16 to nearest even (round_bf16).  cdae_amd/csrc cites:
+  //   z  : the products read the bf16 image Zb / ZTb (encode_users_kernel / to_bf16_transpose_*_kernel; GEMM 1, the fused kernel's
+  //        zf fragments, GEMM 3 / gemm3_rows_fused_kernel over ZTb); act' and the hidden steps read the fp32 z (d_Z, d_Dz).
+  //   D  : the bf16 images Db / DTb (full_rows_kernel store_row_bf16, full_rows_wave_kernel, to_bf16_transpose_*) in all three
+  //        products: Y = Z D^T, hg = G D (GEMM 2 NT over DTb or TN over Db, the fused kernel's product 2 over its D^T slice).
+  //   y  : fp32 accumulation of the bf16 products plus the fp32 b' (full_decode_fused_kernel c1 + bb, GemmEpilogue EPI_LOSS,
+  //        gemm1_loss_duo_kernel); here the exact sum of the same rounded operands.
+  //   g  : bf16(loss'(y, t)), rounded ONCE (full_decode_fused_kernel's `(__bf16)g`; GemmEpilogue EPI_LOSS / gemm1_loss_duo_kernel
+  //        for the negatives of the unfused plans).
+  //   unrounded_positives (the unfused plans: K > 256, CDAE_FULL_UNFUSED, the item-rows shards): full_positive_fixup_kernel
+  //        recomputes a positive's y from the fp32 z row and decoder row, not their bf16 images, and stores bf16(loss'(y, 1));
+  //        here y = the unrounded z . D + b' for the positives.
+  //   hg, dD, db': fp32 sums of bf16 g times bf16 D / z (GEMM 2, GEMM 3, the row step's column sums of G^T); here exact sums.
+  // Everything after the three products (delta, the steps) is the default mode's fp64 arithmetic.
+  void train_users_full(uint64_t seed, uint32_t epoch, size_t u0, size_t u1, size_t B, bool bf16 = false,
+                        bool unrounded_positives = false) {
     if (B == 0) B = 1;
     const double sc = scale();
     std::vector<double>& D = c.asymmetric ? V : W;
@@ -491,17 +521,30 @@ struct Oracle {
           act_deriv(&Z[s * K], &Dv[s * K]);
           if (c.linear_function) input_sum(in.data(), in.size(), &SSUM[s * K]);
         }
+        // the operands of the three products: the parameters themselves, or (bf16) their rounded images
+        std::vector<double> Zr, Dr;
+        if (bf16) {
+          Zr.resize(nb * K); Dr.resize(I * K);
+          for (size_t i = 0; i < nb * K; ++i) Zr[i] = round_bf16(Z[i]);
+          for (size_t i = 0; i < I * K; ++i) Dr[i] = round_bf16(D[i]);
+        }
+        const double* Zop = bf16 ? Zr.data() : Z.data();
+        const double* Dop = bf16 ? Dr.data() : D.data();
         for (size_t s = 0; s < nb; ++s) {                      // dense decode against the block-start rows
           const size_t uid = s0 + s;
           const uint32_t* pos = &col[row_ptr[uid]];
           const size_t n_pos = row_ptr[uid + 1] - row_ptr[uid];
-          const double* z = &Z[s * K];
+          const double* z = &Zop[s * K];
           size_t t = 0;
           for (size_t j = 0; j < I; ++j) {
             while (t < n_pos && pos[t] < j) ++t;
             const double truth = (t < n_pos && pos[t] == j) ? 1. : 0.;
-            const double g = loss_grad(output(z, j), truth);
-            const double* row = &D[j * K];
+            const double* row = &Dop[j * K];
+            double y = 0;
+            for (size_t k = 0; k < K; ++k) y += row[k] * z[k];
+            const bool unrounded = bf16 && unrounded_positives && truth == 1.;
+            double g = loss_grad(unrounded ? output(&Z[s * K], j) : y + bp[j], truth);
+            if (bf16) g = round_bf16(g);
             for (size_t k = 0; k < K; ++k) { HG[s * K + k] += g * row[k]; dD[j * K + k] += g * z[k]; }
             dbp[j] += g;
           }
@@ -731,6 +774,12 @@ void oracle_train_users_batched(void* h, uint64_t seed, uint32_t epoch, uint64_t
 void oracle_train_users_full(void* h, uint64_t seed, uint32_t epoch, uint64_t u0, uint64_t u1, uint64_t B) {
   ((Oracle*)h)->train_users_full(seed, epoch, u0, u1, B);
 }
+// the bf16-faithful variant (Oracle::train_users_full, bf16 = true)
+void oracle_train_users_full_bf16(void* h, uint64_t seed, uint32_t epoch, uint64_t u0, uint64_t u1, uint64_t B,
+                                  uint32_t unrounded_positives) {
+  ((Oracle*)h)->train_users_full(seed, epoch, u0, u1, B, true, unrounded_positives != 0);
+}
+double oracle_round_bf16(double x) { return round_bf16(x); }
 // explicit-input single step with taps (known-answer fixtures)
 void oracle_step_user(void* h, uint64_t uid, const uint32_t* in, uint64_t n_in, const uint32_t* neg,
                       uint64_t n_neg, double* z, double* y, double* g, double* hg) {
