@@ -2331,7 +2331,8 @@ recommend_kernel(HyperParams hp, const int64_t* __restrict__ row_ptr, const uint
     best = -INFINITY; best_i = 0xFFFFFFFFu;
     for (uint32_t item = threadIdx.x; item < hp.num_items; item += blockDim.x) {
       const float v = score[item];
-      if (v > best || (v == best && item < best_i)) { best = v; best_i = item; }
+      // (a masked or retired score never wins: with fewer than topk candidates the surplus places keep the 0xFFFFFFFF sentinel)
+      if (v > best || (v == best && item < best_i && v > -INFINITY)) { best = v; best_i = item; }
     }
   };
   rescan();

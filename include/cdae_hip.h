@@ -268,6 +268,9 @@ int cdae_hip_penalty_loss(cdae_hip_t* h, double* out);
  * ties -> lower item id first (heap.hpp:44-52 + utils.hpp:16-19 with ascending scan order).  num_dim <= 256 and topk <= 16
  * run on the matrix cores (all users of a chunk per launch); any other combination — and any item count — takes the
  * general one-workgroup-per-user path.
+ * A user with fewer than topk unrated items gets them all, in that order, and 0xFFFFFFFF in every surplus place, on both
+ * paths and through the item-rows merge of cdae_hip_multi_recommend_all (the reference's heap returns a shorter list there,
+ * cdae.hpp:181-188); a rated item is never returned.
  * out is [(u_end-u_begin) x topk] uint32 on the host. */
 int cdae_hip_recommend_all(cdae_hip_t* h, uint64_t u_begin, uint64_t u_end, uint32_t topk,
                            uint32_t* out);

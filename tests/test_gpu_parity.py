@@ -11,7 +11,7 @@ import cdae_amd
 from cdae_amd import synth
 import oracle as orc
 from oracle import binding as ob
-from helpers import make_pair, max_param_err, record_measured
+from helpers import assert_valid_topk, make_pair, max_param_err, record_measured
 
 pytestmark = pytest.mark.gpu
 
@@ -101,6 +101,7 @@ def test_linear_function_gate_matches_oracle(tiny, B, K, variant):
     rec_o, sc_o = o.recommend(10, with_scores=True)
     clear = np.abs(np.diff(sc_o, axis=1)).min(axis=1) > 1e-3
     np.testing.assert_array_equal(rec_g[clear], rec_o[clear])
+    assert_valid_topk(model, tiny, rec_g, 10, K, eps="derived")      # every user, the near-ties included
 
 
 def test_linear_function_full_output(tiny):
@@ -129,6 +130,7 @@ def test_loss_and_recommend_match_oracle(small):
     clear = gap > 1e-4
     assert clear.mean() > 0.9
     np.testing.assert_array_equal(rec_g[clear], rec_o[clear])
+    assert_valid_topk(model, small, rec_g, 10, 50, eps="derived")    # every user, the near-ties included
     m_g = orc.eval_topn(rec_g, small.test_ptr, small.test_col)
     m_o = orc.eval_topn(rec_o, small.test_ptr, small.test_col)
     assert np.abs(m_g - m_o).max() < 2e-3                     # a near-tie may swap one id
@@ -523,26 +525,6 @@ def test_item_rows_with_thousands_of_examples_per_batch(built, K, B):
     assert err < 3e-4, (err, which)          # (thousands of sequential fp32 steps per row and batch)
 
 
-def _assert_valid_topk(model, data, rec, topk, K):
-    """rec[u] must be a correct top-k of the unrated items under fp64 scores z_u . D[j] + b'[j], up to fp32 noise."""
-    uids = np.arange(data.num_users, dtype=np.uint32)
-    Z = model.get_hidden_values(uids, seed=0, epoch=0, mode=0).astype(np.float64)
-    D = model.get(0).astype(np.float64).reshape(data.num_items, -1)[:, :K]
-    bp = model.get(8).astype(np.float64)
-    S = Z[:, :K] @ D.T + bp
-    eps = 2e-5 * (1.0 + np.abs(S).max())
-    for u in range(data.num_users):
-        rated = data.train_col[data.train_ptr[u]:data.train_ptr[u + 1]]
-        ids = rec[u]
-        assert len(set(ids.tolist())) == topk and not np.intersect1d(ids, rated).size
-        sc = S[u, ids]
-        assert np.all(np.diff(sc) <= eps), (u, sc)                       # descending
-        s = S[u].copy()
-        s[rated] = -np.inf
-        kth = np.sort(s)[::-1][topk - 1]
-        assert sc.min() >= kth - eps, (u, sc.min(), kth)                  # nothing better was left out
-
-
 @pytest.mark.parametrize("K,topk", [(8, 1), (40, 10), (100, 16), (200, 10), (256, 5), (64, 20), (300, 10)])
 def test_recommend_matrix_core_path(ragged, K, topk):
     """K7 on MFMA (K <= 256, topk <= 16) and the per-user fallback (topk 20, K 300): ragged user/item counts that are no
@@ -551,7 +533,7 @@ def test_recommend_matrix_core_path(ragged, K, topk):
     model.train_one_iteration(seed=5, epoch=0)
     rec = model.recommend_all(topk)
     assert rec.shape == (ragged.num_users, topk)
-    _assert_valid_topk(model, ragged, rec, topk, K)
+    assert_valid_topk(model, ragged, rec, topk, K)
     part = model.recommend_all(topk, 3, ragged.num_users - 2)            # a sub-range of users
     np.testing.assert_array_equal(part, rec[3:ragged.num_users - 2])
 
@@ -617,6 +599,7 @@ def test_more_than_65536_items(built):
     clear = np.abs(np.diff(sc_o, axis=1)).min(axis=1) > 1e-4
     assert clear.mean() > 0.5
     np.testing.assert_array_equal(rec_g[clear], rec_o[clear])
+    assert_valid_topk(model, data, rec_g, 10, 8, eps="derived")      # every user, the near-ties included
     full, of = make_pair(data, K=8, B=32, full_output=True)
     full.train_one_iteration(seed=3, epoch=0)
     of.train_full(3, 0, 32)
@@ -669,12 +652,14 @@ def test_recommend_general_path_large_item_space_and_k_above_256(built):
         clear = _clear_rows(sc_o)
         assert clear.mean() > 0.8
         np.testing.assert_array_equal(rec_g[clear], rec_o[clear])
+        assert_valid_topk(model, d, rec_g, topk, 300, eps="derived")   # every user, the near-ties included
     # K <= 256 with topk > 16 on the same item space: general path as well
     model2, o2 = make_pair(d, K=40, B=64)
     rec_g = model2.recommend_all(24)
     rec_o, sc_o = o2.recommend(24, with_scores=True)
     clear = _clear_rows(sc_o, 1e-5)
     np.testing.assert_array_equal(rec_g[clear], rec_o[clear])
+    assert_valid_topk(model2, d, rec_g, 24, 40, eps="derived")
 
 
 def test_recommend_with_a_rated_set_that_is_not_the_train_row(small):
@@ -700,6 +685,15 @@ def test_recommend_with_a_rated_set_that_is_not_the_train_row(small):
         assert not np.intersect1d(got, foreign).size
         if _clear_rows(sc)[0]:
             np.testing.assert_array_equal(got, ref[0])
+        # clear or not: a valid top-10 under the z a handle encodes from the foreign set (a twin whose train row of that user it is)
+        twin = cdae_amd.CDAE(model.cfg)
+        twin.set_interactions(small.num_users, small.num_items, ptr2, col2)
+        twin.init_params(0)
+        for which in range(12):
+            if o.get(which).size:
+                twin.set(which, model.get(which))
+        z = twin.get_hidden_values(np.array([uid], dtype=np.uint32), mode=0)
+        assert_valid_topk(model, small, got[None, :], 10, 50, eps="derived", users=[uid], rated=[foreign], Z=z)
         # the train row itself through the explicit path == the table
         np.testing.assert_array_equal(model.recommend_user(uid, row, 10), model.recommend_all(10, uid, uid + 1)[0])
     with pytest.raises(cdae_amd.CDAEError):
