@@ -435,19 +435,32 @@ int collect_profile(cdae_hip* h, cdae_hip_stats* st) {
   return 0;
 }
 
+// Every device allocation of a handle that set_interactions (or a later entry point) makes, visited as void**: f(slot) != 0 stops the
+// visit and is returned.  A new buffer is added HERE only.  (d_scalar is not in the list: cdae_hip_create allocates it and it lives
+// as long as the handle.)
+template <class F, class... P> int visit_slots(F& f, P*&... p) {
+  int rc = 0;
+  ((rc = rc ? rc : f((void**)&p)), ...);
+  return rc;
+}
+template <class F> int visit_device_ptrs(cdae_hip* h, F f) {
+  for (auto& b : h->ex)
+    CHK(visit_slots(f, b.item, b.val, b.sorted_item, b.sorted_val, b.seg, b.dup_of_pos, b.dup_of_ex, b.dup_count, b.key16, b.sorted_key16,
+                    b.item_count, b.prefix, b.rank, b.bucketed, b.tile_hist, b.block_total, b.wg_state, b.cells, b.cell_flag));
+  return visit_slots(f, h->d_row_ptr, h->d_col, h->d_item_order, h->d_shared, h->d_Wu, h->d_Wu_ag, h->d_D0, h->d_HGpart, h->d_sort_tmp,
+                     h->d_unit_ptr, h->d_Hpart, h->d_uptr_tmp, h->d_Zb, h->d_ZTb, h->d_Db, h->d_DTb, h->d_Gb, h->d_GTb, h->d_dD, h->d_has_in,
+                     h->d_Z, h->d_Dz, h->d_HG, h->d_G, h->d_touched, h->d_uids, h->d_rec, h->d_base, h->d_delta, h->d_recv, h->d_snap,
+                     h->d_dup_corr, h->d_unit_user, h->d_zeval, h->d_bits, h->d_hpart_eval, h->d_iota, h->d_bits_train,
+                     h->d_Uu, h->d_Uu_ag, h->d_Ssum, h->d_delta_rows, h->d_score, h->d_Hsum, h->d_hsum_eval, h->d_iota_eval, h->d_rec_score,
+                     h->d_gpos, h->d_ub, h->d_ub_ag, h->d_UVpre, h->d_rank_of, h->d_grow_ptr, h->d_gcol, h->d_gunit_ptr, h->d_gunit_user,
+                     h->d_test_ptr, h->d_test_col, h->d_topn_pu, h->d_topn_out, h->d_bucket_cut, h->d_range_of,
+                     h->d_Ghot, h->d_hotdup, h->d_late_bits, h->d_cold_map);
+}
+
 void free_all(cdae_hip* h) {
-  void* ptrs[] = {h->d_row_ptr, h->d_col, h->d_item_order, h->d_shared, h->d_Wu, h->d_Wu_ag, h->d_D0, h->d_HGpart,
-                  h->d_unit_ptr, h->d_Hpart, h->d_uptr_tmp, h->d_Zb, h->d_ZTb, h->d_Db, h->d_DTb, h->d_Gb, h->d_GTb, h->d_dD, h->d_has_in,
-                  h->d_sort_tmp, h->d_Z, h->d_Dz, h->d_HG, h->d_G, h->d_touched, h->d_scalar, h->d_uids, h->d_rec,
-                  h->d_base, h->d_delta, h->d_recv, h->d_snap, h->d_dup_corr, h->d_unit_user, h->d_zeval, h->d_bits, h->d_hpart_eval, h->d_iota, h->d_bits_train,
-                  h->d_Uu, h->d_Uu_ag, h->d_Ssum, h->d_delta_rows, h->d_score, h->d_Hsum, h->d_hsum_eval, h->d_iota_eval, h->d_rec_score, h->d_gpos, h->d_ub, h->d_ub_ag, h->d_UVpre, h->d_rank_of,
-                  h->d_grow_ptr, h->d_gcol, h->d_gunit_ptr, h->d_gunit_user, h->d_test_ptr, h->d_test_col, h->d_topn_pu, h->d_topn_out, h->d_bucket_cut, h->d_range_of,
-                  h->d_Ghot, h->d_hotdup, h->d_late_bits, h->d_cold_map};
-  for (void* p : ptrs) if (p) (void)hipFree(p);
+  (void)visit_device_ptrs(h, [](void** p) { if (*p) (void)hipFree(*p); *p = nullptr; return 0; });   // (errors ignored: the handle goes away)
+  if (h->d_scalar) (void)hipFree(h->d_scalar);
   for (auto& b : h->ex) {
-    void* q[] = {b.item, b.val, b.sorted_item, b.sorted_val, b.seg, b.dup_of_pos, b.dup_of_ex, b.dup_count, b.key16, b.sorted_key16,
-                 b.item_count, b.prefix, b.rank, b.bucketed, b.tile_hist, b.block_total, b.wg_state, b.cells, b.cell_flag};
-    for (void* p : q) if (p) (void)hipFree(p);
     if (b.ready) (void)hipEventDestroy(b.ready);
     if (b.released) (void)hipEventDestroy(b.released);
   }
@@ -475,25 +488,10 @@ int quiesce(cdae_hip* h) {
 }
 
 int free_interaction_state(cdae_hip* h) {
-  void** ptrs[] = {(void**)&h->d_row_ptr, (void**)&h->d_col, (void**)&h->d_item_order, (void**)&h->d_shared,
-                   (void**)&h->d_Wu, (void**)&h->d_Wu_ag, (void**)&h->d_D0, (void**)&h->d_HGpart, (void**)&h->d_sort_tmp,
-                   (void**)&h->d_unit_ptr, (void**)&h->d_Hpart, (void**)&h->d_uptr_tmp, (void**)&h->d_Zb, (void**)&h->d_ZTb,
-                   (void**)&h->d_Db, (void**)&h->d_DTb, (void**)&h->d_Gb, (void**)&h->d_GTb, (void**)&h->d_dD, (void**)&h->d_has_in,
-                   (void**)&h->d_Z, (void**)&h->d_Dz, (void**)&h->d_HG, (void**)&h->d_G, (void**)&h->d_touched,
-                   (void**)&h->d_uids, (void**)&h->d_rec, (void**)&h->d_base, (void**)&h->d_delta, (void**)&h->d_recv, (void**)&h->d_snap, (void**)&h->d_dup_corr, (void**)&h->d_unit_user, (void**)&h->d_zeval, (void**)&h->d_bits, (void**)&h->d_hpart_eval, (void**)&h->d_iota, (void**)&h->d_bits_train,
-                   (void**)&h->d_Uu, (void**)&h->d_Uu_ag, (void**)&h->d_Ssum, (void**)&h->d_delta_rows, (void**)&h->d_score,
-                   (void**)&h->d_Hsum, (void**)&h->d_hsum_eval, (void**)&h->d_iota_eval, (void**)&h->d_rec_score, (void**)&h->d_gpos, (void**)&h->d_ub, (void**)&h->d_ub_ag, (void**)&h->d_UVpre, (void**)&h->d_rank_of,
-                   (void**)&h->d_grow_ptr, (void**)&h->d_gcol, (void**)&h->d_gunit_ptr, (void**)&h->d_gunit_user,
-                   (void**)&h->d_test_ptr, (void**)&h->d_test_col, (void**)&h->d_topn_pu, (void**)&h->d_topn_out, (void**)&h->d_bucket_cut, (void**)&h->d_range_of,
-                   (void**)&h->d_Ghot, (void**)&h->d_hotdup, (void**)&h->d_late_bits, (void**)&h->d_cold_map};
-  for (auto& b : h->ex) {
-    void** q[] = {(void**)&b.item, (void**)&b.val, (void**)&b.sorted_item, (void**)&b.sorted_val, (void**)&b.seg,
-                  (void**)&b.dup_of_pos, (void**)&b.dup_of_ex, (void**)&b.dup_count, (void**)&b.key16, (void**)&b.sorted_key16,
-                  (void**)&b.item_count, (void**)&b.prefix, (void**)&b.rank, (void**)&b.bucketed, (void**)&b.tile_hist, (void**)&b.block_total,
-                  (void**)&b.wg_state, (void**)&b.cells, (void**)&b.cell_flag};
-    for (void** p : q) if (*p) { HIPCHK(hipFree(*p)); *p = nullptr; }
-  }
-  for (void** p : ptrs) if (*p) { HIPCHK(hipFree(*p)); *p = nullptr; }
+  CHK(visit_device_ptrs(h, [](void** p) {
+    if (*p) { HIPCHK(hipFree(*p)); *p = nullptr; }
+    return 0;
+  }));
   h->rec_cap = 0; h->score_cap = 0; h->rec_score_cap = 0; h->hsum_eval_cap = 0;
   h->db_valid = false; h->db_rows_valid = false; h->zb_rows = 0xFFFFFFFFu;
   h->eval_cap = 0; h->eval_unit_cap = 0; h->bits_cap = 0;
@@ -502,6 +500,15 @@ int free_interaction_state(cdae_hip* h) {
 
 template <class T> int dev_alloc(T** p, size_t n) {
   HIPCHK(hipMalloc((void**)p, std::max<size_t>(n, 1) * sizeof(T)));
+  return 0;
+}
+// grow-only workspace: *p holds at least n units of `per` elements, *cap is the number of units it was allocated for
+template <class T, class S> int ensure_cap(T** p, S* cap, size_t n, size_t per = 1) {
+  if (*cap >= n) return 0;
+  if (*p) HIPCHK(hipFree(*p));
+  *p = nullptr; *cap = 0;
+  CHK(dev_alloc(p, n * per));
+  *cap = (S)n;
   return 0;
 }
 
@@ -741,6 +748,29 @@ int launch_decode(cdae_hip* h, cdae_hip::ExBuf& x, const cdae::GatherArgs* fused
   return 0;
 }
 
+// Tail of the sampled step, shared by the single handle (compute_batch) and the item shard (fs_phase2): delta from hg, the Wu / Uu
+// steps, then the input rows with the strictly sequential hidden-bias recurrence as leading workgroups (both need only delta).
+// hg = HG + `parts` slabs of HGpart over the unit prefix uptr (an item shard: parts 0, d_HG already holds the all-reduced hg);
+// uu_b: the batch's gathered Uu rows (item shard); pr: the caller's open F_HIDDEN span, or nullptr (no profiling of the tail).
+int sampled_tail(cdae_hip* h, cdae_hip::ExBuf& x, uint64_t s0, uint32_t nb, const uint32_t* uptr, uint32_t n_units, uint32_t parts,
+                 const float* uu_b, const cdae::LateFinish& late, Prof* pr) {
+  using namespace cdae;
+  hipStream_t st = h->stream;
+  const uint32_t I = (uint32_t)h->I;
+  const dim3 blk(256);
+  DISPATCH_NI(h->NI, hidden_finish_kernel, dim3(nb), blk, 0, st, h->hp, uptr, n_units, s0, nb, h->d_HGpart, h->d_Dz, h->d_HG,
+              h->d_Wu, h->d_Wu_ag, parts, h->d_Uu, h->d_Uu_ag, h->d_Ssum, h->d_delta_rows, uu_b, late);
+  if (pr) { CHK(pr->end()); CHK(pr->begin(h, F_INPUT, st)); }
+  const uint32_t bias_blocks = (h->Kp + 255u) / 256u;
+  DISPATCH_NI(h->NI, input_rows_kernel, dim3(bias_blocks + (I + 3) / 4), blk, 0, st, h->hp, h->d_item_order, x.seg + 2 * (size_t)I, x.seg + 3 * (size_t)I,
+              x.sorted_val, h->d_Z, h->d_HG, h->d_G, h->P(CDAE_P_W), h->P(CDAE_P_W_AG), CDAE_TOUCHED_ARG, nb, h->P(CDAE_P_B),
+              h->P(CDAE_P_B_AG), h->delta_rows());
+  if (pr) CHK(pr->end());
+  HIPCHK(hipEventRecord(x.released, st));
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
 // K2..K5 on the main stream from example-buffer set `b`.
 // explicit_in != nullptr: single user whose example list (already sorted into set b) and input set come from the caller
 int compute_batch(cdae_hip* h, int b, const Batch& bt, uint64_t seed, uint32_t epoch,
@@ -795,21 +825,7 @@ int compute_batch(cdae_hip* h, int b, const Batch& bt, uint64_t seed, uint32_t e
     DISPATCH_NI(h->NI, hidden_gather_kernel, dim3(8 * ((n_units + 3) / 4)), blk, 0, st, h->hp, ga.row_ptr, uptr, n_units, s0, nb,
                 x.item, h->d_G, h->d_D0, h->d_HGpart, ga.explicit_examples, x.dup_of_ex, h->d_dup_corr, ga.unit_user,
                 ga.late_bits, ga.late_words);
-  DISPATCH_NI(h->NI, hidden_finish_kernel, dim3(nb), blk, 0, st, h->hp, uptr, n_units, s0, nb, h->d_HGpart, h->d_Dz, h->d_HG,
-              h->d_Wu, h->d_Wu_ag, 8u, h->d_Uu, h->d_Uu_ag, h->d_Ssum, h->d_delta_rows, (const float*)nullptr, h->late_finish());
-  CHK(pr.end());
-  // input rows + (leading workgroups) the strictly sequential hidden-bias recurrence: both need only delta
-  CHK(pr.begin(h, F_INPUT, st));
-  {
-    const uint32_t bias_blocks = (h->Kp + 255u) / 256u;
-    DISPATCH_NI(h->NI, input_rows_kernel, dim3(bias_blocks + (I + 3) / 4), blk, 0, st, h->hp, h->d_item_order, x.seg + 2 * (size_t)I, x.seg + 3 * (size_t)I,
-                x.sorted_val, h->d_Z, h->d_HG, h->d_G, h->P(CDAE_P_W), h->P(CDAE_P_W_AG), CDAE_TOUCHED_ARG, nb, h->P(CDAE_P_B),
-                h->P(CDAE_P_B_AG), h->delta_rows());
-  }
-  CHK(pr.end());
-  HIPCHK(hipEventRecord(x.released, st));
-  HIPCHK(hipGetLastError());
-  return 0;
+  return sampled_tail(h, x, s0, nb, uptr, n_units, 8u, nullptr, h->late_finish(), &pr);
 }
 
 // LDS-staged NT GEMM: the 256 x 128 three-stage kernel where the rows allow it (M % 256 == 0), else the 128 x 128 one.
@@ -946,6 +962,99 @@ int full_products_k512(cdae_hip* h, hipStream_t st, cdae_hip::ExBuf& x, const Ba
   return 0;
 }
 
+// The fused full-output decode (K <= 256; cdae_full_kernels.hpp full_decode_fused_kernel): forward product, loss' against the targets of
+// example-buffer set b — one bit per (batch user, item), built by prep_batch — and the hidden gradient in one launch, which leaves hg
+// as h->full_slices slabs of HGpart.  Shared by the single handle and the item shard (its own item rows); the caller has waited for
+// the set's `ready` event.
+int launch_full_fused(cdae_hip* h, hipStream_t st, int b, uint32_t nb) {
+  using namespace cdae;
+  const uint32_t I = (uint32_t)h->I, Kp = h->Kp, Bp = h->Bp, Ip = h->Ip;
+  const uint32_t words = (I + 31) / 32, slices = h->full_slices, tiles = Ip / (32 * FUSED_SUB);   // staged steps of 64 items
+  const uint32_t* bits = h->d_bits_train + (size_t)b * h->bits_stride;
+  const uint32_t tps = (tiles + slices - 1) / slices;
+  const dim3 grid(slices, Bp / 128), blk(256);
+  const size_t lds = full_fused_lds_bytes(Kp);
+  if ((uint64_t)Ip * Bp > 0xFFFFFFFFull) return fail("full-output decode: G^T of %u x %u exceeds 2^32 elements; lower batch_users", Ip, Bp);
+#define FUSED_LAUNCH2(NKS_, L_)                                                                                                         \
+  do {                                                                                                                                  \
+    if (!h->fused_attr_set) {      /* per handle (the attribute belongs to the (function, device) pair): a runtime call per batch otherwise */ \
+      HIPCHK(hipFuncSetAttribute((const void*)full_decode_fused_kernel<NKS_, L_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
+      h->fused_attr_set = true;                                                                                                          \
+    }                                                                                                                                     \
+    hipLaunchKernelGGL((full_decode_fused_kernel<NKS_, L_>), grid, blk, lds, st, h->hp, h->d_Zb, h->d_Db, h->d_DTb, Ip, h->P(CDAE_P_BP), \
+                       bits, words, nb, tps, h->d_GTb, Bp, h->d_HGpart);                                                     \
+  } while (0)
+#define FUSED_LAUNCH(NKS_)                                                                       \
+  do {                                                                                           \
+    if (h->cfg.loss_type == CDAE_LOSS_CROSS_ENTROPY) FUSED_LAUNCH2(NKS_, 5); else FUSED_LAUNCH2(NKS_, 0); \
+  } while (0)
+  switch (Kp) { case 64: FUSED_LAUNCH(4); break; case 128: FUSED_LAUNCH(8); break; default: FUSED_LAUNCH(16); break; }
+#undef FUSED_LAUNCH2
+#undef FUSED_LAUNCH
+  return 0;
+}
+
+// Two-stream tail of the full-output step, shared by the single handle (compute_batch_full) and the item shard (fs_phase2).  The aux
+// stream takes what needs hg only — delta_u, the Wu / Uu steps, then the strictly sequential hidden-bias recurrence (2048 users x
+// 58 ns) — beside GEMM 3 on the main stream; the row steps wait for delta, and the recurrence is joined by its next consumer (join_aux).
+// (Round 4 measured GEMM 2 on the aux stream too, BESIDE the fused row launch of the K = 512 path, which needs G^T and Z^T only — two
+// bf16 images of the decoder, swapped per block: 5.0 ms per 1024-user block against 4.75 in order.  The two launches stretch each
+// other — GEMM 2 + hidden layer 1.2 -> 3.7 ms, row launch 2.3 -> 3.8 — because GEMM 2's LDS fill and the row launch's streams share
+// the L2s and the fabric, and a CU holds one or the other, not both (139 KiB / 2 x 72 KiB of LDS).  Removed.)
+struct FullTail {
+  uint32_t hg_parts, hg_rows;   // hg = HG + hg_parts slabs of HGpart, hg_rows rows each (an item shard: 0 slabs, d_HG holds the all-reduced hg)
+  const float* uu_b;            // item shard: the batch's gathered Uu rows, else nullptr
+  bool write_images;            // full_rows_kernel / full_rows_wave_kernel leave the bf16 images of the rows they step (the fused row step always does)
+  uint64_t prof_q;              // batch sequence number the profiling spans are sampled by
+  Prof* decode_span;            // the caller's open F_DECODE span, ended behind GEMM 3, or nullptr
+};
+int full_tail(cdae_hip* h, cdae_hip::ExBuf& x, uint64_t s0, uint32_t nb, const FullTail& a) {
+  using namespace cdae;
+  hipStream_t st = h->stream;
+  const uint32_t I = (uint32_t)h->I, Kp = h->Kp, Bp = h->Bp, Ip = h->Ip;
+  const dim3 blk(256);
+  const bool rows_fused = rows_fused_path(h);                             // GEMM 3 + row step in one launch (Kp = 512, >= 32768 items)
+  __bf16* const img = a.write_images ? h->d_Db : nullptr;
+  Prof pr;
+  HIPCHK(hipEventRecord(h->ev_fork, st));
+  HIPCHK(hipStreamWaitEvent(h->aux, h->ev_fork, 0));
+  CHK(pr.begin(h, F_HIDDEN, h->aux, a.prof_q));
+  DISPATCH_NI(h->NI, hidden_finish_kernel, dim3(nb), blk, 0, h->aux, h->hp, (const uint32_t*)h->d_iota, a.hg_rows, s0, nb, h->d_HGpart,
+              h->d_Dz, h->d_HG, h->d_Wu, h->d_Wu_ag, a.hg_parts, h->d_Uu, h->d_Uu_ag, h->d_Ssum, h->d_delta_rows, a.uu_b);
+  CHK(pr.end());
+  HIPCHK(hipEventRecord(h->ev_delta, h->aux));
+  hipLaunchKernelGGL(hidden_bias_kernel, dim3((Kp + 255u) / 256u), blk, 0, h->aux, h->hp, nb, h->d_HG, h->P(CDAE_P_B), h->P(CDAE_P_B_AG));
+  HIPCHK(hipEventRecord(h->ev_join, h->aux));
+  if (!rows_fused) {      // GEMM 3: dD = G^T Z, contraction over the batch's users (rows_fused: the product stays in the accumulators of the row-step launch)
+    GemmEpilogue e3{};
+    e3.Cout = h->d_dD; e3.ldc = Kp;
+    CHK(launch_gemm_lds<EPI_STORE>(h, st, h->d_GTb, h->d_ZTb, Ip, Kp, Bp, Bp, Bp, Bp, e3, 1, 1));
+  }
+  if (a.decode_span) CHK(a.decode_span->end());
+
+  HIPCHK(hipStreamWaitEvent(st, h->ev_delta, 0));
+  CHK(pr.begin(h, F_INPUT, st, a.prof_q));
+  if (rows_fused)      // dD = G^T Z and the row steps from its accumulators, the row-major bf16 image left current
+    CHK(launch_rows_fused(h, st, x, nb, h->d_Db));
+  else if (I >= 32768u)     // rows are plentiful and mostly without kept inputs: one wavefront per row (the row-major image only)
+    DISPATCH_NI(h->NI, full_rows_wave_kernel, dim3((I + 3) / 4), blk, 0, st, h->hp, x.seg, x.seg + I, x.sorted_val, h->delta_rows(),
+                h->d_dD, h->d_GTb, Bp, nb, h->P(CDAE_P_W), h->P(CDAE_P_W_AG), h->P(CDAE_P_V), h->P(CDAE_P_V_AG), h->P(CDAE_P_BP),
+                h->P(CDAE_P_BP_AG), h->d_touched, img);
+  else
+    DISPATCH_NI(h->NI, full_rows_kernel, dim3(I), blk, 0, st, h->hp, x.seg, x.seg + I, x.sorted_val, h->delta_rows(),
+                h->d_dD, h->d_GTb, Bp, nb, h->P(CDAE_P_W), h->P(CDAE_P_W_AG), h->P(CDAE_P_V), h->P(CDAE_P_V_AG), h->P(CDAE_P_BP),
+                h->P(CDAE_P_BP_AG), (float*)nullptr, (float*)nullptr, h->d_touched,
+                img, a.write_images ? h->d_DTb : (__bf16*)nullptr, a.write_images ? Ip : 0u);
+  CHK(pr.end());
+  // which bf16 images of the decoder the row step left current: both (full_rows_kernel), or the row-major one
+  h->db_valid = a.write_images && I < 32768u;
+  h->db_rows_valid = rows_fused || (a.write_images && I >= 32768u);
+  h->join_pending = true;                                      // the aux stream (b recurrence) is joined by its next consumer: join_aux
+  HIPCHK(hipEventRecord(x.released, st));
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
 // Full-output decode of one batch (MFMA path, cdae_full_kernels.hpp).  The example list holds the positives only.
 int compute_batch_full(cdae_hip* h, int b, const Batch& bt, uint64_t seed, uint32_t epoch) {
   using namespace cdae;
@@ -1005,31 +1114,9 @@ int compute_batch_full(cdae_hip* h, int b, const Batch& bt, uint64_t seed, uint3
   const bool fused = Kp <= 256 && !h->full_unfused;
   uint32_t hg_parts = 0, hg_rows = nb;           // slabs of HGpart holding hg and their row count
   if (fused) {
-    // targets: one bit per (batch user, item); then forward + loss' + hidden gradient in one launch (cdae_full_kernels.hpp)
-    const uint32_t words = (I + 31) / 32, slices = h->full_slices, tiles = Ip / (32 * FUSED_SUB);   // staged steps of 64 items
-    const uint32_t* bits = h->d_bits_train + (size_t)b * h->bits_stride;      // built by prep_batch on the prep stream
     HIPCHK(hipStreamWaitEvent(st, x.ready, 0));
-    const uint32_t tps = (tiles + slices - 1) / slices;
-    const dim3 grid(slices, Bp / 128);
-    const size_t lds = full_fused_lds_bytes(Kp);
-#define FUSED_LAUNCH2(NKS_, L_)                                                                                                         \
-  do {                                                                                                                                  \
-    if (!h->fused_attr_set) {      /* per handle (the attribute belongs to the (function, device) pair): a runtime call per batch otherwise */ \
-      HIPCHK(hipFuncSetAttribute((const void*)full_decode_fused_kernel<NKS_, L_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-      h->fused_attr_set = true;                                                                                                          \
-    }                                                                                                                                     \
-    hipLaunchKernelGGL((full_decode_fused_kernel<NKS_, L_>), grid, blk, lds, st, h->hp, h->d_Zb, h->d_Db, h->d_DTb, Ip, h->P(CDAE_P_BP), \
-                       bits, words, nb, tps, h->d_GTb, Bp, h->d_HGpart);                                                     \
-  } while (0)
-#define FUSED_LAUNCH(NKS_)                                                                       \
-  do {                                                                                           \
-    if (h->cfg.loss_type == CDAE_LOSS_CROSS_ENTROPY) FUSED_LAUNCH2(NKS_, 5); else FUSED_LAUNCH2(NKS_, 0); \
-  } while (0)
-    if ((uint64_t)Ip * Bp > 0xFFFFFFFFull) return fail("full-output decode: G^T of %u x %u exceeds 2^32 elements; lower batch_users", Ip, Bp);
-    switch (Kp) { case 64: FUSED_LAUNCH(4); break; case 128: FUSED_LAUNCH(8); break; default: FUSED_LAUNCH(16); break; }
-#undef FUSED_LAUNCH2
-#undef FUSED_LAUNCH
-    hg_parts = slices;
+    CHK(launch_full_fused(h, st, b, nb));
+    hg_parts = h->full_slices;
   } else {
     CHK(full_products_k512(h, st, x, bt, nb, &hg_parts, &hg_rows));
   }
@@ -1069,53 +1156,7 @@ int compute_batch_full(cdae_hip* h, int b, const Batch& bt, uint64_t seed, uint3
     HIPCHK(hipGetLastError());
     return 0;
   }
-  // Second stream: delta_u, the Wu steps and then the strictly sequential hidden-bias recurrence (2048 users x 58 ns) need
-  // hg only; they run beside GEMM 3, and the row steps join them.
-  // (Round 4 measured GEMM 2 on this stream too, BESIDE the fused row launch of the K = 512 path, which needs G^T and Z^T only — two
-  // bf16 images of the decoder, swapped per block: 5.0 ms per 1024-user block against 4.75 in order.  The two launches stretch each
-  // other — GEMM 2 + hidden layer 1.2 -> 3.7 ms, row launch 2.3 -> 3.8 — because GEMM 2's LDS fill and the row launch's streams share
-  // the L2s and the fabric, and a CU holds one or the other, not both (139 KiB / 2 x 72 KiB of LDS).  Removed.)
-  HIPCHK(hipEventRecord(h->ev_fork, st));
-  HIPCHK(hipStreamWaitEvent(h->aux, h->ev_fork, 0));
-  {
-    Prof pa;
-    CHK(pa.begin(h, F_HIDDEN, h->aux));
-    DISPATCH_NI(h->NI, hidden_finish_kernel, dim3(nb), blk, 0, h->aux, h->hp, (const uint32_t*)h->d_iota, hg_rows, s0, nb, h->d_HGpart,
-                h->d_Dz, h->d_HG, h->d_Wu, h->d_Wu_ag, hg_parts, h->d_Uu, h->d_Uu_ag, h->d_Ssum, h->d_delta_rows);
-    CHK(pa.end());
-  }
-  HIPCHK(hipEventRecord(h->ev_delta, h->aux));
-  hipLaunchKernelGGL(hidden_bias_kernel, dim3((Kp + 255u) / 256u), blk, 0, h->aux, h->hp, nb, h->d_HG, h->P(CDAE_P_B), h->P(CDAE_P_B_AG));
-  HIPCHK(hipEventRecord(h->ev_join, h->aux));
-  // GEMM 3: dD = G^T Z  (contraction over the batch's users)
-  {
-    GemmEpilogue e3{};
-    e3.Cout = h->d_dD; e3.ldc = Kp;
-    if (!rows_fused)                                             // (rows_fused: the product stays in the accumulators of the row-step launch below)
-      CHK(launch_gemm_lds<EPI_STORE>(h, st, h->d_GTb, h->d_ZTb, Ip, Kp, Bp, Bp, Bp, Bp, e3, 1, 1));
-  }
-  CHK(pr.end());
-
-  HIPCHK(hipStreamWaitEvent(st, h->ev_delta, 0));
-  CHK(pr.begin(h, F_INPUT, st));
-  if (rows_fused)      // dD = G^T Z and the row steps from its accumulators (gemm3_rows_fused_kernel)
-    CHK(launch_rows_fused(h, st, x, nb, h->d_Db));
-  else if (I >= 32768u)     // rows are plentiful and mostly without kept inputs: one wavefront per row
-    DISPATCH_NI(h->NI, full_rows_wave_kernel, dim3((I + 3) / 4), blk, 0, st, h->hp, x.seg, x.seg + I, x.sorted_val, h->delta_rows(),
-                h->d_dD, h->d_GTb, Bp, nb, h->P(CDAE_P_W), h->P(CDAE_P_W_AG), h->P(CDAE_P_V), h->P(CDAE_P_V_AG), h->P(CDAE_P_BP),
-                h->P(CDAE_P_BP_AG), h->d_touched, rows_write_db ? h->d_Db : (__bf16*)nullptr);
-  else
-    DISPATCH_NI(h->NI, full_rows_kernel, dim3(I), blk, 0, st, h->hp, x.seg, x.seg + I, x.sorted_val, h->delta_rows(),
-                h->d_dD, h->d_GTb, Bp, nb, h->P(CDAE_P_W), h->P(CDAE_P_W_AG), h->P(CDAE_P_V), h->P(CDAE_P_V_AG), h->P(CDAE_P_BP),
-                h->P(CDAE_P_BP_AG), (float*)nullptr, (float*)nullptr, h->d_touched,
-                rows_write_images ? h->d_Db : (__bf16*)nullptr, rows_write_images ? h->d_DTb : (__bf16*)nullptr, Ip);
-  h->db_valid = rows_write_images;                             // every decoder row was stepped and imaged by this launch
-  h->db_rows_valid = rows_write_db;
-  h->join_pending = true;                                      // the aux stream (b recurrence) is joined by its next consumer: join_aux
-  CHK(pr.end());
-  HIPCHK(hipEventRecord(x.released, st));
-  HIPCHK(hipGetLastError());
-  return 0;
+  return full_tail(h, x, s0, nb, FullTail{hg_parts, hg_rows, nullptr, true, h->prof_q, &pr});
 }
 
 // IMF / BPR: one block of users (cdae_mf_kernels.hpp).  A block of one user is the reference loop itself (in place).
@@ -1180,19 +1221,8 @@ constexpr uint32_t EVAL_CHUNK = 32768;
 constexpr uint32_t SHARD_BLOCKS = 3;
 inline uint32_t shard_blocks_of(const cdae_hip* h) { return 1u + (h->cfg.user_factor ? 1u : 0u) + (h->cfg.linear_function ? 1u : 0u); }
 int ensure_eval_ws(cdae_hip* h, uint32_t users, uint32_t units) {
-  if (h->eval_cap < users) {
-    if (h->d_zeval) HIPCHK(hipFree(h->d_zeval));
-    h->d_zeval = nullptr; h->eval_cap = 0;
-    CHK(dev_alloc(&h->d_zeval, (size_t)users * h->Kp));
-    h->eval_cap = users;
-  }
-  if (h->eval_unit_cap < units) {
-    if (h->d_hpart_eval) HIPCHK(hipFree(h->d_hpart_eval));
-    h->d_hpart_eval = nullptr; h->eval_unit_cap = 0;
-    CHK(dev_alloc(&h->d_hpart_eval, (size_t)units * h->Kp));
-    h->eval_unit_cap = units;
-  }
-  return 0;
+  CHK(ensure_cap(&h->d_zeval, &h->eval_cap, users, h->Kp));
+  return ensure_cap(&h->d_hpart_eval, &h->eval_unit_cap, units, h->Kp);
 }
 
 inline bool is_user_indexed(uint32_t which) {
@@ -2182,31 +2212,44 @@ void topn_chunk(cdae_hip* h, uint32_t topk, uint64_t u0, uint32_t nu) {
                      (const int64_t*)h->d_test_ptr, (const uint32_t*)h->d_test_col, (double)h->test_users_with_rows, h->d_topn_pu,
                      reinterpret_cast<unsigned long long*>(h->d_topn_out + 8));
 }
+// recommend_kernel over this handle's item rows, for the single handle's general path and an item shard's local lists alike.  A
+// user's score row sits in LDS where num_items floats fit; otherwise the scores of a launch go to a global workspace of <= 256 MiB,
+// which bounds the users of one launch.  prepare(): that decision, the workspaces (lists in d_rec; with_scores: their scores in
+// d_rec_score) and the dynamic-LDS attribute; launch(): one chunk of at most `chunk` users.
+struct Scorer {
+  bool in_lds = false, with_scores = false;
+  size_t shmem = 0;
+  uint32_t chunk = 0, topk = 0;
+  int prepare(cdae_hip* h, uint32_t users, uint32_t topk_, bool with_scores_) {
+    const size_t lds_scores = (size_t)h->I * sizeof(float) + 64;
+    in_lds = lds_scores <= 160 * 1024;
+    shmem = in_lds ? lds_scores : 64;
+    chunk = users; topk = topk_; with_scores = with_scores_;
+    if (!in_lds) {
+      chunk = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(users, (256ull << 20) / ((uint64_t)h->I * sizeof(float))));
+      CHK(ensure_cap(&h->d_score, &h->score_cap, (size_t)chunk * h->I));
+    }
+    CHK(ensure_cap(&h->d_rec, &h->rec_cap, (size_t)chunk * topk));
+    if (with_scores) CHK(ensure_cap(&h->d_rec_score, &h->rec_score_cap, (size_t)chunk * topk));
+    const void* kernel = h->NI == 1 ? (const void*)cdae::recommend_kernel<1> : h->NI == 2 ? (const void*)cdae::recommend_kernel<2>
+                       : h->NI == 4 ? (const void*)cdae::recommend_kernel<4> : (const void*)cdae::recommend_kernel<8>;
+    HIPCHK(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
+    return 0;
+  }
+  // users [u0, u0 + nb) with hidden rows z; d_rated != nullptr: the caller's input set instead of the train row (one user)
+  void launch(cdae_hip* h, uint64_t u0, uint32_t nb, const float* z, const uint32_t* d_rated = nullptr, uint32_t n_rated = 0) const {
+    DISPATCH_NI(h->NI, cdae::recommend_kernel, dim3(nb), dim3(256), shmem, h->stream, h->hp, h->d_row_ptr, h->d_col, u0, z, h->dec(),
+                h->P(CDAE_P_BP), topk, h->d_rec, in_lds ? (float*)nullptr : h->d_score, d_rated, n_rated,
+                with_scores ? h->d_rec_score : (float*)nullptr);
+  }
+};
+
 int recommend_general(cdae_hip* h, uint64_t u_begin, uint64_t u_end, uint32_t topk, uint32_t* out, const uint32_t* rated, uint32_t n_rated) {
-  const size_t lds_scores = (size_t)h->I * sizeof(float) + 64;
-  const bool in_lds = lds_scores <= 160 * 1024;
-  const size_t shmem = in_lds ? lds_scores : 64;
   // users per launch: a chunk of the EVALUATION workspace, not of the training batch (through round 3 it was batch_users: a handle
   // with one user per block — the reference schedule — evaluated 16 384 users in 16 384 launches + host round trips, 75 s)
-  uint32_t B = rated ? 1u : (uint32_t)std::min<uint64_t>(h->mf ? EVAL_CHUNK : 4096u, std::max<uint64_t>(h->U, 1));
-  if (!in_lds) {     // scores of a launch in a global workspace of <= 256 MiB
-    B = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(B, (256ull << 20) / ((uint64_t)h->I * sizeof(float))));
-    if (h->score_cap < (size_t)B * h->I) {
-      if (h->d_score) HIPCHK(hipFree(h->d_score));
-      h->d_score = nullptr; h->score_cap = 0;
-      CHK(dev_alloc(&h->d_score, (size_t)B * h->I));
-      h->score_cap = (size_t)B * h->I;
-    }
-  }
-  if (h->rec_cap < (size_t)B * topk) {
-    if (h->d_rec) HIPCHK(hipFree(h->d_rec));
-    h->d_rec = nullptr; h->rec_cap = 0;
-    CHK(dev_alloc(&h->d_rec, (size_t)B * topk));
-    h->rec_cap = (size_t)B * topk;
-  }
-#define SET_SHMEM(NI_) HIPCHK(hipFuncSetAttribute((const void*)cdae::recommend_kernel<NI_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem))
-  switch (h->NI) { case 1: SET_SHMEM(1); break; case 2: SET_SHMEM(2); break; case 4: SET_SHMEM(4); break; default: SET_SHMEM(8); break; }
-#undef SET_SHMEM
+  Scorer sc;
+  CHK(sc.prepare(h, rated ? 1u : (uint32_t)std::min<uint64_t>(h->mf ? EVAL_CHUNK : 4096u, std::max<uint64_t>(h->U, 1)), topk, false));
+  const uint32_t B = sc.chunk;
   uint32_t* d_rated = nullptr;
   if (rated) {
     CHK(dev_alloc(&d_rated, std::max<uint32_t>(n_rated, 1)));
@@ -2231,8 +2274,7 @@ int recommend_general(cdae_hip* h, uint64_t u_begin, uint64_t u_end, uint32_t to
       if (!rc) rc = encode_chunk(h, nullptr, s0, nb, 0, CDAE_STREAM_CORRUPT, 0, 0, 0, 0, h->d_zeval, h->d_hpart_eval, h->eval_unit_cap);      // cdae.hpp:167-172
       if (rc) break;
     }
-    DISPATCH_NI(h->NI, cdae::recommend_kernel, dim3(nb), dim3(256), shmem, h->stream, h->hp, h->d_row_ptr, h->d_col, s0,
-                h->mf ? h->d_Wu + (size_t)s0 * h->Kp : (rated ? h->d_Z : h->d_zeval), h->dec(), h->P(CDAE_P_BP), topk, h->d_rec, in_lds ? (float*)nullptr : h->d_score, (const uint32_t*)d_rated, n_rated, (float*)nullptr);
+    sc.launch(h, s0, nb, h->mf ? h->d_Wu + (size_t)s0 * h->Kp : (rated ? h->d_Z : h->d_zeval), d_rated, n_rated);
     hipError_t e = hipGetLastError();
     if (e == hipSuccess && h->topn_active) { topn_chunk(h, topk, s0, nb); e = hipGetLastError(); }
     if (e == hipSuccess && out) e = hipMemcpyAsync(out + (s0 - u_begin) * topk, h->d_rec, (size_t)nb * topk * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream);
@@ -2490,18 +2532,8 @@ int cdae_hip_recommend_all(cdae_hip_t* h, uint64_t u_begin, uint64_t u_end, uint
     const uint32_t words = (uint32_t)((h->I + 31) / 32);
     const uint64_t n_all = u_end - u_begin;
     const uint32_t UC = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(n_all, 1), EVAL_CHUNK);
-    if (h->bits_cap < (size_t)UC * words) {
-      if (h->d_bits) HIPCHK(hipFree(h->d_bits));
-      h->d_bits = nullptr; h->bits_cap = 0;
-      CHK(dev_alloc(&h->d_bits, (size_t)UC * words));
-      h->bits_cap = (size_t)UC * words;
-    }
-    if (h->rec_cap < (size_t)UC * topk) {
-      if (h->d_rec) HIPCHK(hipFree(h->d_rec));
-      h->d_rec = nullptr; h->rec_cap = 0;
-      CHK(dev_alloc(&h->d_rec, (size_t)UC * topk));
-      h->rec_cap = (size_t)UC * topk;
-    }
+    CHK(ensure_cap(&h->d_bits, &h->bits_cap, (size_t)UC * words));
+    CHK(ensure_cap(&h->d_rec, &h->rec_cap, (size_t)UC * topk));
     const size_t lds = cdae::recommend_mfma_lds_bytes((int)nch);
     for (uint64_t c0 = u_begin; c0 < u_end; c0 += UC) {
       const uint32_t nu = (uint32_t)std::min<uint64_t>(UC, u_end - c0);
@@ -2569,12 +2601,7 @@ int cdae_hip_eval_topn(cdae_hip_t* h, uint32_t topk, double* rets8, uint64_t* hi
     CHK(cdae_hip_recommend_all(h, 0, h->U, topk, all.data()));
     if (ids_out) std::copy(all.begin(), all.end(), ids_out);
     const uint32_t UC = (uint32_t)std::min<uint64_t>(h->U, EVAL_CHUNK);
-    if (h->rec_cap < (size_t)UC * topk) {
-      if (h->d_rec) HIPCHK(hipFree(h->d_rec));
-      h->d_rec = nullptr; h->rec_cap = 0;
-      CHK(dev_alloc(&h->d_rec, (size_t)UC * topk));
-      h->rec_cap = (size_t)UC * topk;
-    }
+    CHK(ensure_cap(&h->d_rec, &h->rec_cap, (size_t)UC * topk));
     HIPCHK(hipMemsetAsync(h->d_topn_out, 0, 16 * sizeof(double), h->stream));
     for (uint64_t c0 = 0; c0 < h->U; c0 += UC) {
       const uint32_t nu = (uint32_t)std::min<uint64_t>(UC, h->U - c0);
@@ -3014,23 +3041,8 @@ int fs_phase1(cdae_hip_t* h, uint64_t s0, uint32_t nb) {
   HIPCHK(hipStreamWaitEvent(st, x.ready, 0));
   uint32_t parts = 0, rows = nb;
   if (Kp <= 256 && !h->full_unfused) {
-    const uint32_t words = (I + 31) / 32, slices = h->full_slices, tiles = Ip / (32 * FUSED_SUB);
-    const uint32_t* bits = h->d_bits_train + (size_t)b * h->bits_stride;
-    const uint32_t tps = (tiles + slices - 1) / slices;
-    const dim3 grid(slices, Bp / 128);
-    const size_t lds = full_fused_lds_bytes(Kp);
-    if ((uint64_t)Ip * Bp > 0xFFFFFFFFull) return fail("full-output decode: G^T of %u x %u exceeds 2^32 elements; lower batch_users", Ip, Bp);
-#define FS_FUSED2(NKS_, L_)                                                                                                              \
-  do {                                                                                                                                  \
-    HIPCHK(hipFuncSetAttribute((const void*)full_decode_fused_kernel<NKS_, L_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));  \
-    hipLaunchKernelGGL((full_decode_fused_kernel<NKS_, L_>), grid, blk, lds, st, h->hp, h->d_Zb, h->d_Db, h->d_DTb, Ip, h->P(CDAE_P_BP), \
-                       bits, words, nb, tps, h->d_GTb, Bp, h->d_HGpart);                                                                 \
-  } while (0)
-#define FS_FUSED(NKS_) do { if (h->cfg.loss_type == CDAE_LOSS_CROSS_ENTROPY) FS_FUSED2(NKS_, 5); else FS_FUSED2(NKS_, 0); } while (0)
-    switch (Kp) { case 64: FS_FUSED(4); break; case 128: FS_FUSED(8); break; default: FS_FUSED(16); break; }
-#undef FS_FUSED
-#undef FS_FUSED2
-    parts = slices; rows = nb;
+    CHK(launch_full_fused(h, st, b, nb));
+    parts = h->full_slices; rows = nb;
   } else {
     Prof prd;
     CHK(prd.begin(h, F_DECODE, st, h->seq));
@@ -3048,60 +3060,14 @@ int fs_phase2(cdae_hip_t* h, uint64_t s0, uint32_t nb) {
   HIPCHK(hipSetDevice(h->device));
   Batch bt;
   CHK(fs_batch(h, s0, nb, 0, &bt));
-  const int b = (int)(h->seq & 1);
-  cdae_hip::ExBuf& x = h->ex[b];
-  hipStream_t st = h->stream;
-  const uint32_t I = (uint32_t)h->I, Kp = h->Kp, Bp = h->Bp, Ip = h->Ip;
-  const dim3 blk(256), grid_users((nb + 3) / 4);
+  cdae_hip::ExBuf& x = h->ex[h->seq & 1];
   const float* uu_b = gathered_uu(h, h->d_Hsum, nb);
-  if (!h->cfg.full_output) {
-    // ---- sampled decode: delta from the all-reduced hg, the Wu / Uu steps of the users this shard owns, then the local input rows
-    // and (replicated, identical everywhere) the b recurrence — the tail of the single-GPU step ----
-    DISPATCH_NI(h->NI, hidden_finish_kernel, dim3(nb), blk, 0, st, h->hp, (const uint32_t*)h->d_iota, nb, s0, nb, h->d_HGpart, h->d_Dz,
-                h->d_HG, h->d_Wu, h->d_Wu_ag, 0u, h->d_Uu, h->d_Uu_ag, h->d_Ssum, h->d_delta_rows, uu_b);
-    const uint32_t bias_blocks = (h->Kp + 255u) / 256u;
-    DISPATCH_NI(h->NI, input_rows_kernel, dim3(bias_blocks + (I + 3) / 4), blk, 0, st, h->hp, h->d_item_order, x.seg + 2 * (size_t)I, x.seg + 3 * (size_t)I,
-                x.sorted_val, h->d_Z, h->d_HG, h->d_G, h->P(CDAE_P_W), h->P(CDAE_P_W_AG), CDAE_TOUCHED_ARG, nb, h->P(CDAE_P_B),
-                h->P(CDAE_P_B_AG), h->delta_rows());
-    HIPCHK(hipEventRecord(x.released, st));
-    HIPCHK(hipGetLastError());
-    h->seq++;
-    h->acc_examples += bt.E; h->acc_batches++; h->acc_users += nb;
-    return 0;
-  }
-  HIPCHK(hipEventRecord(h->ev_fork, st));
-  HIPCHK(hipStreamWaitEvent(h->aux, h->ev_fork, 0));
-  // d_HG holds the all-reduced hg: delta, the Wu steps of the users this shard owns, then the b recurrence (replicated)
-  DISPATCH_NI(h->NI, hidden_finish_kernel, dim3(nb), blk, 0, h->aux, h->hp, (const uint32_t*)h->d_iota, nb, s0, nb, h->d_HGpart, h->d_Dz,
-              h->d_HG, h->d_Wu, h->d_Wu_ag, 0u, h->d_Uu, h->d_Uu_ag, h->d_Ssum, h->d_delta_rows, uu_b);
-  HIPCHK(hipEventRecord(h->ev_delta, h->aux));
-  hipLaunchKernelGGL(hidden_bias_kernel, dim3((Kp + 255u) / 256u), blk, 0, h->aux, h->hp, nb, h->d_HG, h->P(CDAE_P_B), h->P(CDAE_P_B_AG));
-  HIPCHK(hipEventRecord(h->ev_join, h->aux));
-  const bool rows_fused = rows_fused_path(h);
-  if (!rows_fused) {
-    GemmEpilogue e3{};
-    e3.Cout = h->d_dD; e3.ldc = Kp;
-    CHK(launch_gemm_lds<EPI_STORE>(h, st, h->d_GTb, h->d_ZTb, Ip, Kp, Bp, Bp, Bp, Bp, e3, 1, 1));
-  }
-  HIPCHK(hipStreamWaitEvent(st, h->ev_delta, 0));
-  Prof pri;
-  CHK(pri.begin(h, F_INPUT, st, h->seq));
-  if (rows_fused)      // dD = G^T Z and the row steps from its accumulators, the row-major bf16 image left current
-    CHK(launch_rows_fused(h, st, x, nb, h->d_Db));
-  else if (I >= 32768u)
-    DISPATCH_NI(h->NI, full_rows_wave_kernel, dim3((I + 3) / 4), blk, 0, st, h->hp, x.seg, x.seg + I, x.sorted_val, h->delta_rows(),
-                h->d_dD, h->d_GTb, Bp, nb, h->P(CDAE_P_W), h->P(CDAE_P_W_AG), h->P(CDAE_P_V), h->P(CDAE_P_V_AG), h->P(CDAE_P_BP),
-                h->P(CDAE_P_BP_AG), h->d_touched);
-  else
-    DISPATCH_NI(h->NI, full_rows_kernel, dim3(I), blk, 0, st, h->hp, x.seg, x.seg + I, x.sorted_val, h->delta_rows(),
-                h->d_dD, h->d_GTb, Bp, nb, h->P(CDAE_P_W), h->P(CDAE_P_W_AG), h->P(CDAE_P_V), h->P(CDAE_P_V_AG), h->P(CDAE_P_BP),
-                h->P(CDAE_P_BP_AG), (float*)nullptr, (float*)nullptr, h->d_touched);
-  CHK(pri.end());
-  h->db_valid = false;
-  h->db_rows_valid = rows_fused;                                 // the fused row step imaged every decoder row it stepped
-  h->join_pending = true;
-  HIPCHK(hipEventRecord(x.released, st));
-  HIPCHK(hipGetLastError());
+  // the tail of the single handle's step over the local rows: d_HG holds the all-reduced hg (no slab to add, no late-row terms), delta
+  // and the Wu / Uu steps are those of the users this shard owns, the b recurrence is replicated (identical everywhere).  Full
+  // output: the row kernels write no bf16 image here — phase 1 converts the decoder — except the fused row step, which always
+  // leaves the row-major image current
+  if (!h->cfg.full_output) CHK(sampled_tail(h, x, s0, nb, h->d_iota, nb, 0u, uu_b, LateFinish{}, nullptr));
+  else CHK(full_tail(h, x, s0, nb, FullTail{0u, nb, uu_b, false, h->seq, nullptr}));
   h->seq++;
   h->acc_examples += bt.E; h->acc_batches++; h->acc_users += nb;
   return 0;
@@ -3114,12 +3080,7 @@ int ev_phase0(cdae_hip_t* h, uint64_t u0, uint32_t nu, int mode, uint32_t cidx, 
   CHK(join_aux(h));
   const uint32_t n_units = h->h_unit_ptr[u0 + nu] - h->h_unit_ptr[u0];
   CHK(ensure_eval_ws(h, nu, std::max<uint32_t>(n_units, 1u)));
-  if (h->hsum_eval_cap < nu) {
-    if (h->d_hsum_eval) HIPCHK(hipFree(h->d_hsum_eval));
-    h->d_hsum_eval = nullptr; h->hsum_eval_cap = 0;
-    CHK(dev_alloc(&h->d_hsum_eval, (size_t)SHARD_BLOCKS * nu * h->Kp));
-    h->hsum_eval_cap = nu;
-  }
+  CHK(ensure_cap(&h->d_hsum_eval, &h->hsum_eval_cap, nu, (size_t)SHARD_BLOCKS * h->Kp));
   const uint32_t* uptr = h->d_unit_ptr + u0;
   if (n_units)
     DISPATCH_NI(h->NI, cdae::encode_partial_kernel, dim3((n_units + 3) / 4), dim3(256), 0, h->stream, h->hp, h->d_row_ptr, h->d_col,
@@ -3157,39 +3118,11 @@ int ev_data_loss(cdae_hip_t* h, uint64_t u0, uint32_t nu, double* sum) {
 int ev_recommend(cdae_hip_t* h, uint64_t u0, uint32_t nu, uint32_t topk, uint32_t* ids, float* scores) {
   HIPCHK(hipSetDevice(h->device));
   if (topk == 0 || topk > h->I) return fail("topk %u exceeds the %llu items of this shard", topk, (unsigned long long)h->I);
-  const size_t lds_scores = (size_t)h->I * sizeof(float) + 64;
-  const bool in_lds = lds_scores <= 160 * 1024;
-  const size_t shmem = in_lds ? lds_scores : 64;
-  uint32_t Bq = nu;
-  if (!in_lds) {
-    Bq = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(nu, (256ull << 20) / ((uint64_t)h->I * sizeof(float))));
-    if (h->score_cap < (size_t)Bq * h->I) {
-      if (h->d_score) HIPCHK(hipFree(h->d_score));
-      h->d_score = nullptr; h->score_cap = 0;
-      CHK(dev_alloc(&h->d_score, (size_t)Bq * h->I));
-      h->score_cap = (size_t)Bq * h->I;
-    }
-  }
-  if (h->rec_cap < (size_t)Bq * topk) {
-    if (h->d_rec) HIPCHK(hipFree(h->d_rec));
-    h->d_rec = nullptr; h->rec_cap = 0;
-    CHK(dev_alloc(&h->d_rec, (size_t)Bq * topk));
-    h->rec_cap = (size_t)Bq * topk;
-  }
-  if (h->rec_score_cap < (size_t)Bq * topk) {
-    if (h->d_rec_score) HIPCHK(hipFree(h->d_rec_score));
-    h->d_rec_score = nullptr; h->rec_score_cap = 0;
-    CHK(dev_alloc(&h->d_rec_score, (size_t)Bq * topk));
-    h->rec_score_cap = (size_t)Bq * topk;
-  }
-#define SET_SHMEM(NI_) HIPCHK(hipFuncSetAttribute((const void*)cdae::recommend_kernel<NI_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem))
-  switch (h->NI) { case 1: SET_SHMEM(1); break; case 2: SET_SHMEM(2); break; case 4: SET_SHMEM(4); break; default: SET_SHMEM(8); break; }
-#undef SET_SHMEM
-  for (uint32_t c0 = 0; c0 < nu; c0 += Bq) {
-    const uint32_t nb = std::min(Bq, nu - c0);
-    DISPATCH_NI(h->NI, cdae::recommend_kernel, dim3(nb), dim3(256), shmem, h->stream, h->hp, h->d_row_ptr, h->d_col, u0 + c0,
-                h->d_zeval + (size_t)c0 * h->Kp, h->dec(), h->P(CDAE_P_BP), topk, h->d_rec, in_lds ? (float*)nullptr : h->d_score,
-                (const uint32_t*)nullptr, 0u, h->d_rec_score);
+  Scorer sc;
+  CHK(sc.prepare(h, nu, topk, true));
+  for (uint32_t c0 = 0; c0 < nu; c0 += sc.chunk) {
+    const uint32_t nb = std::min(sc.chunk, nu - c0);
+    sc.launch(h, u0 + c0, nb, h->d_zeval + (size_t)c0 * h->Kp);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(ids + (size_t)c0 * topk, h->d_rec, (size_t)nb * topk * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipMemcpyAsync(scores + (size_t)c0 * topk, h->d_rec_score, (size_t)nb * topk * sizeof(float), hipMemcpyDeviceToHost, h->stream));

@@ -492,7 +492,7 @@ struct Oracle {
   //        gemm1_loss_duo_kernel); here the exact sum of the same rounded operands.
   //   g  : bf16(loss'(y, t)), rounded ONCE (full_decode_fused_kernel's `(__bf16)g`; GemmEpilogue EPI_LOSS / gemm1_loss_duo_kernel
   //        for the negatives of the unfused plans).
-  //   unrounded_positives (the unfused plans: K > 256, CDAE_FULL_UNFUSED, the item-rows shards): full_positive_fixup_kernel
+  //   unrounded_positives (the unfused plans: K > 256, CDAE_FULL_UNFUSED, on one handle or on item-rows shards): full_positive_fixup_kernel
   //        recomputes a positive's y from the fp32 z row and decoder row, not their bf16 images, and stores bf16(loss'(y, 1));
   //        here y = the unrounded z . D + b' for the positives.
   //   hg, dD, db': fp32 sums of bf16 g times bf16 D / z (GEMM 2, GEMM 3, the row step's column sums of G^T); here exact sums.

@@ -4,8 +4,9 @@ The other full-output tests compare the device with the fp64 oracle within a few
 path with another bit for bit; neither sees a fault that moves a few elements a little, or one that every path shares (the loss
 epilogue's masking, the positive fix-up, the b' sums, the padding of Kp / Ip / Bp).  The faithful oracle rounds z, D and g to bf16
 exactly where the device does (oracle/cdae_oracle.cpp train_users_full), so what is left between the two is fp32 arithmetic.  On the
-unfused plans (K > 256, CDAE_FULL_UNFUSED, the item-rows shards) full_positive_fixup_kernel recomputes a positive's y from the fp32 z
-and decoder rows rather than their bf16 images; those cases run the oracle with unrounded_positives=True.
+unfused plans (K > 256, CDAE_FULL_UNFUSED) full_positive_fixup_kernel recomputes a positive's y from the fp32 z and decoder rows
+rather than their bf16 images; those cases run the oracle with unrounded_positives=True.  An item-rows shard takes the plan of a
+single handle of the same K: the fused kernel at K <= 256 (no fix-up), the unfused products above.
 
 Tier A — exact known-answer step.  SQUARE, SGD, linear hidden layer, lambda = 0, learn rate 2^-4, scale 1 or 2, every parameter an
 integer multiple of 2^-4 (asymmetric values, most of them small).  Then z is on the 2^-4 grid, y = z . D + b' on 2^-8, g = 2 (y - t)
@@ -97,10 +98,11 @@ def oracle_of(model, data, cfg_kw):
     return o
 
 
-def assert_plan(model, want_plan, shards, data):
+def assert_plan(model, want_plan, shards, data, min_largest_shard=0):
     if shards:
         cuts = model.shards()
         assert len(cuts) == shards and cuts[0][0] == 0 and cuts[-1][1] == data.num_items, cuts
+        assert max(b - a for a, b in cuts) >= min_largest_shard, cuts
     else:
         assert model.full_output_plan == want_plan, (model.full_output_plan, want_plan)
 
@@ -110,8 +112,10 @@ def grid(rng, shape, choices):
     return rng.choice(np.asarray(choices, dtype=np.float64), size=shape) * 2.0 ** -E
 
 
-def tier_a(data, K, B, nb, *, asym, scale2, want_plan, shards=0, double_rounding=False, dense=0.3):
-    """one block of nb users on the exact grid: premise, then bit equality with the faithful oracle"""
+def tier_a(data, K, B, nb, *, asym, scale2, want_plan, shards=0, double_rounding=False, dense=0.3, min_largest_shard=0):
+    """one block of nb users on the exact grid: premise, then bit equality with the faithful oracle.
+    shards: MultiCDAE(item_rows=True) over that many logical shards; of want_plan only the FUSED bit then matters (every shard
+    decodes with the fused kernel, or none does: the choice depends on K alone)"""
     rng = np.random.default_rng(K * 7919 + data.num_items * 31 + nb)
     U, I = data.num_users, data.num_items
     flags = dict(using_adagrad=False, asymmetric=asym, user_factor=True, linear=True, scaled=scale2, tanh=False, linear_function=False)
@@ -119,7 +123,7 @@ def tier_a(data, K, B, nb, *, asym, scale2, want_plan, shards=0, double_rounding
     cfg = cdae_amd.CDAEConfig(num_dim=K, lt=cdae_amd.SQUARE, batch_users=B, full_output=True, **flags, **hyper)
     model = new_model(cfg, shards)
     model.reset(data, seed=3)
-    assert_plan(model, want_plan, shards, data)
+    assert_plan(model, want_plan, shards, data, min_largest_shard)
     sparse = [-2, -1] + [0] * int(6 * (1 - dense) / max(dense, 1e-3)) + [1, 3]      # asymmetric values, mostly 0
     params = {cdae_amd.P_W: grid(rng, (I, K), sparse), cdae_amd.P_WU: grid(rng, (U, K), [-1, 0, 0, 2]),
               cdae_amd.P_B: grid(rng, K, [-1, 0, 1, 3])}
@@ -153,7 +157,7 @@ def tier_a(data, K, B, nb, *, asym, scale2, want_plan, shards=0, double_rounding
         n_diff = int(((twice != G) & (T == 1)).sum())
         assert n_diff > 0, "no positive tells one rounding from two"
     model.train_users(SEED, 0, 0, nb)
-    o.train_full(SEED, 0, B, 0, nb, bf16=True, unrounded_positives=bool(shards) or not want_plan & FUSED)
+    o.train_full(SEED, 0, B, 0, nb, bf16=True, unrounded_positives=not want_plan & FUSED)
     for which in range(ob.P_COUNT):
         ref = o.get(which)
         if not ref.size or (which in (ob.P_V, ob.P_V_AG) and not asym):
@@ -181,6 +185,7 @@ CASES_FUSED = [
     (129, 33, 40, 31, 31, False, True, {"CDAE_FULL_ONE_STREAM_MAX": "0"}, FUSED),
     (256, 4097, 140, 256, 129, True, True, {"CDAE_FULL_ONE_STREAM_MAX": "0"}, FUSED),
     (256, 129, 140, 128, 128, False, False, {}, FUSED),
+    (64, 65537, 4, 48, 2, True, True, {}, FUSED),           # >= 32768 items at Kp <= 256: full_rows_wave_kernel, the row-major image only
 ]
 CASES_UNFUSED = [
     (40, 4097, 60, 128, 33, False, True, {"CDAE_FULL_UNFUSED": "1"}, 0),
@@ -195,13 +200,13 @@ CASES_UNFUSED = [
 ]
 
 
-def _run(devlib, monkeypatch, case, double_rounding):
+def _run(devlib, monkeypatch, case, double_rounding, **kw):
     K, I, users, B, nb, asym, scale2, env, plan = case
     for k, v in env.items():
         monkeypatch.setenv(k, v)
     data = make_data(users, I, 24 if I > 64 else max(1, I // 2), np.random.default_rng(I + users))
     tier_a(data, K, B, nb, asym=asym, scale2=scale2, want_plan=plan, double_rounding=double_rounding,
-           dense=0.3 if I * K < 2_000_000 else 0.1)
+           dense=0.3 if I * K < 2_000_000 else 0.1, **kw)
 
 
 @pytest.mark.parametrize("case", CASES_FUSED, ids=lambda c: f"K{c[0]}-I{c[1]}-B{c[3]}-nb{c[4]}-{'asym' if c[5] else 'tied'}"
@@ -219,7 +224,30 @@ def test_exact_step_unfused_and_k512(devlib, monkeypatch, case):
 def test_exact_step_item_rows_eight_shards(built):
     """Kp = 512 on MultiCDAE(item_rows=True): each of 8 shards runs the K > 256 products over its own item rows (fs_phase1)"""
     data = make_data(260, 3000, 24, np.random.default_rng(8))
-    tier_a(data, 300, 256, 40, asym=False, scale2=True, want_plan=None, shards=8, double_rounding=True)
+    tier_a(data, 300, 256, 40, asym=False, scale2=True, want_plan=0, shards=8, double_rounding=True)
+
+
+# Item-rows shards run the launch sequences of the single handle (cdae_hip.hip: launch_full_fused, full_products_k512, full_tail) over
+# their own item rows.  Each case is a tuple of CASES_FUSED / CASES_UNFUSED: make_data and tier_a seed from its values alone, so data,
+# parameters and the exact-grid premise are the ones that case already runs on one handle.  (case, shards, items the largest shard must hold)
+CASES_ITEM_ROWS = [
+    (CASES_FUSED[5], 2, 0),          # K 65 (Kp = 128), 129 items, tied: the fused kernel on two shards
+    (CASES_FUSED[7], 3, 0),          # K 256, 4097 items, asymmetric: the fused kernel on three shards
+    (CASES_UNFUSED[5], 3, 0),        # K 512, 3000 items, asymmetric: the K > 256 products on three shards
+    # K 300 (Kp = 512), 65537 items on two shards: one of them holds >= 32768 items, whichever way the cut falls.  Its Ip is a multiple
+    # of 256, so rows_fused_path holds (Ip % FR_ITEMS == 0) and it runs gemm3_rows_fused_kernel; the other shard, below 32768 items,
+    # runs GEMM 3 + full_rows_kernel.
+    (CASES_UNFUSED[8], 2, 32768),
+    (CASES_FUSED[9], 2, 32768),      # K 64, 65537 items: the shard of >= 32768 items runs full_rows_wave_kernel, the other full_rows_kernel
+]
+
+
+@pytest.mark.parametrize("case,shards,largest", CASES_ITEM_ROWS,
+                         ids=[f"K{c[0]}-I{c[1]}-B{c[3]}-nb{c[4]}-{'asym' if c[5] else 'tied'}-shards{s}" for c, s, _ in CASES_ITEM_ROWS])
+def test_exact_step_item_rows_shards(built, monkeypatch, case, shards, largest):
+    """the shared full-output launches on MultiCDAE(item_rows=True): fused and K > 256 plans, tied and asymmetric, each of the three
+    row steps.  (The shipped library: the developer switches in the tuples do not apply to a shard.)"""
+    _run(None, monkeypatch, case[:7] + ({}, case[8]), double_rounding=not case[8] & FUSED, shards=shards, min_largest_shard=largest)
 
 
 # ---- Tier B ------------------------------------------------------------------------------------------------------------------------

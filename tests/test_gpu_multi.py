@@ -327,6 +327,25 @@ def test_item_rows_sampled_with_one_shard_is_the_single_handle_bit_for_bit(built
     assert abs(la - lb) <= 1e-12 * abs(lb)
 
 
+@pytest.mark.parametrize("K,B", [(24, 48), (300, 64)])
+def test_item_rows_full_output_with_one_shard_is_the_single_handle_bit_for_bit(built, K, B):
+    """Full-output decode, one item shard: the products and the two-stream tail are the single handle's launches (K 24: the fused
+    kernel, K 300: the K > 256 products).  The schedules differ in where hg is summed — slab_sum_kernel, then hidden_finish_kernel
+    over the sum, against hidden_finish_kernel over the slabs — and in who writes the bf16 images; neither changes a bit."""
+    d = synth.generate_shape("tiny", seed=5)
+    cfg = cfg_of(K=K, B=B, full_output=True)
+    one = cdae_amd.CDAE(cfg)
+    one.reset(d, seed=11)
+    mm = cdae_amd.MultiCDAE(cfg, devices=[0], item_rows=True)
+    mm.reset(d, seed=11)
+    for ep in range(2):
+        mm.train_one_iteration(3, ep)
+        one.train_one_iteration(3, ep)
+    a, b = _all_params(mm), _all_params(one)
+    for w in a:
+        np.testing.assert_array_equal(a[w], b[w], err_msg=f"parameter {w}")
+
+
 @pytest.mark.parametrize("K,B,shards,kw", [(24, 48, 2, {}), (24, 300, 3, {}), (200, 64, 4, {}), (300, 32, 2, {}), (24, 48, 3, dict(asymmetric=True)),
                                            (24, 48, 2, dict(linear_function=True)), (24, 64, 5, dict(lt=cdae_amd.SQUARE, beta=1.0))])
 def test_item_rows_sampled_layout_is_the_single_gpu_schedule(built, K, B, shards, kw):
