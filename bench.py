@@ -12,6 +12,11 @@ is fixed; --scaling strong shards ONE data set instead) and the ranks exchange t
 shared parameters with one RCCL all-reduce per period on a communicator the library owns (cdae_multi.hip).
 Inputs (CSR, parameters) are resident in HBM before the timed region.  Timing: barrier +
 torch.cuda.synchronize() on both sides of exactly K steps, max over ranks; rank 0 prints ONE JSON line.
+
+A plain run does only what that line's headline needs: set-up, the untimed pre-warm and W warm-up steps, the K timed steps (HIP events
+around the decode launches inside them), --dump-outputs, the line.  `--full` adds, around the same timed steps, what takes runs of its
+own: the one-core CPU baseline, the untimed pass that times the other kernel families, shard 0's launches of --layout item-rows and the
+same-node side figures of --layout certified.
 """
 from __future__ import annotations
 
@@ -151,8 +156,14 @@ def main():
                          "sequential reference (mean over six fixture seeds within +-0.002, tests/test_gpu_accuracy.py)")
     ap.add_argument("--shape", default="ml10m")
     ap.add_argument("--num-dim", type=int, default=200)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--cpu-users", type=int, default=40000, help="users in the timed CPU-baseline sample (~20 s)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need, each in a run of its own beside the timed steps: the CPU baseline "
+                         "(`cpu_baseline`), the kernel families other than the decode (`kernel_ms_per_step`, an untimed pass behind the timed steps), "
+                         "shard 0's launches of --layout item-rows and the same-node side figures of --layout certified.  Off by default: a plain "
+                         "run sets up, warms up, times the K steps, writes --dump-outputs and prints the line.  The timed steps, `value`, "
+                         "`ms_per_step` and the dumped arrays are the same either way")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--cpu-users", type=int, default=40000, help="--full: users in the timed CPU-baseline sample (~20 s)")
     ap.add_argument("--seed", type=int, default=20141119)
     ap.add_argument("--profile-every", type=int, default=8, help="HIP-event kernel timing on every n-th batch (0 = off)")
     ap.add_argument("--full-output", action="store_true", help="BASELINE configs[1]/[4]: every unrated item is a negative; "
@@ -166,7 +177,7 @@ def main():
                     help="How N > 1 GPUs divide the model.  certified (the DEFAULT for N > 1 since round 6): the users are sharded, ONE process "
                          "(rank 0) drives all N GPUs through cdae_hip_multi_* on the schedule whose accuracy bounds driver-run tests assert — "
                          "one relayed epoch on the single-GPU schedule (untimed warm-up here; 1 of an application's 50 epochs), then "
-                         "synchronous exchanged steps of 64 users per GPU folded in by the global-accumulator rule (DESIGN.md §7); the line "
+                         "synchronous exchanged steps of 64 users per GPU folded in by the global-accumulator rule (DESIGN.md §7); with --full the line "
                          "carries the single-GPU and the item-rows figure of the same node beside it in `config` (--no-side-figures skips "
                          "them).  item-rows: the GPUs cut the ITEM rows of W / b' and the "
                          "decode over them, every GPU sees every user, the user node is sharded by user; two [batch x K] all-reduces per "
@@ -176,7 +187,7 @@ def main():
                          "ranks only keep the barriers).  With --full-output it is BASELINE configs[4]'s layout (--shape cfg5_items "
                          "--num-dim 512).  users: user shards + exchange of shared-parameter deltas (one process per GPU, library-owned "
                          "RCCL): scales in throughput but is OUTSIDE the accuracy envelope (DESIGN.md §7) — a throughput figure only")
-    ap.add_argument("--no-side-figures", action="store_true", help="--layout certified: do not measure the single-GPU and item-rows figures beside the line")
+    ap.add_argument("--no-side-figures", action="store_true", help="--layout certified --full: do not measure the single-GPU and item-rows figures beside the line")
     ap.add_argument("--sync-batch-users", type=int, default=64, help="--layout certified: users per GPU and exchanged step (64 is the certified size)")
     ap.add_argument("--item-rows-devices", type=int, default=0, help="(internal: the side-figure run of --layout certified) item-rows over this many GPUs from one process")
     ap.add_argument("--users", type=int, default=0, help="--layout item-rows: generate this many users instead of the shape's own count "
@@ -394,7 +405,7 @@ def main():
               f"model.synchronize {1e6 * (t_b - t_a):.1f} us, torch.cuda.synchronize {1e6 * (t_c - t_b):.1f} us", file=sys.stderr)
     add(model.collect_stats())
     timed = dict(acc)
-    if args.profile_every:
+    if args.profile_every and args.full:
         # untimed: the other kernel families, every second batch of 32 more steps (kernel_ms_per_step; not part of `value`)
         model.set_profiling(2)
         run(args_first + args.steps, 32)
@@ -481,6 +492,9 @@ def main():
                         "whole_step": {"achieved": step_tf, "frac": step_tf / MFMA_PEAK_TFLOPS, "binding_floor_frac": floors / step_ms,
                                        "note": "frac: all three products' 6 K I flop per user over the whole step at the bf16 peak; binding_floor_frac: the sum "
                                                "of the families' binding floors / the whole step (encode, hidden layer and every launch boundary included)"}}
+            if not args.full:
+                roofline["note"] = ("the 'rows' family is timed in the untimed pass of --full only: without it its `ms` is 0, the headline record is the "
+                                    "'decode' family and `binding_floor_frac` counts floors of a family that was not timed")
         else:
             hbm_bytes = 2.0 * data.num_items * Kp * 2 + 2.0 * data.num_items * max(128.0, users_per_launch) * 2      # bf16 images of D / D^T in, G^T out and in
             roofline = {"bound": "mfma", "kernel": kernels + " (+ positive fix-up, rated-items bitmap)",
@@ -558,13 +572,14 @@ def main():
                                 else "data-parallel delta exchange (pipelined, or more than 64 users per rank and step): OUTSIDE the measured envelope "
                                      "(DESIGN.md §7 table); throughput only")},
         "roofline": roofline,
-        "kernel_ms_per_step": {k[3:]: acc[k] / max(1, acc["launches_decode"]) for k in acc if k.startswith("ms_")},
+        "kernel_ms_per_step": {k[3:]: acc[k] / max(1, acc["launches_decode"]) for k in acc if k.startswith("ms_") and (args.full or k == "ms_decode")},
         "profiled_steps": int(acc["launches_decode"]),
         "prewarm_steps": prewarm,          # untimed device pre-warm in front of the W warm-up steps (see the comment at `prewarm`)
         "cold_start_ms_per_step": cold_ms, # the process's first 20 steps (part of the pre-warm), timed on their own
-        "kernel_ms_note": "decode: HIP events inside the timed region; the other families: an untimed pass of 32 steps after it",
+        "kernel_ms_note": ("decode: HIP events inside the timed region; the other families: " +
+                           ("an untimed pass of 32 steps after it" if args.full else "not timed (--full adds an untimed pass for them)")),
     }
-    if not args.no_cpu_baseline and args.gpus == 1:          # reported at N = 1 only (rank 0's host cores)
+    if args.full and not args.no_cpu_baseline and args.gpus == 1:          # reported at N = 1 only (rank 0's host cores)
         out["cpu_baseline"] = cpu_baseline(data, cfg, args)
     model.close()
     if dist is not None:
@@ -642,9 +657,10 @@ def bench_item_rows(args, rank, world):
         dist.barrier()
     # per-kernel record (untimed pass behind the timed region): HIP events around shard 0's decode / row launches of a few batches
     prof.update(ms_decode=0.0, ms_input=0.0, launches=0)
-    model.shard_profiling(0, 1, [3, 5])
-    run(args.warmup + args.steps, min(8, args.steps))
-    model.shard_profiling(0, 0)
+    if args.full:
+        model.shard_profiling(0, 1, [3, 5])
+        run(args.warmup + args.steps, min(8, args.steps))
+        model.shard_profiling(0, 0)
     k_launches = max(1, prof["launches"])
     ms_decode0, ms_rows0 = prof["ms_decode"] / k_launches, prof["ms_input"] / k_launches
     i0, i1 = model.shards()[0]
@@ -692,6 +708,9 @@ def bench_item_rows(args, rank, world):
                                       "frac": (compulsory_decode_bytes(K, Kp, int(i1 - i0), ex_per_batch * (i1 - i0) / data.num_items, B) / (ms_decode0 * 1e-3) / 1e9 / HBM_PEAK_GBS
                                                if ms_decode0 > 0 else None),
                                       "note": "examples of shard 0 estimated as its share of the item rows (negatives are uniform over items)"}}
+    if not args.full:                    # shard 0's launches are timed in the untimed pass of --full only
+        roofline.pop("shard0_launches", None)
+        roofline.pop("shard0_decode", None)
     out = {"metric": metric,
            "value": users / elapsed, "unit": "users/s", "n_gpus": n_gpus, "steps": args.steps, "warmup": args.warmup,
            "ms_per_step": 1e3 * elapsed / args.steps, "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
@@ -752,7 +771,7 @@ def bench_certified(args, rank, world):
     n_shards = args.logical_shards or world
     devices = [0] * n_shards if (args.logical_shards or args.share_device) else list(range(world))
     side = {}
-    if not args.no_side_figures:
+    if args.full and not args.no_side_figures:
         # the same node's other two answers to "N GPUs", measured now, in their own processes, before this one holds the devices
         base = ["--shape", args.shape, "--num-dim", str(args.num_dim), "--seed", str(args.seed)]
         side["single_gpu"] = side_figure(base + ["--steps", "200", "--warmup", "40"])

@@ -40,7 +40,7 @@ def check(d, n_gpus=1):
 
 
 def test_default_line_with_cpu_baseline(built):
-    d = run_bench(["--cpu-users", "300"])
+    d = run_bench(["--full", "--cpu-users", "300"])
     check(d)
     assert d["dtype"] == "f32" and d["roofline"]["bound"] == "hbm"
     c = d["cpu_baseline"]
@@ -50,7 +50,7 @@ def test_default_line_with_cpu_baseline(built):
 def test_dump_outputs_are_what_the_timed_steps_left(built, tmp_path):
     """--dump-outputs: the parameters after the last timed step, float32 .npy.  Training is bit-deterministic
     (tests/test_gpu_parity.py::test_training_is_bit_deterministic_and_handles_reload), so the same arguments write the same arrays, also
-    without the untimed profiling pass that follows the timed steps; one more timed step writes other arrays."""
+    without the HIP events around the decode launches of the timed steps (--profile-every 0); one more timed step writes other arrays."""
     dumps = []
     for name, extra in (("a", []), ("b", ["--profile-every", "0"]), ("c", ["--steps", "7"])):
         d = run_bench(["--no-cpu-baseline", "--dump-outputs", str(tmp_path / name)] + extra)
@@ -94,10 +94,10 @@ def test_item_rows_layout_line(built):
 
 def test_certified_schedule_line_is_what_gpus_n_runs_by_default(built):
     """What `--gpus N` (N > 1) runs by default since round 6 — user shards on the relay + synchronous-exchange + global-accumulator
-    schedule, one process driving every GPU, with the single-GPU and item-rows figures of the same node beside the line — exercised on
+    schedule, one process driving every GPU, with (--full) the single-GPU and item-rows figures of the same node beside the line — exercised on
     one GPU as logical shards (the sum kernel in RCCL's place).  K timed steps are exactly K exchanged steps (cdae_hip_multi_train_steps)."""
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--shape", "small", "--steps", "20", "--warmup", "3", "--batch-users", "128",
-                          "--num-dim", "32", "--layout", "certified", "--logical-shards", "4", "--sync-batch-users", "32", "--no-cpu-baseline"],
+                          "--num-dim", "32", "--layout", "certified", "--logical-shards", "4", "--sync-batch-users", "32", "--full", "--no-cpu-baseline"],
                          cwd=ROOT, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-2000:]
     d = json.loads([l for l in out.stdout.splitlines() if l.strip()][-1])
@@ -125,3 +125,54 @@ def test_sampled_item_rows_line(built):
     assert d["scaling"] == "strong" and d["n_gpus"] == 1 and d["steps"] == 20 and d["value"] > 0 and d["dtype"] == "f32"
     assert d["roofline"]["bound"] == "hbm" and abs(d["roofline"]["frac"] - d["roofline"]["achieved"] / d["roofline"]["peak"]) < 1e-9
     assert "item-rows x4" in d["config"]["parallelism"] and "single-GPU schedule exactly" in d["config"]["accuracy"]
+
+
+FAMILIES = {"sample", "sort", "encode", "decode", "hidden", "input"}
+
+
+def test_plain_run_is_lean_and_full_leaves_the_timed_steps_alone(built, tmp_path):
+    """A plain run measures what the headline needs and nothing beside it: no CPU baseline, no untimed pass for the kernel families other
+    than the decode (whose events sit inside the timed region).  --full adds both and changes nothing the timed steps compute: the same
+    arguments dump the same arrays bit for bit either way."""
+    plain = run_bench(["--dump-outputs", str(tmp_path / "plain")])
+    full = run_bench(["--full", "--cpu-users", "300", "--dump-outputs", str(tmp_path / "full")])
+    for d in (plain, full):
+        check(d)
+        assert d["dtype"] == "f32" and d["prewarm_steps"] == 298 and d["profiled_steps"] > 0
+        assert d["kernel_ms_per_step"]["decode"] > 0 and d["roofline"]["avg_launch_ms"] > 0
+    assert "cpu_baseline" not in plain and set(plain["kernel_ms_per_step"]) == {"decode"}
+    assert full["cpu_baseline"]["value"] > 0 and set(full["kernel_ms_per_step"]) == FAMILIES
+    assert all(full["kernel_ms_per_step"][k] > 0 for k in FAMILIES)
+    assert plain["metric"] == full["metric"]
+    names = sorted(os.listdir(tmp_path / "plain"))
+    assert names == sorted(os.listdir(tmp_path / "full")) and len(names) == 8
+    for f in names:
+        assert np.array_equal(np.load(tmp_path / "plain" / f), np.load(tmp_path / "full" / f)), f
+
+
+def test_plain_certified_line_starts_no_side_runs(built):
+    """--layout certified without --full: the line of the exchanged schedule alone — no single-GPU or item-rows run in a process beside it"""
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--shape", "small", "--steps", "20", "--warmup", "3", "--batch-users", "128",
+                          "--num-dim", "32", "--layout", "certified", "--logical-shards", "4", "--sync-batch-users", "32"],
+                         cwd=ROOT, capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stderr[-2000:]
+    d = json.loads([l for l in out.stdout.splitlines() if l.strip()][-1])
+    for k, t in REQUIRED.items():
+        assert k in d, k
+    c = d["config"]
+    assert d["steps"] == 20 and d["value"] > 0 and c["batch_users"] == 32 and c["schedule"]["relay_epochs"] == 1.0
+    assert c["same_node_alternatives"] == {} and c["vs_single_gpu"] is None
+
+
+def test_plain_item_rows_line_has_no_untimed_pass(built):
+    """--layout item-rows without --full: shard 0's launches are not timed in a pass of their own; with --full they are"""
+    lines = []
+    for extra in ([], ["--full"]):
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--shape", "small", "--steps", "4", "--warmup", "1", "--batch-users", "128",
+                              "--num-dim", "32", "--logical-shards", "2"] + extra, cwd=ROOT, capture_output=True, text=True, timeout=600)
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines.append(json.loads([l for l in out.stdout.splitlines() if l.strip()][-1]))
+    plain, full = lines
+    assert plain["value"] > 0 and "shard0_decode" not in plain["roofline"]
+    assert full["value"] > 0 and full["roofline"]["shard0_decode"]["avg_launch_ms"] > 0
+    assert abs(plain["roofline"]["frac"] - plain["roofline"]["achieved"] / plain["roofline"]["peak"]) < 1e-9
