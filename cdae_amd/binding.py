@@ -30,6 +30,7 @@ P_COUNT = 14
 PLAN_FUSED_DECODE, PLAN_GEMM2_TN, PLAN_ROWS_FUSED = 1, 2, 4     # cdae_hip_full_output_plan bits (include/cdae_hip.h)
 IMF_DEFAULT_BATCH_USERS = 16   # CDAE_IMF_DEFAULT_BATCH_USERS / CDAE_BPR_DEFAULT_BATCH_USERS (include/cdae_hip.h): what an IMF / BPR handle created
 BPR_DEFAULT_BATCH_USERS = 8    # with batch_users = 0 trains on a BASELINE-sized data set (cdae_hip_mf_default_batch_users); 1 on smaller ones
+NO_USER = 0xFFFFFFFF           # CDAE_NO_USER (include/cdae_hip.h): a row of recommend_rows / eval_topn_rows without a user node
 DEFAULT_BATCH_USERS = 0        # 0 = the library's default (cdae_hip_default_batch_users: num_users / 160, within [32, 256])
 
 
@@ -92,6 +93,9 @@ EXPORTS = {
     "cdae_hip_penalty_loss": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
     "cdae_hip_recommend_all": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint32, C.c_void_p]),
     "cdae_hip_recommend_user": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p]),
+    "cdae_hip_recommend_rows": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "cdae_hip_eval_topn_rows": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
+                                          C.c_void_p, C.c_void_p, C.c_void_p]),
     "cdae_hip_set_test_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "cdae_hip_eval_topn": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "cdae_hip_stream": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
@@ -393,6 +397,44 @@ class CDAE:
         out = np.empty(topk, dtype=np.uint32)
         _chk(self.lib, self.lib.cdae_hip_recommend_user(self.h, uid, r.ctypes.data, r.size, topk, out.ctypes.data))
         return out
+
+    @staticmethod
+    def _rows(row_ptr, col, uids):
+        rp = np.ascontiguousarray(row_ptr, dtype=np.int64)
+        rc = np.ascontiguousarray(col, dtype=np.uint32)
+        if rp.ndim != 1 or rp.size < 1 or (rp.size > 1 and rc.size < rp[-1]):
+            raise ValueError("row_ptr / col are not a CSR")
+        ru = None if uids is None else np.ascontiguousarray(uids, dtype=np.uint32)
+        if ru is not None and ru.size != rp.size - 1:
+            raise ValueError("one uid per row")
+        return rp, rc, ru
+
+    def recommend_rows(self, row_ptr, col, uids=None, topk: int = 10, with_scores: bool = False):
+        """recommend(uid, topk, rated_item_set) for many caller-supplied rated sets at once (cdae_hip_recommend_rows): CSR rows
+        with ascending unique items, uids[r] the user whose private rows row r takes (NO_USER: none; None: none anywhere).
+        -> ids [n_rows, topk] uint32 (0xFFFFFFFF beyond a row's unrated items), or (ids, scores) with the fp32 scores."""
+        rp, rc, ru = self._rows(row_ptr, col, uids)
+        n = rp.size - 1
+        ids = np.empty((n, topk), dtype=np.uint32)
+        scores = np.empty((n, topk), dtype=np.float32) if with_scores else None
+        _chk(self.lib, self.lib.cdae_hip_recommend_rows(self.h, n, None if ru is None else ru.ctypes.data, rp.ctypes.data, rc.ctypes.data,
+                                                        topk, ids.ctypes.data, scores.ctypes.data if with_scores else None))
+        return (ids, scores) if with_scores else ids
+
+    def eval_topn_rows(self, row_ptr, col, target_ptr, target_col, uids=None, topk: int = 10, with_ids: bool = False):
+        """The lists of recommend_rows scored on the device against per-row target sets by the rules of eval_topn
+        (cdae_hip_eval_topn_rows): (rets[8], hits[3]) or (rets, hits, ids)."""
+        rp, rc, ru = self._rows(row_ptr, col, uids)
+        tp, tc, _ = self._rows(target_ptr, target_col, None)
+        if tp.size != rp.size:
+            raise ValueError("the target CSR covers the same rows")
+        n = rp.size - 1
+        rets, hits = np.empty(8, dtype=np.float64), np.empty(3, dtype=np.uint64)
+        ids = np.empty((n, topk), dtype=np.uint32) if with_ids else None
+        _chk(self.lib, self.lib.cdae_hip_eval_topn_rows(self.h, n, None if ru is None else ru.ctypes.data, rp.ctypes.data, rc.ctypes.data,
+                                                        tp.ctypes.data, tc.ctypes.data, topk, rets.ctypes.data, hits.ctypes.data,
+                                                        ids.ctypes.data if with_ids else None))
+        return (rets, hits, ids) if with_ids else (rets, hits)
 
     def set_test_rows(self, test_ptr, test_col):
         """the validation rows TOPN_Evaluation scores against (evaluation.hpp:118-120), CSR over this handle's users"""

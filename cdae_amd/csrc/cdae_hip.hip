@@ -209,6 +209,13 @@ struct cdae_hip {
   int64_t* d_test_ptr = nullptr; uint32_t* d_test_col = nullptr; double* d_topn_pu = nullptr; double* d_topn_out = nullptr;
   uint64_t test_users_with_rows = 0;
   bool topn_active = false;             // recommend paths: score every chunk's lists with topn_user_kernel (cdae_hip_eval_topn)
+  // cdae_hip_recommend_rows / cdae_hip_eval_topn_rows: the caller's rated sets (CSR + user of every row), target sets and per-row metric
+  // terms; grow-only (capacities in rows / items), so a steady-state call allocates nothing
+  int64_t* d_rows_ptr = nullptr; size_t rows_ptr_cap = 0; uint32_t* d_rows_uid = nullptr; size_t rows_uid_cap = 0;
+  uint32_t* d_rows_col = nullptr; size_t rows_col_cap = 0;
+  int64_t* d_rows_tptr = nullptr; size_t rows_tptr_cap = 0; double* d_rows_pu = nullptr; size_t rows_pu_cap = 0;
+  uint32_t* d_rows_tcol = nullptr; size_t rows_tcol_cap = 0;
+  double* d_rows_out = nullptr;         // [16]: the eight means, then the three hit counts
   int sort_bits = 1;
   // prep worker: the ~12 launches that sample + sort a batch are issued by a second host thread (the training loop was bound by
   // the HOST's launch rate: ~21 runtime calls x 4.5 us per batch on one thread)
@@ -454,7 +461,8 @@ template <class F> int visit_device_ptrs(cdae_hip* h, F f) {
                      h->d_Uu, h->d_Uu_ag, h->d_Ssum, h->d_delta_rows, h->d_score, h->d_Hsum, h->d_hsum_eval, h->d_iota_eval, h->d_rec_score,
                      h->d_gpos, h->d_ub, h->d_ub_ag, h->d_UVpre, h->d_rank_of, h->d_grow_ptr, h->d_gcol, h->d_gunit_ptr, h->d_gunit_user,
                      h->d_test_ptr, h->d_test_col, h->d_topn_pu, h->d_topn_out, h->d_bucket_cut, h->d_range_of,
-                     h->d_Ghot, h->d_hotdup, h->d_late_bits, h->d_cold_map);
+                     h->d_Ghot, h->d_hotdup, h->d_late_bits, h->d_cold_map,
+                     h->d_rows_ptr, h->d_rows_uid, h->d_rows_col, h->d_rows_tptr, h->d_rows_pu, h->d_rows_tcol, h->d_rows_out);
 }
 
 void free_all(cdae_hip* h) {
@@ -495,6 +503,7 @@ int free_interaction_state(cdae_hip* h) {
   h->rec_cap = 0; h->score_cap = 0; h->rec_score_cap = 0; h->hsum_eval_cap = 0;
   h->db_valid = false; h->db_rows_valid = false; h->zb_rows = 0xFFFFFFFFu;
   h->eval_cap = 0; h->eval_unit_cap = 0; h->bits_cap = 0;
+  h->rows_ptr_cap = h->rows_uid_cap = h->rows_col_cap = h->rows_tptr_cap = h->rows_pu_cap = h->rows_tcol_cap = 0;
   return 0;
 }
 
@@ -2236,9 +2245,12 @@ struct Scorer {
     HIPCHK(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
     return 0;
   }
-  // users [u0, u0 + nb) with hidden rows z; d_rated != nullptr: the caller's input set instead of the train row (one user)
-  void launch(cdae_hip* h, uint64_t u0, uint32_t nb, const float* z, const uint32_t* d_rated = nullptr, uint32_t n_rated = 0) const {
-    DISPATCH_NI(h->NI, cdae::recommend_kernel, dim3(nb), dim3(256), shmem, h->stream, h->hp, h->d_row_ptr, h->d_col, u0, z, h->dec(),
+  // users [u0, u0 + nb) with hidden rows z; d_rated != nullptr: the caller's input set instead of the train row (one user);
+  // rows_ptr != nullptr: rows [u0, u0 + nb) of that device CSR are the masks instead of the train rows (cdae_hip_recommend_rows)
+  void launch(cdae_hip* h, uint64_t u0, uint32_t nb, const float* z, const uint32_t* d_rated = nullptr, uint32_t n_rated = 0,
+              const int64_t* rows_ptr = nullptr, const uint32_t* rows_col = nullptr) const {
+    DISPATCH_NI(h->NI, cdae::recommend_kernel, dim3(nb), dim3(256), shmem, h->stream, h->hp, rows_ptr ? rows_ptr : (const int64_t*)h->d_row_ptr,
+                rows_ptr ? rows_col : (const uint32_t*)h->d_col, u0, z, h->dec(),
                 h->P(CDAE_P_BP), topk, h->d_rec, in_lds ? (float*)nullptr : h->d_score, d_rated, n_rated,
                 with_scores ? h->d_rec_score : (float*)nullptr);
   }
@@ -2283,6 +2295,31 @@ int recommend_general(cdae_hip* h, uint64_t u_begin, uint64_t u_end, uint32_t to
   }
   if (d_rated) (void)hipFree(d_rated);
   return rc;
+}
+
+// recommend(), matrix-core path (topk <= REC_TOPK_MAX, num_dim <= 256): recommend_mfma_kernel over nu hidden rows z and their bit
+// rows in h->d_bits, lists to h->d_rec.  The one place that maps num_dim to the kernel's contraction length.  d_score == nullptr:
+// the instantiations cdae_hip_recommend_all has always launched; otherwise the SCORES ones (cdae_hip_recommend_rows with out_scores).
+bool mfma_path(const cdae_hip* h, uint32_t topk) { return topk <= (uint32_t)cdae::REC_TOPK_MAX && h->K <= 256; }
+template <int NCH, bool SCORES>
+int launch_recommend_mfma_as(cdae_hip* h, const float* z, uint32_t nu, uint32_t words, uint32_t topk, float* d_score) {
+  const size_t lds = cdae::recommend_mfma_lds_bytes(NCH);
+  const dim3 grid((nu + cdae::REC_USERS_PER_BLOCK - 1) / cdae::REC_USERS_PER_BLOCK);
+  HIPCHK(hipFuncSetAttribute((const void*)cdae::recommend_mfma_kernel<NCH, SCORES>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  hipLaunchKernelGGL((cdae::recommend_mfma_kernel<NCH, SCORES>), grid, dim3(256), lds, h->stream, h->hp, z, nu, (const float*)h->dec(),
+                     (const float*)h->P(CDAE_P_BP), (const uint32_t*)h->d_bits, words, topk, h->d_rec, d_score);
+  return 0;
+}
+template <bool SCORES>
+int launch_recommend_mfma_nch(cdae_hip* h, const float* z, uint32_t nu, uint32_t words, uint32_t topk, float* d_score) {
+  if (h->K <= 32) return launch_recommend_mfma_as<4, SCORES>(h, z, nu, words, topk, d_score);
+  if (h->K <= 64) return launch_recommend_mfma_as<8, SCORES>(h, z, nu, words, topk, d_score);
+  if (h->K <= 128) return launch_recommend_mfma_as<16, SCORES>(h, z, nu, words, topk, d_score);
+  if (h->K <= 200) return launch_recommend_mfma_as<25, SCORES>(h, z, nu, words, topk, d_score);
+  return launch_recommend_mfma_as<32, SCORES>(h, z, nu, words, topk, d_score);
+}
+int launch_recommend_mfma(cdae_hip* h, const float* z, uint32_t nu, uint32_t words, uint32_t topk, float* d_score) {
+  return d_score ? launch_recommend_mfma_nch<true>(h, z, nu, words, topk, d_score) : launch_recommend_mfma_nch<false>(h, z, nu, words, topk, nullptr);
 }
 }  // namespace
 
@@ -2526,15 +2563,13 @@ int cdae_hip_recommend_all(cdae_hip_t* h, uint64_t u_begin, uint64_t u_end, uint
       std::copy(all.begin() + (size_t)h->user_inv[u] * topk, all.begin() + ((size_t)h->user_inv[u] + 1) * topk, out + (u - u_begin) * topk);
     return 0;
   }
-  if (topk <= (uint32_t)cdae::REC_TOPK_MAX && h->K <= 256) {
+  if (mfma_path(h, topk)) {
     // matrix-core path: all users of a chunk in one launch (cdae_recommend_kernels.hpp)
-    const uint32_t nch = h->K <= 32 ? 4 : (h->K <= 64 ? 8 : (h->K <= 128 ? 16 : (h->K <= 200 ? 25 : 32)));
     const uint32_t words = (uint32_t)((h->I + 31) / 32);
     const uint64_t n_all = u_end - u_begin;
     const uint32_t UC = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(n_all, 1), EVAL_CHUNK);
     CHK(ensure_cap(&h->d_bits, &h->bits_cap, (size_t)UC * words));
     CHK(ensure_cap(&h->d_rec, &h->rec_cap, (size_t)UC * topk));
-    const size_t lds = cdae::recommend_mfma_lds_bytes((int)nch);
     for (uint64_t c0 = u_begin; c0 < u_end; c0 += UC) {
       const uint32_t nu = (uint32_t)std::min<uint64_t>(UC, u_end - c0);
       if (!h->mf) CHK(ensure_eval_ws(h, nu, h->h_unit_ptr[c0 + nu] - h->h_unit_ptr[c0]));
@@ -2542,15 +2577,7 @@ int cdae_hip_recommend_all(cdae_hip_t* h, uint64_t u_begin, uint64_t u_end, uint
       const float* zsrc = h->d_zeval;
       if (h->mf) zsrc = h->d_Wu + (size_t)c0 * h->Kp;      // IMF / BPR: score = ub + ib + uv . iv (imf.hpp:117-119); ub does not rank
       else CHK(encode_chunk(h, nullptr, c0, nu, 0, CDAE_STREAM_CORRUPT, 0, 0, 0, 0, h->d_zeval, h->d_hpart_eval, h->eval_unit_cap));   // cdae.hpp:167-172, full rows
-      const dim3 grid((nu + cdae::REC_USERS_PER_BLOCK - 1) / cdae::REC_USERS_PER_BLOCK);
-#define REC_LAUNCH(NCH_)                                                                                                              \
-  do {                                                                                                                                \
-    HIPCHK(hipFuncSetAttribute((const void*)cdae::recommend_mfma_kernel<NCH_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-    hipLaunchKernelGGL(cdae::recommend_mfma_kernel<NCH_>, grid, dim3(256), lds, h->stream, h->hp, zsrc, nu, h->dec(),                 \
-                       h->P(CDAE_P_BP), h->d_bits, words, topk, h->d_rec);                                                           \
-  } while (0)
-      switch (nch) { case 4: REC_LAUNCH(4); break; case 8: REC_LAUNCH(8); break; case 16: REC_LAUNCH(16); break; case 25: REC_LAUNCH(25); break; default: REC_LAUNCH(32); break; }
-#undef REC_LAUNCH
+      CHK(launch_recommend_mfma(h, zsrc, nu, words, topk, nullptr));
       HIPCHK(hipGetLastError());
       if (h->topn_active) { topn_chunk(h, topk, c0, nu); HIPCHK(hipGetLastError()); }
       if (out) {
@@ -2642,6 +2669,146 @@ int cdae_hip_recommend_user(cdae_hip_t* h, uint64_t uid, const uint32_t* rated_i
     if (i && rated[i] == rated[i - 1]) return fail("duplicate rated item %u", rated[i]);
   }
   return recommend_general(h, uid, uid + 1, topk, out, rated.data(), (uint32_t)n_rated);
+}
+
+}  // extern "C"
+
+// ---- top-k and TOPN for caller-supplied rated sets (cdae_hip_recommend_rows, cdae_hip_eval_topn_rows) -------------------------------
+namespace {
+struct RowsArgs {
+  uint64_t n_rows; const uint32_t* uids; const int64_t* row_ptr; const uint32_t* col;
+  const int64_t* t_ptr; const uint32_t* t_col; uint64_t with_targets;      // eval_topn_rows only (t_ptr == nullptr: no scoring)
+  uint32_t topk; uint32_t* out_ids; float* out_scores;
+};
+// a host CSR over n rows: row_ptr from 0 and non-decreasing, items below I, ascending and unique inside a row
+int validate_rows_csr(const char* what, const int64_t* row_ptr, const uint32_t* col, uint64_t n, uint64_t I) {
+  if (!row_ptr) return fail("null %s row_ptr", what);
+  if (row_ptr[0] != 0) return fail("%s row_ptr[0] must be 0", what);
+  for (uint64_t r = 0; r < n; ++r)
+    if (row_ptr[r + 1] < row_ptr[r]) return fail("%s row_ptr decreases at row %llu", what, (unsigned long long)r);
+  if (row_ptr[n] > 0 && !col) return fail("null %s col with %lld items", what, (long long)row_ptr[n]);
+  for (uint64_t r = 0; r < n; ++r)
+    for (int64_t p = row_ptr[r]; p < row_ptr[r + 1]; ++p) {
+      if (col[p] >= I) return fail("%s row %llu: item %u out of range", what, (unsigned long long)r, col[p]);
+      if (p > row_ptr[r] && col[p] <= col[p - 1])
+        return fail("%s row %llu is not ascending and unique (item %u after %u)", what, (unsigned long long)r, col[p], col[p - 1]);
+    }
+  return 0;
+}
+int rows_check(cdae_hip* h, const char* fn, const RowsArgs& a) {
+  if (!h) return fail("%s: null handle", fn);
+  if (h->mf) return fail("%s does not apply to an IMF / BPR handle (its score does not depend on the rated set)", fn);
+  if (h->item_shard) return fail("%s applies to a whole model, not to an item shard", fn);
+  if (!h->d_shared) return fail("%s: cdae_hip_set_interactions first", fn);
+  if (a.topk == 0 || a.topk > h->I) return fail("%s: topk must be in [1, num_items]", fn);
+  if (a.n_rows == 0) return 0;
+  CHK(validate_rows_csr("rated", a.row_ptr, a.col, a.n_rows, h->I));
+  if (a.uids)
+    for (uint64_t r = 0; r < a.n_rows; ++r)
+      if (a.uids[r] != cdae::ROW_NO_USER && a.uids[r] >= h->U) return fail("%s: row %llu names user %u of %llu", fn, (unsigned long long)r, a.uids[r], (unsigned long long)h->U);
+  return 0;
+}
+int rows_run(cdae_hip* h, const RowsArgs& a) {
+  HIPCHK(hipSetDevice(h->device));
+  CHK(join_aux(h));
+  const uint64_t R = a.n_rows;
+  const size_t nnz = (size_t)a.row_ptr[R];
+  CHK(ensure_cap(&h->d_rows_ptr, &h->rows_ptr_cap, R + 1));
+  CHK(ensure_cap(&h->d_rows_uid, &h->rows_uid_cap, R));
+  CHK(ensure_cap(&h->d_rows_col, &h->rows_col_cap, std::max<size_t>(nnz, 1)));
+  HIPCHK(hipMemcpyAsync(h->d_rows_ptr, a.row_ptr, (R + 1) * sizeof(int64_t), hipMemcpyHostToDevice, h->stream));
+  if (nnz) HIPCHK(hipMemcpyAsync(h->d_rows_col, a.col, nnz * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
+  if (a.uids) HIPCHK(hipMemcpyAsync(h->d_rows_uid, a.uids, R * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
+  else HIPCHK(hipMemsetAsync(h->d_rows_uid, 0xFF, R * sizeof(uint32_t), h->stream));          // every row: no user node
+  if (a.t_ptr) {
+    const size_t tnnz = (size_t)a.t_ptr[R];
+    CHK(ensure_cap(&h->d_rows_tptr, &h->rows_tptr_cap, R + 1));
+    CHK(ensure_cap(&h->d_rows_pu, &h->rows_pu_cap, R, 8));
+    CHK(ensure_cap(&h->d_rows_tcol, &h->rows_tcol_cap, std::max<size_t>(tnnz, 1)));
+    if (!h->d_rows_out) CHK(dev_alloc(&h->d_rows_out, 16));
+    HIPCHK(hipMemcpyAsync(h->d_rows_tptr, a.t_ptr, (R + 1) * sizeof(int64_t), hipMemcpyHostToDevice, h->stream));
+    if (tnnz) HIPCHK(hipMemcpyAsync(h->d_rows_tcol, a.t_col, tnnz * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemsetAsync(h->d_rows_out, 0, 16 * sizeof(double), h->stream));
+  }
+  const uint32_t topk = a.topk;
+  const bool with_scores = a.out_scores != nullptr;
+  const bool mfma = mfma_path(h, topk);
+  const uint32_t empty_input = h->hp.keep_thr == 0x100000000ull ? 1u : 0u;                   // cdae.hpp:168-172 (q == 1)
+  const uint32_t words = (uint32_t)((h->I + 31) / 32);
+  Scorer sc;
+  uint32_t UC = (uint32_t)std::min<uint64_t>(R, EVAL_CHUNK);
+  if (mfma) {
+    CHK(ensure_cap(&h->d_bits, &h->bits_cap, (size_t)UC * words));
+    CHK(ensure_cap(&h->d_rec, &h->rec_cap, (size_t)UC * topk));
+    if (with_scores) CHK(ensure_cap(&h->d_rec_score, &h->rec_score_cap, (size_t)UC * topk));
+  } else {
+    CHK(sc.prepare(h, (uint32_t)std::min<uint64_t>(R, 4096u), topk, with_scores));
+    UC = sc.chunk;
+  }
+  CHK(ensure_cap(&h->d_zeval, &h->eval_cap, UC, h->Kp));
+  for (uint64_t c0 = 0; c0 < R; c0 += UC) {
+    const uint32_t nu = (uint32_t)std::min<uint64_t>(UC, R - c0);
+    // rows of at most one summation group: a wavefront each; longer ones (if the chunk has any): a workgroup each
+    bool any_long = false;
+    for (uint64_t r = c0; r < c0 + nu && !any_long && !empty_input; ++r) any_long = a.row_ptr[r + 1] - a.row_ptr[r] > (int64_t)h->hp.unit_pos;
+    DISPATCH_NI(h->NI, cdae::encode_rows_kernel, dim3((nu + cdae::ENC_ROWS_WAVES - 1) / cdae::ENC_ROWS_WAVES), dim3(cdae::ENC_ROWS_WAVES * cdae::WAVE),
+                0, h->stream, h->hp, (const int64_t*)h->d_rows_ptr, (const uint32_t*)h->d_rows_col, (const uint32_t*)h->d_rows_uid, c0, nu, empty_input,
+                (const float*)h->P(CDAE_P_W), (const float*)h->d_Wu, (const float*)h->d_Uu, (const float*)h->P(CDAE_P_B), h->d_zeval);
+    if (any_long)
+      DISPATCH_NI(h->NI, cdae::encode_rows_long_kernel, dim3(nu), dim3(cdae::ENC_ROWS_WAVES * cdae::WAVE), 0, h->stream, h->hp,
+                  (const int64_t*)h->d_rows_ptr, (const uint32_t*)h->d_rows_col, (const uint32_t*)h->d_rows_uid, c0, empty_input,
+                  (const float*)h->P(CDAE_P_W), (const float*)h->d_Wu, (const float*)h->d_Uu, (const float*)h->P(CDAE_P_B), h->d_zeval);
+    if (mfma) {
+      hipLaunchKernelGGL(cdae::rated_bits_kernel, dim3((nu + 3) / 4), dim3(256), 0, h->stream, (const int64_t*)h->d_rows_ptr,
+                         (const uint32_t*)h->d_rows_col, c0, nu, words, h->d_bits);
+      CHK(launch_recommend_mfma(h, h->d_zeval, nu, words, topk, with_scores ? h->d_rec_score : nullptr));
+    } else {
+      sc.launch(h, c0, nu, h->d_zeval, nullptr, 0, h->d_rows_ptr, h->d_rows_col);
+    }
+    HIPCHK(hipGetLastError());
+    if (a.t_ptr) {
+      hipLaunchKernelGGL(cdae::topn_user_kernel, dim3((nu + 255) / 256), dim3(256), 0, h->stream, (const uint32_t*)h->d_rec, topk, c0, nu,
+                         (const int64_t*)h->d_rows_tptr, (const uint32_t*)h->d_rows_tcol, (double)a.with_targets, h->d_rows_pu,
+                         reinterpret_cast<unsigned long long*>(h->d_rows_out + 8));
+      HIPCHK(hipGetLastError());
+    }
+    if (a.out_ids) HIPCHK(hipMemcpyAsync(a.out_ids + c0 * topk, h->d_rec, (size_t)nu * topk * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+    if (with_scores) HIPCHK(hipMemcpyAsync(a.out_scores + c0 * topk, h->d_rec_score, (size_t)nu * topk * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    if (a.out_ids || with_scores) HIPCHK(hipStreamSynchronize(h->stream));                   // one per chunk: d_rec is the next chunk's too
+  }
+  return 0;
+}
+}  // namespace
+
+extern "C" {
+
+int cdae_hip_recommend_rows(cdae_hip_t* h, uint64_t n_rows, const uint32_t* uids, const int64_t* row_ptr, const uint32_t* col,
+                            uint32_t topk, uint32_t* out_ids, float* out_scores) {
+  const RowsArgs a{n_rows, uids, row_ptr, col, nullptr, nullptr, 0, topk, out_ids, out_scores};
+  CHK(rows_check(h, "cdae_hip_recommend_rows", a));
+  if (n_rows == 0) return 0;
+  if (!out_ids) return fail("cdae_hip_recommend_rows: null out_ids");
+  return rows_run(h, a);
+}
+
+int cdae_hip_eval_topn_rows(cdae_hip_t* h, uint64_t n_rows, const uint32_t* uids, const int64_t* row_ptr, const uint32_t* col,
+                            const int64_t* target_row_ptr, const uint32_t* target_col, uint32_t topk, double* rets8, uint64_t* hits3,
+                            uint32_t* ids_out) {
+  RowsArgs a{n_rows, uids, row_ptr, col, target_row_ptr, target_col, 0, topk, ids_out, nullptr};
+  CHK(rows_check(h, "cdae_hip_eval_topn_rows", a));
+  if (!rets8) return fail("cdae_hip_eval_topn_rows: null rets8");
+  if (n_rows) CHK(validate_rows_csr("target", target_row_ptr, target_col, n_rows, h->I));
+  for (uint64_t r = 0; r < n_rows; ++r) a.with_targets += target_row_ptr[r + 1] > target_row_ptr[r];
+  if (a.with_targets == 0) return fail("cdae_hip_eval_topn_rows: no row has target items");
+  CHK(rows_run(h, a));
+  hipLaunchKernelGGL(cdae::topn_sum_kernel, dim3(1), dim3(64), 0, h->stream, (const double*)h->d_rows_pu, n_rows, h->d_rows_out);
+  HIPCHK(hipGetLastError());
+  double host[16];
+  HIPCHK(hipMemcpyAsync(host, h->d_rows_out, sizeof host, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  for (int c = 0; c < 8; ++c) rets8[c] = host[c];
+  if (hits3) std::memcpy(hits3, host + 8, 3 * sizeof(uint64_t));
+  return 0;
 }
 
 int cdae_hip_train_one_user_corruption(cdae_hip_t* h, uint64_t uid, const uint32_t* input_items, size_t n_in,

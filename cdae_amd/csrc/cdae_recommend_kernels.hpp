@@ -69,16 +69,171 @@ rated_bits_kernel(const int64_t* __restrict__ row_ptr, const uint32_t* __restric
   }
 }
 
+// ---- caller-supplied rated sets (cdae_hip_recommend_rows / cdae_hip_eval_topn_rows) ----------------------------------------------
+// z of rows [r0, r0 + gridDim.x) of a device CSR that is NOT the handle's train set: get_hidden_values(uid, rated_set) with scale 1
+// (cdae.hpp:169, :373-416), z = act(sum_{k in row} W[k] (.) Uu[uid] + b + Wu[uid]).  uids[row] names the user whose private rows the
+// row takes — any user any number of times — or ROW_NO_USER: a Wu row of zeros that is still added and a Uu row of ones, i.e. the
+// arithmetic of a real user with those rows.  empty_input: corruption_ratio == 1, the sum is over nothing (cdae.hpp:168-172).
+//
+// Summation order (part of the contract, include/cdae_hip.h): the one encode_partial_kernel + encode_finish_kernel give a train
+// row at mode 0 — groups of hp.unit_pos consecutive items, each group summed from 0 in ascending item order, the group sums added
+// from 0 in group order — so a row that equals a handle's train row has that handle's inference z bit for bit.  No unit table is
+// needed: group g of a row is items [g unit_pos, (g + 1) unit_pos).
+//
+// Two launches share the rows of a chunk by length.  encode_rows_kernel gives every row of at most one group — the rows fold-in and
+// sessions bring, 1 to some tens of items — a wavefront of its own, ENC_ROWS_WAVES rows to a workgroup, with no LDS and no barrier
+// (a W row is one 256 NI-byte wave load, UN of them in flight per wavefront).  encode_rows_long_kernel gives every longer row a
+// workgroup: its wavefronts take the groups of a round side by side, the sums meet in LDS and wavefront 0 adds them in group order
+// before the next round.  Each kernel leaves the other's rows alone; the host launches the second only for a chunk that has a long
+// row.  contract(off): h = s * uu + b must round the product as encode_finish_kernel's fmaf(s * uu, 1, b) does.
+constexpr uint32_t ROW_NO_USER = 0xFFFFFFFFu;
+constexpr int ENC_ROWS_WAVES = 4;
+
+// one wavefront: ua = sum of the W rows of items[p_begin, p_end) (at most hp.unit_pos of them), from 0 in ascending position order
+template <int NI>
+__device__ __forceinline__ void enc_rows_group_sum(const HyperParams& hp, const float* __restrict__ W, const uint32_t* __restrict__ items,
+                                                   uint32_t p_begin, uint32_t p_end, uint32_t lane, float (&ua)[NI]) {
+#pragma clang fp contract(off)
+  constexpr int UN = 8;
+  const uint32_t lo = lane * NI;
+#pragma unroll
+  for (int i = 0; i < NI; ++i) ua[i] = 0.f;
+  for (uint32_t q0 = p_begin; q0 < p_end; q0 += WAVE) {
+    const uint32_t cnt = min((uint32_t)WAVE, p_end - q0);
+    const uint32_t item = lane < cnt ? items[q0 + lane] : 0u;
+    for (uint32_t j0 = 0; j0 < cnt; j0 += UN) {
+      float v[UN][NI];
+#pragma unroll
+      for (int j = 0; j < UN; ++j) {
+        if (j0 + j < cnt) {                                        // wave-uniform
+          const uint32_t it = (uint32_t)__builtin_amdgcn_readlane((int)item, (int)(j0 + j));
+          vload<NI>(v[j], W + (size_t)it * hp.Kp + lo);
+        } else {
+#pragma unroll
+          for (int i = 0; i < NI; ++i) v[j][i] = 0.f;
+        }
+      }
+#pragma unroll
+      for (int j = 0; j < UN; ++j)
+#pragma unroll
+        for (int i = 0; i < NI; ++i) ua[i] += v[j][i];
+    }
+  }
+}
+
+// one wavefront: what the finish of a row needs — b, and the user's private rows (zeros / ones for a row without a user node)
+template <int NI>
+__device__ __forceinline__ void enc_rows_user(const HyperParams& hp, uint32_t uid, const float* __restrict__ Wu, const float* __restrict__ Uu,
+                                              const float* __restrict__ b, uint32_t lane, float (&bb)[NI], float (&wu)[NI], float (&uu)[NI]) {
+  const uint32_t lo = lane * NI;
+#pragma unroll
+  for (int i = 0; i < NI; ++i) { wu[i] = 0.f; uu[i] = 1.f; }
+  vload<NI>(bb, b + lo);
+  if (hp.user_factor && uid != ROW_NO_USER) vload<NI>(wu, Wu + (size_t)uid * hp.Kp + lo);
+  if (hp.linear_function && uid != ROW_NO_USER) vload<NI>(uu, Uu + (size_t)uid * hp.Kp + lo);
+}
+
+// one wavefront: z = act(acc (.) uu + b + wu) to zrow, pad elements 0
+template <int NI>
+__device__ __forceinline__ void enc_rows_finish(const HyperParams& hp, const float (&acc)[NI], const float (&bb)[NI], const float (&wu)[NI],
+                                                const float (&uu)[NI], uint32_t lane, float* __restrict__ zrow) {
+#pragma clang fp contract(off)
+  const uint32_t lo = lane * NI;
+  float z[NI];
+#pragma unroll
+  for (int i = 0; i < NI; ++i) {
+    float s = acc[i];
+    if (hp.linear_function) s *= uu[i];                            // h1 = Uu[u] (.) h1   cdae.hpp:382-384
+    float h = s + bb[i];
+    if (hp.user_factor) h += wu[i];
+    z[i] = lo + i < hp.K ? activate(hp, h) : 0.f;                  // pad elements of z must be 0
+  }
+  vstore<NI>(zrow + lo, z);
+}
+
+// rows of at most one group: a wavefront per row, grid = ceil(nu / ENC_ROWS_WAVES)
+template <int NI>
+__global__ void __launch_bounds__(ENC_ROWS_WAVES * WAVE)
+encode_rows_kernel(HyperParams hp, const int64_t* __restrict__ row_ptr, const uint32_t* __restrict__ col,
+                   const uint32_t* __restrict__ uids, uint64_t r0, uint32_t nu, uint32_t empty_input, const float* __restrict__ W,
+                   const float* __restrict__ Wu, const float* __restrict__ Uu, const float* __restrict__ b,
+                   float* __restrict__ Z /* [nu][Kp] */) {
+#pragma clang fp contract(off)
+  const uint32_t wid = threadIdx.x / WAVE, lane = threadIdx.x % WAVE;
+  const uint32_t slot = blockIdx.x * ENC_ROWS_WAVES + wid;
+  if (slot >= nu) return;                                          // (no barrier in this kernel)
+  const uint64_t row = r0 + slot;
+  const int64_t p0 = row_ptr[row];
+  const uint32_t n = empty_input ? 0u : (uint32_t)(row_ptr[row + 1] - p0);
+  if (n > hp.unit_pos) return;                                     // encode_rows_long_kernel's
+  float bb[NI], wu[NI], uu[NI], acc[NI], ua[NI];
+  enc_rows_user<NI>(hp, uids[row], Wu, Uu, b, lane, bb, wu, uu);  // requested before the sum
+#pragma unroll
+  for (int i = 0; i < NI; ++i) acc[i] = 0.f;
+  if (n) {
+    enc_rows_group_sum<NI>(hp, W, col + p0, 0u, n, lane, ua);
+#pragma unroll
+    for (int i = 0; i < NI; ++i) acc[i] += ua[i];                  // group 0 added to 0, as for any row
+  }
+  enc_rows_finish<NI>(hp, acc, bb, wu, uu, lane, Z + (size_t)slot * hp.Kp);
+}
+
+// rows of several groups: a workgroup per row, grid = nu (a workgroup whose row is short leaves at once)
+template <int NI>
+__global__ void __launch_bounds__(ENC_ROWS_WAVES * WAVE)
+encode_rows_long_kernel(HyperParams hp, const int64_t* __restrict__ row_ptr, const uint32_t* __restrict__ col,
+                        const uint32_t* __restrict__ uids, uint64_t r0, uint32_t empty_input, const float* __restrict__ W,
+                        const float* __restrict__ Wu, const float* __restrict__ Uu, const float* __restrict__ b,
+                        float* __restrict__ Z /* [gridDim.x][Kp] */) {
+#pragma clang fp contract(off)
+  __shared__ float part[ENC_ROWS_WAVES][64 * NI];
+  const uint32_t slot = blockIdx.x, wid = threadIdx.x / WAVE, lane = threadIdx.x % WAVE;
+  const uint64_t row = r0 + slot;
+  const int64_t p0 = row_ptr[row];
+  const uint32_t n = empty_input ? 0u : (uint32_t)(row_ptr[row + 1] - p0);
+  if (n <= hp.unit_pos) return;                                    // encode_rows_kernel's (workgroup-uniform, before any barrier)
+  const uint32_t* items = col + p0;
+  const uint32_t n_groups = (n + hp.unit_pos - 1u) / hp.unit_pos;
+  const uint32_t lo = lane * NI;
+  float bb[NI], wu[NI], uu[NI], acc[NI];
+#pragma unroll
+  for (int i = 0; i < NI; ++i) acc[i] = 0.f;
+  if (wid == 0) enc_rows_user<NI>(hp, uids[row], Wu, Uu, b, lane, bb, wu, uu);   // requested before the sums
+  for (uint32_t g0 = 0; g0 < n_groups; g0 += ENC_ROWS_WAVES) {     // (workgroup-uniform trip count)
+    const uint32_t g = g0 + wid;
+    if (g < n_groups) {
+      const uint32_t p_begin = g * hp.unit_pos;
+      float ua[NI];
+      enc_rows_group_sum<NI>(hp, W, items, p_begin, min(p_begin + hp.unit_pos, n), lane, ua);
+#pragma unroll
+      for (int i = 0; i < NI; ++i) part[wid][lo + i] = ua[i];
+    }
+    __syncthreads();
+    if (wid == 0) {
+      const uint32_t nw = min((uint32_t)ENC_ROWS_WAVES, n_groups - g0);
+      for (uint32_t w = 0; w < nw; ++w)
+#pragma unroll
+        for (int i = 0; i < NI; ++i) acc[i] += part[w][lo + i];
+    }
+    __syncthreads();
+  }
+  if (wid != 0) return;
+  enc_rows_finish<NI>(hp, acc, bb, wu, uu, lane, Z + (size_t)slot * hp.Kp);
+}
+
 constexpr size_t recommend_mfma_lds_bytes(int nch) {
   const size_t tiles = 2 * 32 * (size_t)(8 * nch + 4) * sizeof(float), merge = 2 * 4 * 64 * (size_t)REC_TOPK_MAX * sizeof(float);
   return tiles > merge ? tiles : merge;
 }
 
-template <int NCH>
+// SCORES (cdae_hip_recommend_rows with out_scores): the merge also writes the fp32 score of every listed item to out_score
+// [nu x topk], -INFINITY in the sentinel places; the instantiations without it are the code cdae_hip_recommend_all has always launched.
+template <int NCH, bool SCORES = false>
 __global__ void __launch_bounds__(256)
 recommend_mfma_kernel(HyperParams hp, const float* __restrict__ Z /* [nu x Kp] */, uint32_t nu,
                       const float* __restrict__ D, const float* __restrict__ bp,
-                      const uint32_t* __restrict__ bits, uint32_t words, uint32_t topk, uint32_t* __restrict__ out) {
+                      const uint32_t* __restrict__ bits, uint32_t words, uint32_t topk, uint32_t* __restrict__ out,
+                      float* __restrict__ out_score = nullptr) {
   constexpr int KC = 8 * NCH;                     // contraction length (>= K; pad columns are zero in Z and D)
   constexpr int ROW = KC + 4;                     // LDS row stride in floats
   constexpr int TILE = 32;
@@ -193,6 +348,7 @@ recommend_mfma_kernel(HyperParams hp, const float* __restrict__ Z /* [nu x Kp] *
       const uint32_t xa = pa < (uint32_t)REC_TOPK_MAX ? ia[pa] : 0xFFFFFFFFu, xb = pb < (uint32_t)REC_TOPK_MAX ? ib[pb] : 0xFFFFFFFFu;
       const bool take_a = a > b || (a == b && xa <= xb);
       out[(size_t)user * topk + j] = take_a ? xa : xb;
+      if constexpr (SCORES) out_score[(size_t)user * topk + j] = take_a ? a : b;
       if (take_a) ++pa; else ++pb;
     }
   }

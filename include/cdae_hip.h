@@ -23,6 +23,8 @@
  *   CDAE::data_loss                      cdae.hpp:78-101     cdae_hip_data_loss
  *   CDAE::penalty_loss                   cdae.hpp:103-107    cdae_hip_penalty_loss
  *   CDAE::recommend (all users, top-k)   cdae.hpp:162-196    cdae_hip_recommend_all
+ *   CDAE::recommend (any rated sets)     cdae.hpp:162-196    cdae_hip_recommend_rows, cdae_hip_eval_topn_rows (batched),
+ *                                                            cdae_hip_recommend_user (one user)
  *   TOPN_Evaluation::evaluate            evaluation.hpp:113-181, evaluate_rec_list :183-219
  *                                                            cdae_hip_set_test_rows + cdae_hip_eval_topn
  *   (data-parallel exchange; no reference counterpart)       cdae_hip_delta_*, cdae_hip_comm_*, cdae_hip_exchange_*,
@@ -62,7 +64,9 @@ extern "C" {
  *     (relay warm-up epochs on the single-GPU schedule, users per shard of the exchanged steps, combine rule); the drop-in IMF / BPR
  *     classes pass batch_users = 1 (the reference loop) unless CDAE_BATCH_USERS says otherwise
  * 12: cdae_hip_decode_plan, cdae_hip_set_decode_fused (which launches the sampled decode + hidden-gradient step of a handle is made of);
- *     cdae_hip_multi_steps_per_epoch, cdae_hip_multi_train_steps (a range of the exchanged steps of an epoch: what bench.py times) */
+ *     cdae_hip_multi_steps_per_epoch, cdae_hip_multi_train_steps (a range of the exchanged steps of an epoch: what bench.py times)
+ *     added under 12 (no existing entry point or structure changed): cdae_hip_recommend_rows, cdae_hip_eval_topn_rows, CDAE_NO_USER —
+ *     batched top-k and TOPN for rated sets the caller supplies */
 #define CDAE_HIP_ABI_VERSION 12
 
 /* numeric values follow libcf::LossType (/root/reference/src/model/loss.hpp:10-18) */
@@ -293,6 +297,40 @@ int cdae_hip_eval_topn(cdae_hip_t* h, uint32_t topk, double* rets8, uint64_t* hi
  * Items need not be sorted; duplicates are an error.  out is [topk] uint32 on the host. */
 int cdae_hip_recommend_user(cdae_hip_t* h, uint64_t uid, const uint32_t* rated_items, size_t n_rated, uint32_t topk,
                             uint32_t* out);
+
+/* recommend(uid, topk, rated_item_set) for MANY rated sets at once, none of which has to be a train row: the test-phase protocol
+ * (rated = train + validation), fold-in of held-out users, serving of sessions that changed since training.
+ *   rows     row_ptr[n_rows + 1] / col: a host CSR of rated sets, items ascending and unique inside a row (validated: an unsorted,
+ *            duplicate or out-of-range item is an error that names the row); a row may be empty.  cdae_hip_recommend_rows with n_rows == 0 succeeds and touches nothing
+ *            (cdae_hip_eval_topn_rows with n_rows == 0 has no row with targets: its error below).
+ *   uids     uids[r] = the local user whose Wu row (and Uu row under linear_function) row r takes; any user any number of times.
+ *            CDAE_NO_USER: the row has no user node — a Wu row of zeros that is still added and a Uu row of ones, i.e. the arithmetic
+ *            of a real user with those rows.  uids == NULL: every row is CDAE_NO_USER.  Any other id >= num_users is an error.
+ *   hidden   get_hidden_values(uid, rated_set) with scale 1 (cdae.hpp:169, :373-416): z = act(sum_{k in row} W[k] (.) Uu[uid] + b + Wu[uid]);
+ *            corruption_ratio == 1 encodes the empty input (:168-172) and still excludes the row.
+ *   order    of the input sum (part of the contract): the one cdae_hip_encode(mode 0) takes for a train row — groups of `unit`
+ *            consecutive items (the handle's work-unit size: unit = 64 when min(batch_users, num_users) <= 1024, else 128 — so a handle
+ *            with batch_users > 1024 but at most 1024 users sums in groups of 64), each group summed from 0 in ascending item order, the group sums added from 0 in group order.  A row equal to a handle's train row therefore has that
+ *            handle's inference z, and its list, bit for bit.
+ *   ranking  exactly cdae_hip_recommend_all's: descending score, equal scores by ascending item id, the row's own items never
+ *            returned, 0xFFFFFFFF in the surplus places of a row with fewer than topk items left (cdae_hip_recommend_user refuses such
+ *            a set; one short row must not fail a batch).  topk in [1, num_items]; num_dim <= 256 and topk <= 16 run on the matrix
+ *            cores, anything else on the general path.
+ *   out      out_ids [n_rows x topk]; out_scores NULL or [n_rows x topk]: the fp32 score the path computed for every listed item,
+ *            -INFINITY in the sentinel places.
+ * cdae_hip_eval_topn_rows scores those lists on the device against per-row target sets (a second CSR over the same n_rows, items
+ * ascending and unique, empty rows allowed) by the rules of cdae_hip_eval_topn: rets8 = the eight means over the rows WITH targets,
+ * added in row order; hits3 (may be NULL) = integer hits in the first 1 / 5 / 10 places; ids_out (may be NULL) = the lists.  No row
+ * with targets is an error.
+ * Refused: IMF / BPR handles (the score does not depend on the rated set), item shards, calls before cdae_hip_set_interactions.
+ * The caller's arrays are copied into grow-only device buffers of the handle (freed with it): a steady-state call allocates nothing.
+ * Rows are taken in chunks (at most 32 768 per launch group) with one host synchronisation per chunk that returns results. */
+#define CDAE_NO_USER 0xFFFFFFFFu
+int cdae_hip_recommend_rows(cdae_hip_t* h, uint64_t n_rows, const uint32_t* uids, const int64_t* row_ptr, const uint32_t* col,
+                            uint32_t topk, uint32_t* out_ids, float* out_scores);
+int cdae_hip_eval_topn_rows(cdae_hip_t* h, uint64_t n_rows, const uint32_t* uids, const int64_t* row_ptr, const uint32_t* col,
+                            const int64_t* target_row_ptr, const uint32_t* target_col, uint32_t topk, double* rets8, uint64_t* hits3,
+                            uint32_t* ids_out);
 
 /* ---- data-parallel exchange (north star: RCCL all-reduce of the shared W / W' / bias gradients;
  * Wu never leaves its GPU).  Each rank trains its own users from a common snapshot, then

@@ -148,6 +148,36 @@ int main(int argc, char* argv[]) {
     CHECK_EQ(rec.size(), size_t(10));
     for (size_t iid : rec) CHECK(!fewer.count(iid)) << "a rated item was recommended";
     LOG(INFO) << "explicit rated set OK (dropped item " << dropped << ")";
+    // recommend_rows(): many rated sets in one device call.  Every user's train row, handed over in hashtable order (the method
+    // sorts it), must give that user's row of the precomputed table; then a foreign set, a set without a user node and a set that
+    // leaves three items, whose list is cut at the first sentinel.
+    const size_t num_items = train.feature_group_total_dimension(1);
+    std::vector<size_t> row_uids;
+    std::vector<std::vector<size_t>> sets;
+    for (auto& ur : train_sets) {
+      row_uids.push_back(ur.first);
+      sets.emplace_back();
+      for (auto& p : ur.second) sets.back().push_back(p.first);
+    }
+    const size_t n_train_rows = sets.size();
+    std::vector<size_t> fewer_items, all_but_three;
+    for (auto& p : fewer) fewer_items.push_back(p.first);
+    for (size_t i = 3; i < num_items; ++i) all_but_three.push_back(num_items - 1 - (i - 3));       // descending: not sorted
+    row_uids.push_back(uid); sets.push_back(fewer_items);
+    row_uids.push_back(CDAE::kNoUser); sets.push_back(fewer_items);
+    row_uids.push_back(uid); sets.push_back(all_but_three);
+    const std::vector<std::vector<size_t>> lists = trained->recommend_rows(row_uids, sets, 10);
+    CHECK_EQ(lists.size(), n_train_rows + 3);
+    for (size_t r = 0; r < n_train_rows; ++r)
+      CHECK(lists[r] == trained->recommend_train_row(row_uids[r], 10)) << "recommend_rows differs from the table for user " << row_uids[r];
+    for (size_t r = n_train_rows; r < n_train_rows + 2; ++r) {
+      CHECK_EQ(lists[r].size(), size_t(10));
+      for (size_t iid : lists[r]) CHECK(!fewer.count(iid)) << "a rated item was recommended";
+    }
+    std::vector<size_t> left = lists[n_train_rows + 2];
+    std::sort(left.begin(), left.end());
+    CHECK(left == std::vector<size_t>({0, 1, 2})) << "a set that leaves three items must give exactly those, cut at the sentinel";
+    LOG(INFO) << "recommend_rows OK (" << lists.size() << " rows)";
   }
   LOG(INFO) << "host layer OK";
   return 0;

@@ -256,6 +256,39 @@ class CDAE : public RecsysModelBase {
     return std::vector<size_t>(ids.begin(), ids.end());
   }
 
+  // recommend(uid, topk, rated_item_set) for many rated sets in ONE device call (cdae_hip_recommend_rows): rated_sets[r] is the set
+  // row r is encoded from and excludes, uids[r] the user whose user node it takes — any user any number of times, kNoUser for a
+  // set without one (a user the model has never seen).  The test-phase protocol (train + validation rows), fold-in of held-out
+  // users, changed sessions.  Lists as recommend() returns them, except that a set which leaves fewer than topk items gets a
+  // shorter list.  Single-handle models only; serialised on the handle's mutex like recommend().
+  enum : size_t { kNoUser = static_cast<size_t>(-1) };          // (an enumerator: usable by reference before C++17 without a definition)
+  std::vector<std::vector<size_t>> recommend_rows(const std::vector<size_t>& uids, const std::vector<std::vector<size_t>>& rated_sets,
+                                                  size_t topk) const {
+    CHECK_EQ(uids.size(), rated_sets.size());
+    CHECK(!multi_) << "recommend_rows() is provided for a model on one device";
+    const size_t n = rated_sets.size();
+    std::vector<uint32_t> u(n), col;
+    std::vector<int64_t> ptr(n + 1, 0);
+    for (size_t r = 0; r < n; ++r) {
+      if (uids[r] != kNoUser) CHECK_LT(uids[r], num_users_);
+      u[r] = uids[r] == kNoUser ? CDAE_NO_USER : static_cast<uint32_t>(uids[r]);
+      const size_t at = col.size();
+      for (size_t i : rated_sets[r]) { CHECK_LT(i, num_items_); col.push_back(static_cast<uint32_t>(i)); }
+      std::sort(col.begin() + at, col.end());                    // the device CSR is ascending inside a row (duplicates: its error)
+      ptr[r + 1] = static_cast<int64_t>(col.size());
+    }
+    std::vector<uint32_t> ids(n * topk);
+    {
+      std::lock_guard<std::mutex> lk(*mu_);
+      CHECK(ready()) << "reset() must be called first";
+      CDAE_HIP_CHECK(cdae_hip_recommend_rows(dev_.get(), n, u.data(), ptr.data(), col.data(), static_cast<uint32_t>(topk), ids.data(), nullptr));
+    }
+    std::vector<std::vector<size_t>> out(n);
+    for (size_t r = 0; r < n; ++r)
+      for (size_t i = 0; i < topk && ids[r * topk + i] != 0xFFFFFFFFu; ++i) out[r].push_back(ids[r * topk + i]);
+    return out;
+  }
+
   // recommend() for the user's own train row — what Evaluation asks for — without the caller building a hashtable
   // per user per epoch (evaluation.hpp:118-123): TOPN_Evaluation detects this method and uses it.
   std::vector<size_t> recommend_train_row(size_t uid, size_t topk) const {
