@@ -30,6 +30,7 @@ P_COUNT = 14
 PLAN_FUSED_DECODE, PLAN_GEMM2_TN, PLAN_ROWS_FUSED = 1, 2, 4     # cdae_hip_full_output_plan bits (include/cdae_hip.h)
 IMF_DEFAULT_BATCH_USERS = 16   # CDAE_IMF_DEFAULT_BATCH_USERS / CDAE_BPR_DEFAULT_BATCH_USERS (include/cdae_hip.h): what an IMF / BPR handle created
 BPR_DEFAULT_BATCH_USERS = 8    # with batch_users = 0 trains on a BASELINE-sized data set (cdae_hip_mf_default_batch_users); 1 on smaller ones
+RANK_CANDIDATES_MAX = 4096     # CDAE_RANK_CANDIDATES_MAX (include/cdae_hip.h): candidates per row that score_rows ranks
 NO_USER = 0xFFFFFFFF           # CDAE_NO_USER (include/cdae_hip.h): a row of recommend_rows / eval_topn_rows without a user node
 DEFAULT_BATCH_USERS = 0        # 0 = the library's default (cdae_hip_default_batch_users: num_users / 160, within [32, 256])
 
@@ -94,6 +95,7 @@ EXPORTS = {
     "cdae_hip_recommend_all": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint32, C.c_void_p]),
     "cdae_hip_recommend_user": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p]),
     "cdae_hip_recommend_rows": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "cdae_hip_score_rows": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "cdae_hip_eval_topn_rows": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
                                           C.c_void_p, C.c_void_p, C.c_void_p]),
     "cdae_hip_set_test_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -435,6 +437,23 @@ class CDAE:
                                                         tp.ctypes.data, tc.ctypes.data, topk, rets.ctypes.data, hits.ctypes.data,
                                                         ids.ctypes.data if with_ids else None))
         return (rets, hits, ids) if with_ids else (rets, hits)
+
+    def score_rows(self, row_ptr, col, cand_ptr, cand_col, uids=None, with_ranks: bool = False):
+        """get_output_values for many rows at once (cdae_hip_score_rows): the fp32 scores of the candidates a second CSR over the
+        same rows names (ascending unique items; a row's own rated items allowed), in CSR order -> scores float32 [nnz_cand], or
+        (scores, ranks uint32 [nnz_cand]): a candidate's place among its row's candidates in recommend_all's order, 0 the best
+        (rows of at most RANK_CANDIDATES_MAX candidates)."""
+        rp, rc, ru = self._rows(row_ptr, col, uids)
+        cp, cc, _ = self._rows(cand_ptr, cand_col, None)
+        if cp.size != rp.size:
+            raise ValueError("the candidate CSR covers the same rows")
+        n = rp.size - 1
+        total = max(int(cp[-1]), 0) if n else 0
+        scores = np.empty(total, dtype=np.float32)
+        ranks = np.empty(total, dtype=np.uint32) if with_ranks else None
+        _chk(self.lib, self.lib.cdae_hip_score_rows(self.h, n, None if ru is None else ru.ctypes.data, rp.ctypes.data, rc.ctypes.data,
+                                                    cp.ctypes.data, cc.ctypes.data, scores.ctypes.data, ranks.ctypes.data if with_ranks else None))
+        return (scores, ranks) if with_ranks else scores
 
     def set_test_rows(self, test_ptr, test_col):
         """the validation rows TOPN_Evaluation scores against (evaluation.hpp:118-120), CSR over this handle's users"""

@@ -216,6 +216,11 @@ struct cdae_hip {
   int64_t* d_rows_tptr = nullptr; size_t rows_tptr_cap = 0; double* d_rows_pu = nullptr; size_t rows_pu_cap = 0;
   uint32_t* d_rows_tcol = nullptr; size_t rows_tcol_cap = 0;
   double* d_rows_out = nullptr;         // [16]: the eight means, then the three hit counts
+  // cdae_hip_score_rows: the candidate CSR, the tile table of the call, the scores and ranks of one chunk (grow-only, freed with the handle)
+  int64_t* d_cand_ptr = nullptr; size_t cand_ptr_cap = 0; uint32_t* d_cand_col = nullptr; size_t cand_col_cap = 0;
+  uint2* d_cand_tiles = nullptr; size_t cand_tiles_cap = 0;
+  float* d_cand_score = nullptr; size_t cand_score_cap = 0; uint32_t* d_cand_rank = nullptr; size_t cand_rank_cap = 0;
+  std::vector<uint2> h_cand_tiles;      // host image of the tile table: alive until the call's last synchronisation
   int sort_bits = 1;
   // prep worker: the ~12 launches that sample + sort a batch are issued by a second host thread (the training loop was bound by
   // the HOST's launch rate: ~21 runtime calls x 4.5 us per batch on one thread)
@@ -462,7 +467,8 @@ template <class F> int visit_device_ptrs(cdae_hip* h, F f) {
                      h->d_gpos, h->d_ub, h->d_ub_ag, h->d_UVpre, h->d_rank_of, h->d_grow_ptr, h->d_gcol, h->d_gunit_ptr, h->d_gunit_user,
                      h->d_test_ptr, h->d_test_col, h->d_topn_pu, h->d_topn_out, h->d_bucket_cut, h->d_range_of,
                      h->d_Ghot, h->d_hotdup, h->d_late_bits, h->d_cold_map,
-                     h->d_rows_ptr, h->d_rows_uid, h->d_rows_col, h->d_rows_tptr, h->d_rows_pu, h->d_rows_tcol, h->d_rows_out);
+                     h->d_rows_ptr, h->d_rows_uid, h->d_rows_col, h->d_rows_tptr, h->d_rows_pu, h->d_rows_tcol, h->d_rows_out,
+                     h->d_cand_ptr, h->d_cand_col, h->d_cand_tiles, h->d_cand_score, h->d_cand_rank);
 }
 
 void free_all(cdae_hip* h) {
@@ -504,6 +510,7 @@ int free_interaction_state(cdae_hip* h) {
   h->db_valid = false; h->db_rows_valid = false; h->zb_rows = 0xFFFFFFFFu;
   h->eval_cap = 0; h->eval_unit_cap = 0; h->bits_cap = 0;
   h->rows_ptr_cap = h->rows_uid_cap = h->rows_col_cap = h->rows_tptr_cap = h->rows_pu_cap = h->rows_tcol_cap = 0;
+  h->cand_ptr_cap = h->cand_col_cap = h->cand_tiles_cap = h->cand_score_cap = h->cand_rank_cap = 0;
   return 0;
 }
 
@@ -2708,18 +2715,39 @@ int rows_check(cdae_hip* h, const char* fn, const RowsArgs& a) {
       if (a.uids[r] != cdae::ROW_NO_USER && a.uids[r] >= h->U) return fail("%s: row %llu names user %u of %llu", fn, (unsigned long long)r, a.uids[r], (unsigned long long)h->U);
   return 0;
 }
+// the part every rows entry point shares: the rated-set CSR and the uids to the handle's grow-only buffers (on h->stream) ...
+int rows_upload(cdae_hip* h, uint64_t R, const uint32_t* uids, const int64_t* row_ptr, const uint32_t* col) {
+  const size_t nnz = (size_t)row_ptr[R];
+  CHK(ensure_cap(&h->d_rows_ptr, &h->rows_ptr_cap, R + 1));
+  CHK(ensure_cap(&h->d_rows_uid, &h->rows_uid_cap, R));
+  CHK(ensure_cap(&h->d_rows_col, &h->rows_col_cap, std::max<size_t>(nnz, 1)));
+  HIPCHK(hipMemcpyAsync(h->d_rows_ptr, row_ptr, (R + 1) * sizeof(int64_t), hipMemcpyHostToDevice, h->stream));
+  if (nnz) HIPCHK(hipMemcpyAsync(h->d_rows_col, col, nnz * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
+  if (uids) HIPCHK(hipMemcpyAsync(h->d_rows_uid, uids, R * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
+  else HIPCHK(hipMemsetAsync(h->d_rows_uid, 0xFF, R * sizeof(uint32_t), h->stream));          // every row: no user node
+  return 0;
+}
+inline uint32_t rows_empty_input(const cdae_hip* h) { return h->hp.keep_thr == 0x100000000ull ? 1u : 0u; }   // cdae.hpp:168-172 (q == 1)
+// ... and z of rows [c0, c0 + nu) of that CSR to h->d_zeval (nu rows of Kp floats, allocated by the caller)
+int rows_encode_chunk(cdae_hip* h, const int64_t* row_ptr, uint64_t c0, uint32_t nu) {
+  const uint32_t empty_input = rows_empty_input(h);
+  // rows of at most one summation group: a wavefront each; longer ones (if the chunk has any): a workgroup each
+  bool any_long = false;
+  for (uint64_t r = c0; r < c0 + nu && !any_long && !empty_input; ++r) any_long = row_ptr[r + 1] - row_ptr[r] > (int64_t)h->hp.unit_pos;
+  DISPATCH_NI(h->NI, cdae::encode_rows_kernel, dim3((nu + cdae::ENC_ROWS_WAVES - 1) / cdae::ENC_ROWS_WAVES), dim3(cdae::ENC_ROWS_WAVES * cdae::WAVE),
+              0, h->stream, h->hp, (const int64_t*)h->d_rows_ptr, (const uint32_t*)h->d_rows_col, (const uint32_t*)h->d_rows_uid, c0, nu, empty_input,
+              (const float*)h->P(CDAE_P_W), (const float*)h->d_Wu, (const float*)h->d_Uu, (const float*)h->P(CDAE_P_B), h->d_zeval);
+  if (any_long)
+    DISPATCH_NI(h->NI, cdae::encode_rows_long_kernel, dim3(nu), dim3(cdae::ENC_ROWS_WAVES * cdae::WAVE), 0, h->stream, h->hp,
+                (const int64_t*)h->d_rows_ptr, (const uint32_t*)h->d_rows_col, (const uint32_t*)h->d_rows_uid, c0, empty_input,
+                (const float*)h->P(CDAE_P_W), (const float*)h->d_Wu, (const float*)h->d_Uu, (const float*)h->P(CDAE_P_B), h->d_zeval);
+  return 0;
+}
 int rows_run(cdae_hip* h, const RowsArgs& a) {
   HIPCHK(hipSetDevice(h->device));
   CHK(join_aux(h));
   const uint64_t R = a.n_rows;
-  const size_t nnz = (size_t)a.row_ptr[R];
-  CHK(ensure_cap(&h->d_rows_ptr, &h->rows_ptr_cap, R + 1));
-  CHK(ensure_cap(&h->d_rows_uid, &h->rows_uid_cap, R));
-  CHK(ensure_cap(&h->d_rows_col, &h->rows_col_cap, std::max<size_t>(nnz, 1)));
-  HIPCHK(hipMemcpyAsync(h->d_rows_ptr, a.row_ptr, (R + 1) * sizeof(int64_t), hipMemcpyHostToDevice, h->stream));
-  if (nnz) HIPCHK(hipMemcpyAsync(h->d_rows_col, a.col, nnz * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
-  if (a.uids) HIPCHK(hipMemcpyAsync(h->d_rows_uid, a.uids, R * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
-  else HIPCHK(hipMemsetAsync(h->d_rows_uid, 0xFF, R * sizeof(uint32_t), h->stream));          // every row: no user node
+  CHK(rows_upload(h, R, a.uids, a.row_ptr, a.col));
   if (a.t_ptr) {
     const size_t tnnz = (size_t)a.t_ptr[R];
     CHK(ensure_cap(&h->d_rows_tptr, &h->rows_tptr_cap, R + 1));
@@ -2733,7 +2761,6 @@ int rows_run(cdae_hip* h, const RowsArgs& a) {
   const uint32_t topk = a.topk;
   const bool with_scores = a.out_scores != nullptr;
   const bool mfma = mfma_path(h, topk);
-  const uint32_t empty_input = h->hp.keep_thr == 0x100000000ull ? 1u : 0u;                   // cdae.hpp:168-172 (q == 1)
   const uint32_t words = (uint32_t)((h->I + 31) / 32);
   Scorer sc;
   uint32_t UC = (uint32_t)std::min<uint64_t>(R, EVAL_CHUNK);
@@ -2748,16 +2775,7 @@ int rows_run(cdae_hip* h, const RowsArgs& a) {
   CHK(ensure_cap(&h->d_zeval, &h->eval_cap, UC, h->Kp));
   for (uint64_t c0 = 0; c0 < R; c0 += UC) {
     const uint32_t nu = (uint32_t)std::min<uint64_t>(UC, R - c0);
-    // rows of at most one summation group: a wavefront each; longer ones (if the chunk has any): a workgroup each
-    bool any_long = false;
-    for (uint64_t r = c0; r < c0 + nu && !any_long && !empty_input; ++r) any_long = a.row_ptr[r + 1] - a.row_ptr[r] > (int64_t)h->hp.unit_pos;
-    DISPATCH_NI(h->NI, cdae::encode_rows_kernel, dim3((nu + cdae::ENC_ROWS_WAVES - 1) / cdae::ENC_ROWS_WAVES), dim3(cdae::ENC_ROWS_WAVES * cdae::WAVE),
-                0, h->stream, h->hp, (const int64_t*)h->d_rows_ptr, (const uint32_t*)h->d_rows_col, (const uint32_t*)h->d_rows_uid, c0, nu, empty_input,
-                (const float*)h->P(CDAE_P_W), (const float*)h->d_Wu, (const float*)h->d_Uu, (const float*)h->P(CDAE_P_B), h->d_zeval);
-    if (any_long)
-      DISPATCH_NI(h->NI, cdae::encode_rows_long_kernel, dim3(nu), dim3(cdae::ENC_ROWS_WAVES * cdae::WAVE), 0, h->stream, h->hp,
-                  (const int64_t*)h->d_rows_ptr, (const uint32_t*)h->d_rows_col, (const uint32_t*)h->d_rows_uid, c0, empty_input,
-                  (const float*)h->P(CDAE_P_W), (const float*)h->d_Wu, (const float*)h->d_Uu, (const float*)h->P(CDAE_P_B), h->d_zeval);
+    CHK(rows_encode_chunk(h, a.row_ptr, c0, nu));
     if (mfma) {
       hipLaunchKernelGGL(cdae::rated_bits_kernel, dim3((nu + 3) / 4), dim3(256), 0, h->stream, (const int64_t*)h->d_rows_ptr,
                          (const uint32_t*)h->d_rows_col, c0, nu, words, h->d_bits);
@@ -2778,9 +2796,102 @@ int rows_run(cdae_hip* h, const RowsArgs& a) {
   }
   return 0;
 }
+
+// ---- scores and ranks of caller-supplied candidates (cdae_hip_score_rows) ------------------------------------------------------------
+// Candidates per chunk: a chunk takes whole candidate rows while they fit; a row of more candidates than this (scores only: ranks stop
+// at CDAE_RANK_CANDIDATES_MAX) is cut into chunks of exactly this many, so a row of num_items candidates fits whatever num_items is.
+constexpr int64_t SCORE_CAND_CHUNK = 65536;
+static_assert(SCORE_CAND_CHUNK % cdae::SCORE_TILE == 0 && SCORE_CAND_CHUNK >= CDAE_RANK_CANDIDATES_MAX, "a ranked row lies inside one chunk");
+static_assert(cdae::RANK_CANDIDATES_MAX == CDAE_RANK_CANDIDATES_MAX, "rank_rows_kernel's LDS row");
+static_assert(EVAL_CHUNK <= 65536, "a tile names its row's slot in 16 bits");
+struct ScoreChunk {
+  uint64_t c0; uint32_t nu; bool encode;        // the rows whose z the chunk reads: [c0, c0 + nu), encoded by the first chunk over them
+  int64_t p0, p1;                               // its candidates: positions [p0, p1) of the candidate CSR
+  size_t t0, t1;                                // its tiles in the call's tile table
+  uint64_t ra, rb;                              // the rows that have candidates in it (ranks: each of them wholly)
+};
+// Host side of the tile map: one walk over the candidate CSR (validated before) cuts the call into chunks and the chunks into tiles.
+void score_plan(uint64_t R, const int64_t* cp, std::vector<uint2>& tiles, std::vector<ScoreChunk>& chunks) {
+  tiles.clear(); chunks.clear();
+  for (uint64_t c0 = 0; c0 < R; c0 += EVAL_CHUNK) {
+    const uint32_t nu = (uint32_t)std::min<uint64_t>(EVAL_CHUNK, R - c0);
+    bool first = true;
+    int64_t pb = cp[c0]; size_t tb = tiles.size(); uint64_t ra = c0;          // the open chunk
+    auto close = [&](int64_t pe, uint64_t rb) {
+      if (pe > pb) { chunks.push_back(ScoreChunk{c0, nu, first, pb, pe, tb, tiles.size(), ra, rb}); first = false; }
+      pb = pe; tb = tiles.size(); ra = rb;
+    };
+    for (uint64_t r = c0; r < c0 + nu; ++r) {
+      int64_t q = cp[r];
+      const int64_t qe = cp[r + 1];
+      while (q < qe) {
+        const int64_t room = SCORE_CAND_CHUNK - (q - pb);
+        if (qe - q > room && q > pb) { close(q, q == cp[r] ? r : r + 1); if (q != cp[r]) ra = r; continue; }   // does not fit: the open chunk ends here
+        const int64_t take = std::min(qe - q, SCORE_CAND_CHUNK);
+        for (int64_t t = q; t < q + take; t += cdae::SCORE_TILE) {
+          const uint32_t cnt = (uint32_t)std::min<int64_t>(cdae::SCORE_TILE, q + take - t);
+          tiles.push_back(make_uint2((uint32_t)(r - c0) | (cnt - 1u) << 16, (uint32_t)(t - pb)));
+        }
+        q += take;
+      }
+    }
+    close(cp[c0 + nu], c0 + nu);
+  }
+}
+int score_run(cdae_hip* h, uint64_t R, const uint32_t* uids, const int64_t* row_ptr, const uint32_t* col, const int64_t* cp,
+              const uint32_t* cc, float* out_scores, uint32_t* out_ranks) {
+  HIPCHK(hipSetDevice(h->device));
+  CHK(join_aux(h));
+  CHK(rows_upload(h, R, uids, row_ptr, col));
+  const size_t total = (size_t)cp[R];
+  std::vector<ScoreChunk> chunks;
+  score_plan(R, cp, h->h_cand_tiles, chunks);
+  const size_t per_chunk = std::min<size_t>(total, (size_t)SCORE_CAND_CHUNK);
+  CHK(ensure_cap(&h->d_cand_ptr, &h->cand_ptr_cap, R + 1));
+  CHK(ensure_cap(&h->d_cand_col, &h->cand_col_cap, total));
+  CHK(ensure_cap(&h->d_cand_tiles, &h->cand_tiles_cap, h->h_cand_tiles.size()));
+  CHK(ensure_cap(&h->d_cand_score, &h->cand_score_cap, per_chunk));
+  if (out_ranks) CHK(ensure_cap(&h->d_cand_rank, &h->cand_rank_cap, per_chunk));
+  CHK(ensure_cap(&h->d_zeval, &h->eval_cap, (size_t)std::min<uint64_t>(R, EVAL_CHUNK), h->Kp));
+  HIPCHK(hipMemcpyAsync(h->d_cand_ptr, cp, (R + 1) * sizeof(int64_t), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(hipMemcpyAsync(h->d_cand_col, cc, total * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(hipMemcpyAsync(h->d_cand_tiles, h->h_cand_tiles.data(), h->h_cand_tiles.size() * sizeof(uint2), hipMemcpyHostToDevice, h->stream));
+  for (const ScoreChunk& c : chunks) {
+    if (c.encode) CHK(rows_encode_chunk(h, row_ptr, c.c0, c.nu));
+    const uint32_t n_tiles = (uint32_t)(c.t1 - c.t0);
+    const size_t n_cand = (size_t)(c.p1 - c.p0);
+    DISPATCH_NI(h->NI, cdae::score_rows_kernel, dim3((n_tiles + cdae::SCORE_WAVES - 1) / cdae::SCORE_WAVES), dim3(cdae::SCORE_WAVES * cdae::WAVE), 0,
+                h->stream, h->hp, (const uint2*)(h->d_cand_tiles + c.t0), n_tiles, (const uint32_t*)(h->d_cand_col + c.p0), (const float*)h->d_zeval,
+                (const float*)h->dec(), (const float*)h->P(CDAE_P_BP), h->d_cand_score);
+    if (out_ranks)
+      hipLaunchKernelGGL(cdae::rank_rows_kernel, dim3((uint32_t)(c.rb - c.ra)), dim3(256), 0, h->stream, (const int64_t*)h->d_cand_ptr, c.ra, c.p0,
+                         (int64_t)n_cand, (const float*)h->d_cand_score, h->d_cand_rank);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(out_scores + c.p0, h->d_cand_score, n_cand * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    if (out_ranks) HIPCHK(hipMemcpyAsync(out_ranks + c.p0, h->d_cand_rank, n_cand * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));                                                 // one per chunk: the buffers are the next chunk's too
+  }
+  return 0;
+}
 }  // namespace
 
 extern "C" {
+
+int cdae_hip_score_rows(cdae_hip_t* h, uint64_t n_rows, const uint32_t* uids, const int64_t* row_ptr, const uint32_t* col,
+                        const int64_t* cand_row_ptr, const uint32_t* cand_col, float* out_scores, uint32_t* out_ranks) {
+  const RowsArgs a{n_rows, uids, row_ptr, col, nullptr, nullptr, 0, 1, nullptr, nullptr};
+  CHK(rows_check(h, "cdae_hip_score_rows", a));
+  if (n_rows == 0) return 0;
+  CHK(validate_rows_csr("candidate", cand_row_ptr, cand_col, n_rows, h->I));
+  if (cand_row_ptr[n_rows] == 0) return 0;
+  if (!out_scores) return fail("cdae_hip_score_rows: null out_scores with %lld candidates", (long long)cand_row_ptr[n_rows]);
+  if (out_ranks)
+    for (uint64_t r = 0; r < n_rows; ++r)
+      if (cand_row_ptr[r + 1] - cand_row_ptr[r] > (int64_t)CDAE_RANK_CANDIDATES_MAX)
+        return fail("cdae_hip_score_rows: candidate row %llu has %lld candidates, ranks are computed for rows of at most %u", (unsigned long long)r,
+                    (long long)(cand_row_ptr[r + 1] - cand_row_ptr[r]), CDAE_RANK_CANDIDATES_MAX);
+  return score_run(h, n_rows, uids, row_ptr, col, cand_row_ptr, cand_col, out_scores, out_ranks);
+}
 
 int cdae_hip_recommend_rows(cdae_hip_t* h, uint64_t n_rows, const uint32_t* uids, const int64_t* row_ptr, const uint32_t* col,
                             uint32_t topk, uint32_t* out_ids, float* out_scores) {

@@ -221,6 +221,93 @@ encode_rows_long_kernel(HyperParams hp, const int64_t* __restrict__ row_ptr, con
   enc_rows_finish<NI>(hp, acc, bb, wu, uu, lane, Z + (size_t)slot * hp.Kp);
 }
 
+// ---- scores and ranks of caller-supplied candidates (cdae_hip_score_rows: get_output_values, cdae.hpp:418-426) -------------------
+// out[p] = D[cand[p]] . z_row + b'[cand[p]] for the candidates of a chunk.  A gather, not a GEMM: ~100 candidates out of thousands
+// of items would leave the matrix-core path streaming 99 % of D for nothing.  Work unit: a TILE of up to SCORE_TILE consecutive
+// candidates of one row, one wavefront per tile, SCORE_WAVES tiles to a workgroup, no LDS and no barrier (encode_rows_kernel's
+// pattern).  The wavefront keeps z_row in NI registers per lane (lane l owns elements [l NI, (l + 1) NI), pad elements 0 by
+// enc_rows_finish), takes the candidate ids one per lane and streams the candidates' D rows as whole-row wave loads, UN in flight.
+//
+// Contraction order (part of the contract, include/cdae_hip.h) — one per row stride, the same for every candidate wherever it sits:
+//   lane l:      p = z[l NI] * D[l NI], then p = p + z[l NI + i] * D[l NI + i] for i = 1 .. NI - 1, every product and every sum
+//                rounded on its own (contract(off): no fused multiply-add);
+//   across lanes: wave_sum's tree — lanes 1 apart, 2 apart, the two quads of 8, the two eights of a row of 16, then row 0 + row 1
+//                and row 2 + row 3, then the two halves;
+//   then + b'[item], once.
+// So the score of (row, item) is a function of z_row, D[item] and b'[item] alone.
+//
+// Tile table (built by the host while it validates the candidate CSR, uploaded with it): word x = slot of the row in the encoded
+// chunk | (candidates in the tile - 1) << 16, word y = offset of the tile's first candidate from the chunk's first candidate.
+constexpr uint32_t SCORE_TILE = 64;
+constexpr int SCORE_WAVES = 4;
+
+template <int NI>
+__global__ void __launch_bounds__(SCORE_WAVES * WAVE)
+score_rows_kernel(HyperParams hp, const uint2* __restrict__ tiles, uint32_t n_tiles, const uint32_t* __restrict__ cand /* the chunk's */,
+                  const float* __restrict__ Z /* [rows of the chunk][Kp] */, const float* __restrict__ D, const float* __restrict__ bp,
+                  float* __restrict__ out /* the chunk's */) {
+#pragma clang fp contract(off)
+  constexpr int UN = 8;
+  const uint32_t wid = threadIdx.x / WAVE, lane = threadIdx.x % WAVE;
+  const uint32_t t = blockIdx.x * SCORE_WAVES + wid;
+  if (t >= n_tiles) return;                                        // (no barrier in this kernel)
+  const uint2 tile = tiles[t];
+  const uint32_t tx = (uint32_t)__builtin_amdgcn_readfirstlane((int)tile.x), off = (uint32_t)__builtin_amdgcn_readfirstlane((int)tile.y);
+  const uint32_t slot = tx & 0xFFFFu, cnt = (tx >> 16) + 1u;
+  const uint32_t lo = lane * NI;
+  float z[NI];
+  vload<NI>(z, Z + (size_t)slot * hp.Kp + lo);
+  const uint32_t item = lane < cnt ? cand[off + lane] : 0u;
+  const float bias = lane < cnt ? bp[item] : 0.f;                  // requested before the rows
+  float s = 0.f;
+  for (uint32_t j0 = 0; j0 < cnt; j0 += UN) {
+    float v[UN][NI];
+#pragma unroll
+    for (int j = 0; j < UN; ++j)
+      if (j0 + j < cnt) {                                          // wave-uniform
+        const uint32_t it = (uint32_t)__builtin_amdgcn_readlane((int)item, (int)(j0 + j));
+        vload<NI>(v[j], D + (size_t)it * hp.Kp + lo);
+      }
+#pragma unroll
+    for (int j = 0; j < UN; ++j)
+      if (j0 + j < cnt) {
+        float p = z[0] * v[j][0];
+#pragma unroll
+        for (int i = 1; i < NI; ++i) p = p + z[i] * v[j][i];
+        const float total = wave_sum(p);
+        if (lane == j0 + j) s = total;
+      }
+  }
+  if (lane < cnt) out[off + lane] = s + bias;                      // one coalesced store per tile
+}
+
+// ranks[p] = how many candidates of the same row precede p in cdae_hip_recommend_all's total order (a strictly greater score, or an
+// equal score and a lower item id), from the very scores score_rows_kernel wrote.  Candidates ascend inside a row, so "a lower item
+// id" is "an earlier position" and the ids are not needed.  One workgroup per row of [row0, row0 + gridDim.x); the row's scores in
+// LDS (at most RANK_CANDIDATES_MAX of them: the host refuses longer rows before anything is launched).
+constexpr uint32_t RANK_CANDIDATES_MAX = 4096;
+__global__ void __launch_bounds__(256)
+rank_rows_kernel(const int64_t* __restrict__ cand_ptr, uint64_t row0, int64_t p_chunk /* the chunk's first candidate */, int64_t n_chunk,
+                 const float* __restrict__ scores /* the chunk's */, uint32_t* __restrict__ ranks /* the chunk's */) {
+  __shared__ float sc[RANK_CANDIDATES_MAX];
+  const uint64_t row = row0 + blockIdx.x;
+  const int64_t p0 = cand_ptr[row];
+  const uint32_t n = min((uint32_t)(cand_ptr[row + 1] - p0), RANK_CANDIDATES_MAX);
+  if (n == 0 || p0 < p_chunk || p0 + n > p_chunk + n_chunk) return;   // (workgroup-uniform, before the barrier; a row outside the chunk is not this launch's)
+  const float* mine = scores + (p0 - p_chunk);
+  for (uint32_t i = threadIdx.x; i < n; i += 256) sc[i] = mine[i];
+  __syncthreads();
+  for (uint32_t i = threadIdx.x; i < n; i += 256) {
+    const float si = sc[i];
+    uint32_t before = 0;
+    for (uint32_t q = 0; q < n; ++q) {
+      const float sq = sc[q];
+      before += (sq > si || (sq == si && q < i)) ? 1u : 0u;
+    }
+    ranks[(p0 - p_chunk) + i] = before;
+  }
+}
+
 constexpr size_t recommend_mfma_lds_bytes(int nch) {
   const size_t tiles = 2 * 32 * (size_t)(8 * nch + 4) * sizeof(float), merge = 2 * 4 * 64 * (size_t)REC_TOPK_MAX * sizeof(float);
   return tiles > merge ? tiles : merge;

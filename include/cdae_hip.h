@@ -25,6 +25,7 @@
  *   CDAE::recommend (all users, top-k)   cdae.hpp:162-196    cdae_hip_recommend_all
  *   CDAE::recommend (any rated sets)     cdae.hpp:162-196    cdae_hip_recommend_rows, cdae_hip_eval_topn_rows (batched),
  *                                                            cdae_hip_recommend_user (one user)
+ *   CDAE::get_output_values              cdae.hpp:418-426    cdae_hip_score_rows
  *   TOPN_Evaluation::evaluate            evaluation.hpp:113-181, evaluate_rec_list :183-219
  *                                                            cdae_hip_set_test_rows + cdae_hip_eval_topn
  *   (data-parallel exchange; no reference counterpart)       cdae_hip_delta_*, cdae_hip_comm_*, cdae_hip_exchange_*,
@@ -66,7 +67,9 @@ extern "C" {
  * 12: cdae_hip_decode_plan, cdae_hip_set_decode_fused (which launches the sampled decode + hidden-gradient step of a handle is made of);
  *     cdae_hip_multi_steps_per_epoch, cdae_hip_multi_train_steps (a range of the exchanged steps of an epoch: what bench.py times)
  *     added under 12 (no existing entry point or structure changed): cdae_hip_recommend_rows, cdae_hip_eval_topn_rows, CDAE_NO_USER —
- *     batched top-k and TOPN for rated sets the caller supplies */
+ *     batched top-k and TOPN for rated sets the caller supplies
+ *     added under 12 (no existing entry point or structure changed): cdae_hip_score_rows, CDAE_RANK_CANDIDATES_MAX — batched scores and
+ *     ranks of candidate sets the caller supplies */
 #define CDAE_HIP_ABI_VERSION 12
 
 /* numeric values follow libcf::LossType (/root/reference/src/model/loss.hpp:10-18) */
@@ -331,6 +334,45 @@ int cdae_hip_recommend_rows(cdae_hip_t* h, uint64_t n_rows, const uint32_t* uids
 int cdae_hip_eval_topn_rows(cdae_hip_t* h, uint64_t n_rows, const uint32_t* uids, const int64_t* row_ptr, const uint32_t* col,
                             const int64_t* target_row_ptr, const uint32_t* target_col, uint32_t topk, double* rets8, uint64_t* hits3,
                             uint32_t* ids_out);
+
+/* get_output_values(z, idx) (cdae.hpp:418-426) for MANY rows at once: the model's scores of the items the caller NAMES, and their
+ * ranks among themselves — re-ranking of a retrieved candidate set, sampled-candidate evaluation (one held-out positive among ~100
+ * sampled negatives, HR@k / NDCG@k from the positive's rank), held-out loss over any items.
+ *   rows, uids, hidden, order of the input sum
+ *            exactly cdae_hip_recommend_rows's, validated alike and encoded by the same launches: the z of a row is bit for bit the
+ *            z cdae_hip_recommend_rows ranks from (CDAE_NO_USER, uids == NULL and corruption_ratio == 1 mean what they mean there).
+ *   candidates
+ *            cand_row_ptr[n_rows + 1] / cand_col: a second host CSR over the same rows, items ascending and unique inside a row
+ *            (validated: an unsorted, duplicate or out-of-range candidate is an error that names the row); a row may be empty.  A
+ *            candidate MAY be one of the row's rated items and is scored like any other: exclusion is the caller's business, as in
+ *            get_output_values.
+ *   out_scores
+ *            [cand_row_ptr[n_rows]]: out_scores[p] = the fp32 D[cand_col[p]] . z_r + b'[cand_col[p]] of the row r that position p
+ *            belongs to (D = V when asymmetric, else W; the output is linear, as in the reference).  Required when there is at least
+ *            one candidate.
+ *   position independence
+ *            the score of (row, item) is a function of z_r, D[item] and b'[item] only: the same bits whatever else the call holds —
+ *            other candidates, other rows, the pair's place in its row, the chunking.  One contraction order per row stride
+ *            (cdae_hip_row_stride() = 64 NI floats, NI = 1, 2, 4, 8): lane l of a 64-lane wavefront owns elements [l NI, (l + 1) NI) and
+ *            computes p_l = z[l NI] * D[l NI], then p_l = p_l + z[l NI + i] * D[l NI + i] for i = 1 .. NI - 1 in ascending i, every
+ *            product and every sum rounded to fp32 on its own (no fused multiply-add); the 64 p_l are added as a balanced tree over
+ *            neighbouring lanes — (p_0 + p_1), (p_2 + p_3), ... then pairs of those, and so on for six levels, each level adding the
+ *            two halves of a block of 2, 4, 8, 16, 32, 64 consecutive lanes; b'[item] is added last, once.
+ *   out_ranks
+ *            NULL or [cand_row_ptr[n_rows]]: out_ranks[p] = the number of candidates of the same row that precede p in
+ *            cdae_hip_recommend_all's total order — a strictly greater score, or an equal score and a lower item id; 0 is the best.
+ *            Computed on the device from the very fp32 scores out_scores reports, so ranks and scores agree by construction.  With
+ *            out_ranks a row of more than CDAE_RANK_CANDIDATES_MAX candidates is an error that names the row, raised before anything
+ *            is launched.  Scores alone have no such cap: a row may list all num_items.
+ * n_rows == 0 succeeds and touches nothing; rows without any candidate succeed and write nothing.
+ * Refused (the handle stays usable): IMF / BPR handles, item shards, calls before cdae_hip_set_interactions, a null out_scores with
+ * candidates present.
+ * The caller's arrays are copied into grow-only device buffers of the handle (freed with it): a steady-state call allocates nothing.
+ * Work is taken in chunks of at most 32 768 rows and at most 65 536 candidates (whole candidate rows while they fit; a longer row is
+ * cut into chunks of 65 536), with one host synchronisation per chunk. */
+#define CDAE_RANK_CANDIDATES_MAX 4096u
+int cdae_hip_score_rows(cdae_hip_t* h, uint64_t n_rows, const uint32_t* uids, const int64_t* row_ptr, const uint32_t* col,
+                        const int64_t* cand_row_ptr, const uint32_t* cand_col, float* out_scores, uint32_t* out_ranks);
 
 /* ---- data-parallel exchange (north star: RCCL all-reduce of the shared W / W' / bias gradients;
  * Wu never leaves its GPU).  Each rank trains its own users from a common snapshot, then

@@ -1,6 +1,8 @@
 // Compile-and-link check of the host layer, and a tiny end-to-end driver used by the tests:
 //   host_check                      -> exercises the CPU-only pieces (flags, logging, Data, split, cache, heap, metrics)
 //   host_check --run_cdae=true ...  -> trains CDAE through Solver<CDAE> on a GPU (needs libcdae_hip.so + a device)
+#include <cmath>
+
 #include <glog/logging.h>
 #include <gflags/gflags.h>
 
@@ -178,6 +180,19 @@ int main(int argc, char* argv[]) {
     std::sort(left.begin(), left.end());
     CHECK(left == std::vector<size_t>({0, 1, 2})) << "a set that leaves three items must give exactly those, cut at the sentinel";
     LOG(INFO) << "recommend_rows OK (" << lists.size() << " rows)";
+    // score_rows(): the scores of named candidates in one device call.  The ids of every list above, in list order, must get
+    // non-increasing scores (the list was ranked from the same z); a candidate inside the rated set is scored like any other.
+    std::vector<std::vector<size_t>> cands(lists);
+    cands[n_train_rows].push_back(fewer_items.front());                                             // a rated item of that row
+    const std::vector<std::vector<double>> scores = trained->score_rows(row_uids, sets, cands);
+    CHECK_EQ(scores.size(), lists.size());
+    for (size_t r = 0; r < lists.size(); ++r) {
+      CHECK_EQ(scores[r].size(), cands[r].size());
+      for (size_t i = 1; i < lists[r].size(); ++i)
+        CHECK_GE(scores[r][i - 1], scores[r][i]) << "score_rows: the scores of row " << r << " do not follow its list";
+    }
+    CHECK(std::isfinite(scores[n_train_rows].back())) << "a candidate inside the rated set must be scored";
+    LOG(INFO) << "score_rows OK (" << scores.size() << " rows)";
   }
   LOG(INFO) << "host layer OK";
   return 0;

@@ -289,6 +289,51 @@ class CDAE : public RecsysModelBase {
     return out;
   }
 
+  // get_output_values(z, idx) (cdae.hpp:418-426 of the reference) for many rows in ONE device call (cdae_hip_score_rows): row r is
+  // encoded from rated_sets[r] with the user node of uids[r] (kNoUser: none), exactly as recommend_rows() encodes it, and
+  // candidate_sets[r] are the items whose scores are wanted — in the caller's order, rated items allowed (nothing is excluded),
+  // duplicates refused.  scores[r][i] is the score of candidate_sets[r][i].  Single-handle models only; serialised on the handle's
+  // mutex like recommend().
+  std::vector<std::vector<double>> score_rows(const std::vector<size_t>& uids, const std::vector<std::vector<size_t>>& rated_sets,
+                                              const std::vector<std::vector<size_t>>& candidate_sets) const {
+    CHECK_EQ(uids.size(), rated_sets.size());
+    CHECK_EQ(candidate_sets.size(), rated_sets.size());
+    CHECK(!multi_) << "score_rows() is provided for a model on one device";
+    const size_t n = rated_sets.size();
+    std::vector<uint32_t> u(n), col, ccol;
+    std::vector<int64_t> ptr(n + 1, 0), cptr(n + 1, 0);
+    std::vector<size_t> where;                                     // where[p]: the place in candidate_sets[r] of sorted position p
+    for (size_t r = 0; r < n; ++r) {
+      if (uids[r] != kNoUser) CHECK_LT(uids[r], num_users_);
+      u[r] = uids[r] == kNoUser ? CDAE_NO_USER : static_cast<uint32_t>(uids[r]);
+      const size_t at = col.size();
+      for (size_t i : rated_sets[r]) { CHECK_LT(i, num_items_); col.push_back(static_cast<uint32_t>(i)); }
+      std::sort(col.begin() + at, col.end());                    // the device CSR is ascending inside a row (duplicates: its error)
+      ptr[r + 1] = static_cast<int64_t>(col.size());
+      const std::vector<size_t>& cand = candidate_sets[r];
+      const size_t cat = where.size();
+      for (size_t i = 0; i < cand.size(); ++i) { CHECK_LT(cand[i], num_items_); where.push_back(i); }
+      std::sort(where.begin() + cat, where.end(), [&cand](size_t a, size_t b) { return cand[a] < cand[b]; });
+      for (size_t p = cat; p < where.size(); ++p) {
+        CHECK(p == cat || cand[where[p]] != cand[where[p - 1]]) << "candidate " << cand[where[p]] << " is listed twice in row " << r;
+        ccol.push_back(static_cast<uint32_t>(cand[where[p]]));
+      }
+      cptr[r + 1] = static_cast<int64_t>(ccol.size());
+    }
+    std::vector<float> sc(ccol.size());
+    {
+      std::lock_guard<std::mutex> lk(*mu_);
+      CHECK(ready()) << "reset() must be called first";
+      CDAE_HIP_CHECK(cdae_hip_score_rows(dev_.get(), n, u.data(), ptr.data(), col.data(), cptr.data(), ccol.data(), sc.data(), nullptr));
+    }
+    std::vector<std::vector<double>> out(n);
+    for (size_t r = 0; r < n; ++r) {
+      out[r].resize(candidate_sets[r].size());
+      for (int64_t p = cptr[r]; p < cptr[r + 1]; ++p) out[r][where[p]] = sc[p];
+    }
+    return out;
+  }
+
   // recommend() for the user's own train row — what Evaluation asks for — without the caller building a hashtable
   // per user per epoch (evaluation.hpp:118-123): TOPN_Evaluation detects this method and uses it.
   std::vector<size_t> recommend_train_row(size_t uid, size_t topk) const {
