@@ -87,6 +87,7 @@ EXPORTS = {
     "cdae_hip_set_profiling": (C.c_int, [C.c_void_p, C.c_int]),
     "cdae_hip_set_profiling_families": (C.c_int, [C.c_void_p, C.c_uint32]),
     "cdae_hip_synchronize": (C.c_int, [C.c_void_p]),
+    "cdae_hip_debug_row_pack": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p, C.POINTER(C.c_uint64)]),
     "cdae_hip_debug_sample_batch": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32] + [C.c_void_p] * 8
                                     + [C.POINTER(C.c_uint64)]),
     "cdae_hip_encode": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
@@ -360,6 +361,14 @@ class CDAE:
             self.h, seed, epoch, u_begin, n_users, cidx, *[a.ctypes.data for a in out.values()], C.byref(n)))
         assert n.value == E
         return out
+
+    def debug_row_pack(self, seed: int, epoch: int, u_begin: int, n_users: int, cidx: int = 0) -> np.ndarray:
+        """The row pack of one batch prepared as training would (cdae_hip_debug_row_pack): uint32 [records, 4] of
+        (item, sorted begin, sorted end, popularity rank); no rows for a handle or batch without a pack."""
+        rec = np.empty(((self.num_items + 3) // 4 * 4, 4), np.uint32)
+        n = C.c_uint64(rec.shape[0])
+        _chk(self.lib, self.lib.cdae_hip_debug_row_pack(self.h, seed, epoch, u_begin, n_users, cidx, rec.ctypes.data, C.byref(n)))
+        return rec[:n.value].copy()
 
     def train_one_user_corruption(self, uid: int, input_items, negative_items):
         """cdae.hpp:198-200 with explicit input set; negatives as the reference would have drawn them."""

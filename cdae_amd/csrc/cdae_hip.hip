@@ -11,6 +11,7 @@
 #include <atomic>
 #include <condition_variable>
 #include <deque>
+#include <functional>
 #include <mutex>
 #include <thread>
 #include <chrono>
@@ -20,6 +21,7 @@
 #include <cstdio>
 #include <cstring>
 #include <numeric>
+#include <random>
 #include <string>
 #include <vector>
 
@@ -116,6 +118,8 @@ struct cdae_hip {
   uint32_t* d_fused_err = nullptr;  // the same word as the device sees it
   cdae::FusedGeom fused_geo{};      // geometry of this handle's fused launch (set at the first one)
   bool fused_geo_set = false;
+  bool row_pack = true;             // the four-row role takes its rows from ExBuf::pack (CDAE_ROW_PACK=0, developer switch: popularity order as before)
+  std::vector<float> h_pack_len;    // [I - hot_rows] expected lengths of the packed rows, longest first: one synthetic draw from h_rank_len (fused launch: balancing packed groups)
   std::vector<float> h_rank_len;    // [I] expected examples per batch of the row of popularity rank r (fused launch: balancing the four-row groups over the SIMDs)
   uint32_t* d_cold_map = nullptr;   // [decode workgroups x 4] four-row group of every wavefront of the fused launch's row workgroups (0xFFFFFFFF: none)
   uint32_t num_cus = 256;
@@ -160,6 +164,7 @@ struct cdae_hip {
     uint32_t* wg_state = nullptr;                                    // bucket_sort_kernel: one word per item range (cleared by the sample kernel)
     uint32_t* cells = nullptr; uint32_t* cell_flag = nullptr;        // ... and its cells [ranges][units][BKC_SLOTS], filled by sample_kernel; overflow word
     uint32_t cell_tag = 0;                                           // (host) the tag of the batch last prepared into this set
+    cdae::RowRecord* pack = nullptr;                                 // row_pack_kernel: the batch's rows of the four-row decode role by this batch's length (nullptr: handle without the role)
     hipEvent_t ready = nullptr, released = nullptr;
   } ex[3];
   static constexpr int NSETS = 3;
@@ -458,7 +463,7 @@ template <class F, class... P> int visit_slots(F& f, P*&... p) {
 template <class F> int visit_device_ptrs(cdae_hip* h, F f) {
   for (auto& b : h->ex)
     CHK(visit_slots(f, b.item, b.val, b.sorted_item, b.sorted_val, b.seg, b.dup_of_pos, b.dup_of_ex, b.dup_count, b.key16, b.sorted_key16,
-                    b.item_count, b.prefix, b.rank, b.bucketed, b.tile_hist, b.block_total, b.wg_state, b.cells, b.cell_flag));
+                    b.item_count, b.prefix, b.rank, b.bucketed, b.tile_hist, b.block_total, b.wg_state, b.cells, b.cell_flag, b.pack));
   return visit_slots(f, h->d_row_ptr, h->d_col, h->d_item_order, h->d_shared, h->d_Wu, h->d_Wu_ag, h->d_D0, h->d_HGpart, h->d_sort_tmp,
                      h->d_unit_ptr, h->d_Hpart, h->d_uptr_tmp, h->d_Zb, h->d_ZTb, h->d_Db, h->d_DTb, h->d_Gb, h->d_GTb, h->d_dD, h->d_has_in,
                      h->d_Z, h->d_Dz, h->d_HG, h->d_G, h->d_touched, h->d_uids, h->d_rec, h->d_base, h->d_delta, h->d_recv, h->d_snap,
@@ -534,6 +539,14 @@ struct Batch { uint64_t s0; uint32_t nb; uint32_t cidx; uint64_t E; };
 inline uint32_t units_of(const cdae_hip* h, const Batch& b) { return h->h_unit_ptr[b.s0 + b.nb] - h->h_unit_ptr[b.s0]; }
 // item shard, sampled decode: units over the WHOLE rows (sample_kernel, hidden_gather_kernel)
 inline uint32_t gunits_of(const cdae_hip* h, const Batch& b) { return h->h_gunit_ptr[b.s0 + b.nb] - h->h_gunit_ptr[b.s0]; }
+
+// Rows [0, decode_hot_rows) take a wavefront of their own in the K <= 256 decode launches; the others go four to a wavefront.
+inline uint32_t decode_hot_rows(const cdae_hip* h) { return std::min<uint32_t>(h->hot_rows, (uint32_t)h->I); }
+// Handles whose batches get a row pack (row_pack_kernel): the sampled K <= 256 decode of a single handle.  An item shard's decode takes
+// its rows in popularity order (pack == nullptr): its step is paced by the exchange, not by this launch.
+inline bool packs_rows(const cdae_hip* h) { return h->row_pack && h->K <= 256 && !h->mf && !h->cfg.full_output && !h->item_shard; }
+// ... and the batches of such a handle that have one: every batch prep_batch ordered (an explicit input set is ordered by its caller)
+inline cdae::RowRecord* pack_of(const cdae_hip* h, const cdae_hip::ExBuf& x, uint64_t E) { return packs_rows(h) && E > 0 ? x.pack : nullptr; }
 
 // K1 + sort on the prep stream into example-buffer set `b`
 // lane 1: the second prep stream with the second half of the sort workspace (two batches are prepared side by side)
@@ -621,6 +634,9 @@ int prep_batch(cdae_hip* h, int b, const Batch& bt, uint64_t seed, uint32_t epoc
                        x.seg, x.seg + I, x.dup_count, h->dup_cap, x.dup_of_pos, x.dup_of_ex, h->dup_stripes,
                        (const uint32_t*)h->d_rank_of, x.seg + 2 * (size_t)I, x.seg + 3 * (size_t)I, shs ? I : 0xFFFFFFFFu);
   }
+  if (RowRecord* const pack = pack_of(h, x, bt.E))
+    hipLaunchKernelGGL(row_pack_kernel, dim3(1), dim3(ROW_PACK_THREADS), 0, st, (const uint32_t*)h->d_item_order, (const uint32_t*)(x.seg + 2 * (size_t)I),
+                       (const uint32_t*)(x.seg + 3 * (size_t)I), decode_hot_rows(h), I, pack);
   CHK(pr.end());
   if (h->cfg.full_output && h->d_bits_train) {
     // fused full-output decode: its targets — one bit per (batch user, item) — depend on the data set only, so they are
@@ -635,7 +651,8 @@ int prep_batch(cdae_hip* h, int b, const Batch& bt, uint64_t seed, uint32_t epoc
 }
 
 // Geometry of the fused launch (decode_gather_kernel), once per handle.
-int fused_geometry(cdae_hip* h, uint32_t hot, uint32_t I) {
+// packed: the groups hold the batch's rows by length (row_pack_kernel) — group q the 4q-th .. (4q+3)-th longest
+int fused_geometry(cdae_hip* h, uint32_t hot, uint32_t I, bool packed) {
   using namespace cdae;
   FusedGeom g{};
   g.hot_wgs = (hot + 3) / 4;
@@ -646,6 +663,19 @@ int fused_geometry(cdae_hip* h, uint32_t hot, uint32_t I) {
   // on it): the k-th group of bin (cu, w) goes to workgroup cu + k S.  The popular rows' CUs take no group.
   const uint32_t n_groups = (I - hot + 3) / 4, S = h->num_cus;
   std::vector<float> len(n_groups, 0.f);
+  if (packed) {
+    // Packed group q lasts as long as the 4q-th longest row of the batch: an ORDER STATISTIC of the lengths, not a rank's mean (in the
+    // tail the means are flat while the sorted lengths run from ~30 down to ~3).  One synthetic batch stands for all: Poisson draws
+    // from the rows' means, fixed seed, sorted.  Scheduling only — no result depends on it.
+    if (h->h_pack_len.size() != (size_t)(I - hot)) {
+      std::mt19937_64 rng(0x9E3779B97F4A7C15ull);
+      h->h_pack_len.resize(I - hot);
+      for (uint32_t r = hot; r < I; ++r)
+        h->h_pack_len[r - hot] = (float)std::poisson_distribution<uint32_t>(std::max((double)h->h_rank_len[r], 1e-6))(rng);
+      std::sort(h->h_pack_len.begin(), h->h_pack_len.end(), std::greater<float>());
+    }
+    for (uint32_t q = 0; q < n_groups; ++q) len[q] = h->h_pack_len[4 * (size_t)q];
+  } else
   for (uint32_t q = 0; q < n_groups; ++q)
     for (uint32_t j = 0; j < 4 && hot + 4 * q + j < I; ++j) len[q] = std::max(len[q], h->h_rank_len[hot + 4 * q + j]);
   std::vector<uint32_t> by_len(n_groups);
@@ -692,14 +722,15 @@ int fused_geometry(cdae_hip* h, uint32_t hot, uint32_t I) {
 // K3 on the main stream: the decode of example-buffer set `x` over this handle's item rows (shared by the single-handle step and
 // the sampled item-shard step)
 // fused != nullptr: the fused launch (decode_gather_kernel) with these gather arguments; the caller then launches no hidden_gather_kernel
-int launch_decode(cdae_hip* h, cdae_hip::ExBuf& x, const cdae::GatherArgs* fused = nullptr) {
+// pack: the set's row pack of this batch (pack_of), or nullptr: rows in popularity order
+int launch_decode(cdae_hip* h, cdae_hip::ExBuf& x, const cdae::GatherArgs* fused = nullptr, const cdae::RowRecord* pack = nullptr) {
   using namespace cdae;
   hipStream_t st = h->stream;
   const uint32_t I = (uint32_t)h->I;
   const dim3 blk(256);
   const dim3 grid_rows((I + 3) / 4);
 #define DECODE_TAIL h->d_item_order, x.seg + 2 * (size_t)I, x.seg + 3 * (size_t)I, x.sorted_val, h->d_Z, h->dec(), h->dec_ag(), \
-                    h->P(CDAE_P_BP), h->P(CDAE_P_BP_AG), h->d_HG, h->d_G, h->d_D0, h->d_touched, x.dup_of_pos, h->d_dup_corr
+                    h->P(CDAE_P_BP), h->P(CDAE_P_BP_AG), h->d_HG, h->d_G, h->d_D0, h->d_touched, x.dup_of_pos, h->d_dup_corr, pack_arg
 #define DECODE_ARGS h->hp, DECODE_TAIL
 #define DECODE_LA(NI_, L_, A_)                                                                                       \
   do {                                                                                                               \
@@ -734,13 +765,14 @@ int launch_decode(cdae_hip* h, cdae_hip::ExBuf& x, const cdae::GatherArgs* fused
   {
     const bool ce = h->cfg.loss_type == CDAE_LOSS_CROSS_ENTROPY, ada = h->cfg.using_adagrad != 0, pad = h->K < h->Kp;
     const uint32_t K = h->K;
+    const RowRecord* const pack_arg = K <= 256 ? pack : nullptr;        // (decode_rows_kernel has no four-row role)
     if (K <= 256) {
-      const uint32_t hot = std::min<uint32_t>(h->hot_rows, I);
+      const uint32_t hot = decode_hot_rows(h);
       const uint32_t waves = hot + (I - hot + 3) / 4;
       const dim3 grid_hy((waves + 3) / 4);
       const DecodeLate late = h->decode_late();
       // fused launch (decode_gather_kernel): [popular rows] [the other rows] [gather]
-      if (fused && !h->fused_geo_set) CHK(fused_geometry(h, hot, I));
+      if (fused && !h->fused_geo_set) CHK(fused_geometry(h, hot, I, pack != nullptr));
       const FusedGeom geo = h->fused_geo;
       const dim3 grid_fu(geo.decode_wgs + (fused ? 8u * ((fused->n_units + 3u) / 4u) : 0u));
       const uint32_t nv = K / 64, tail = K % 64;
@@ -833,7 +865,7 @@ int compute_batch(cdae_hip* h, int b, const Batch& bt, uint64_t seed, uint32_t e
                       h->d_dup_corr, explicit_in ? (const uint32_t*)nullptr : (const uint32_t*)h->d_unit_user,
                       h->late_rows ? (const uint32_t*)h->d_late_bits : (const uint32_t*)nullptr, h->late_words, h->d_fused_err};
   CHK(pr.begin(h, F_DECODE, st));
-  CHK(launch_decode(h, x, fused ? &ga : nullptr));
+  CHK(launch_decode(h, x, fused ? &ga : nullptr, explicit_in ? nullptr : pack_of(h, x, bt.E)));
   CHK(pr.end());
 
   CHK(pr.begin(h, F_HIDDEN, st));
@@ -1300,6 +1332,7 @@ int cdae_hip_create(const cdae_hip_config* cfg, int device_id, cdae_hip_t** out)
   if (const char* e = DEV_ENV("CDAE_FULL_ROWS_KH")) h->rows_fused_kh = std::atoi(e) == 1 ? 1 : 2;
   if (const char* v = DEV_ENV("CDAE_FULL_ONE_STREAM_MAX")) h->full_one_stream_max = (uint32_t)std::strtoul(v, nullptr, 10);
   h->debug_skip_prep = DEV_ENV("CDAE_DEBUG_SKIP_PREP") != nullptr;
+  if (const char* ev = DEV_ENV("CDAE_ROW_PACK")) h->row_pack = std::atoi(ev) != 0;
   h->encode_two_launches = DEV_ENV("CDAE_ENCODE_TWO_LAUNCHES") != nullptr;
   if (const char* ev = DEV_ENV("CDAE_PREP_THREAD")) h->prep_threaded = std::atoi(ev) != 0;
   hipError_t e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
@@ -1758,6 +1791,7 @@ int cdae_hip_set_interactions(cdae_hip_t* h, uint64_t U, uint64_t I, const int64
     CHK(dev_alloc(&b.sorted_item, h->Ecap)); CHK(dev_alloc(&b.sorted_val, h->Ecap));
     CHK(dev_alloc(&b.seg, 4 * (size_t)I));                   // first | one-past-last position by item, then the same by popularity rank
     CHK(dev_alloc(&b.dup_of_pos, h->Ecap)); CHK(dev_alloc(&b.dup_of_ex, h->Ecap)); CHK(dev_alloc(&b.dup_count, cdae::DUP_STRIPES));
+    if (packs_rows(h)) CHK(dev_alloc(&b.pack, ((size_t)I + 3) & ~(size_t)3));   // whole wavefronts of the rows [hot_rows, I)
     if (h->counting_sort) {
       CHK(dev_alloc(&b.item_count, (size_t)I)); CHK(dev_alloc(&b.prefix, (size_t)I + 1));
       CHK(dev_alloc(&b.rank, (size_t)I)); CHK(dev_alloc(&b.bucketed, h->Ecap));
@@ -2418,6 +2452,22 @@ int cdae_hip_collect_stats(cdae_hip_t* h, cdae_hip_stats* stats) {
   CHK(join_aux(h));
   HIPCHK(hipStreamSynchronize(h->stream));
   return fill_stats(h, stats);
+}
+
+int cdae_hip_debug_row_pack(cdae_hip_t* h, uint64_t seed, uint32_t epoch, uint64_t u_begin, uint32_t n_users, uint32_t cidx,
+                            uint32_t* out_records, uint64_t* n_records) {
+  if (!n_records) return fail("null argument");
+  if (!h || !h->d_shared) return fail("set_interactions must be called first");
+  const uint32_t hot = decode_hot_rows(h);
+  const uint64_t want = packs_rows(h) ? (((uint64_t)h->I - hot + 3) & ~3ull) : 0;
+  if (want > *n_records) return fail("the pack has %llu records, the caller's array holds %llu", (unsigned long long)want, (unsigned long long)*n_records);
+  // the batch prepared as training would: sampling, sort, pack (cdae_hip_debug_sample_batch checks the arguments)
+  uint64_t E = h->Ecap;
+  CHK(cdae_hip_debug_sample_batch(h, seed, epoch, u_begin, n_users, cidx, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &E));
+  const cdae::RowRecord* pack = pack_of(h, h->ex[h->seq % cdae_hip::NSETS], E);
+  *n_records = pack ? want : 0;
+  if (pack && out_records && want) HIPCHK(hipMemcpy(out_records, pack, want * sizeof(cdae::RowRecord), hipMemcpyDeviceToHost));
+  return 0;
 }
 
 int cdae_hip_debug_sample_batch(cdae_hip_t* h, uint64_t seed, uint32_t epoch, uint64_t u_begin, uint32_t n_users,

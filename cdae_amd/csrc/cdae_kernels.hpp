@@ -828,6 +828,12 @@ encode_users_kernel(HyperParams hp, const int64_t* __restrict__ row_ptr, const u
 // parked in lane (p mod 64) of one VGPR and written once per chunk.  The inner loop therefore issues
 // loads only, which is what lets s_waitcnt vmcnt(N) be counted instead of drained (on gfx9 stores share
 // the counter and complete out of order with loads).
+// One row of the four-rows-per-wavefront role as row_pack_kernel (cdae_sort_kernels.hpp) lays the batch's rows out: sorted by THIS
+// batch's segment length, longest first, so that the four rows of a wavefront end together.  `pack` == nullptr: no such table, the
+// rows are taken in popularity order (item_order / seg_begin / seg_end by rank).  decode_row64 and decode_rows_kernel ignore it.
+struct alignas(16) RowRecord { uint32_t item, begin, end, rank; };
+constexpr uint32_t ROW_RECORD_PAD = 0xFFFFFFFFu;                 // `rank` of the zero-length records that fill the last wavefront
+
 constexpr int WAIT_VM0 = 0x0F70;   // s_waitcnt vmcnt(0) (expcnt 7, lgkmcnt 15 = don't care), gfx9 encoding
 
 #define CDAE_DECODE_PARAMS                                                                                         \
@@ -835,9 +841,9 @@ constexpr int WAIT_VM0 = 0x0F70;   // s_waitcnt vmcnt(0) (expcnt 7, lgkmcnt 15 =
       const uint32_t *__restrict__ seg_end, const uint64_t *__restrict__ sorted_val, const float *__restrict__ Z,  \
       float *__restrict__ D, float *__restrict__ D_ag, float *__restrict__ bp, float *__restrict__ bp_ag,           \
       float *__restrict__ HGcorr, float *__restrict__ G, float *__restrict__ D0, uint32_t *__restrict__ touched,    \
-      const uint32_t *__restrict__ dup_of_pos, float *__restrict__ dup_corr
+      const uint32_t *__restrict__ dup_of_pos, float *__restrict__ dup_corr, const RowRecord *__restrict__ pack
 #define CDAE_DECODE_PASS \
-  item_order, seg_begin, seg_end, sorted_val, Z, D, D_ag, bp, bp_ag, HGcorr, G, D0, touched, dup_of_pos, dup_corr
+  item_order, seg_begin, seg_end, sorted_val, Z, D, D_ag, bp, bp_ag, HGcorr, G, D0, touched, dup_of_pos, dup_corr, pack
 
 // One row per wavefront; lane holds NI contiguous floats of the row.
 // BIAS_IN_PAD (K < Kp, e.g. K = 200 or 50): b'[j] rides in the last pad element of the row registers with a
@@ -1308,14 +1314,23 @@ constexpr uint32_t ROWS16_LDS_WORDS = 4u * 128u + 4u * 128u + 4u * 64u;
 constexpr uint32_t ROW64_PARK_WORDS = ROWS16_LDS_WORDS;          // the same words as decode_row64 uses them: g parked until the row's end
 
 template <int NV, int NT, int LOSS, bool ADAGRAD, bool FUSED = false>
-__device__ __forceinline__ void decode_rows16(HyperParams hp, const uint32_t rank0, uint32_t* __restrict__ lds, CDAE_DECODE_PARAMS) {
+__device__ __forceinline__ void decode_rows16(HyperParams hp, const uint32_t rank0, const uint32_t rec0, uint32_t* __restrict__ lds, CDAE_DECODE_PARAMS) {
   constexpr int GRP = 16, NE = 4 * NV + NT;
   constexpr bool HAS_PAD = NT > 0;
   const uint32_t lane = threadIdx.x % WAVE, l = lane & (GRP - 1), sub = lane / GRP;
   const uint32_t rank = rank0 + sub;
-  const bool row_ok = rank < hp.num_items;
-  const uint32_t item = row_ok ? item_order[rank] : 0u;
-  const uint32_t beg = row_ok ? seg_begin[rank] : 0u, end = row_ok ? seg_end[rank] : 0u;    // (rank-indexed tables)
+  uint32_t item, beg, end;
+  if (pack) {
+    // packed rows: record rec0 + sub (one 16-byte load).  The table holds whole wavefronts — rank0 < num_items says that this one exists
+    // — and its zero-length records (empty rows, fill) take the row-less path below
+    RowRecord rec{0u, 0u, 0u, ROW_RECORD_PAD};
+    if (rank0 < hp.num_items) rec = pack[rec0 + sub];
+    item = rec.item; beg = rec.begin; end = rec.end;
+  } else {
+    const bool row_ok = rank < hp.num_items;
+    item = row_ok ? item_order[rank] : 0u;
+    beg = row_ok ? seg_begin[rank] : 0u; end = row_ok ? seg_end[rank] : 0u;                 // (rank-indexed tables)
+  }
   const uint32_t n = end - beg;
   // longest segment of the wavefront's four groups (wave-uniform loop bound)
   const uint32_t nmax = max(max((uint32_t)__builtin_amdgcn_readlane((int)n, 0), (uint32_t)__builtin_amdgcn_readlane((int)n, 16)),
@@ -1543,7 +1558,7 @@ decode_hybrid_kernel(HyperParams hp, uint32_t hot_rows, DecodeLate late, CDAE_DE
   } else {
     if (CDAE_SKIP_ROLE(hp, 8u)) return;
     const unsigned long long t0 = trace_begin(hp);
-    decode_rows16<NV, NT, LOSS, ADAGRAD>(hp, hot_rows + (wave - hot_rows) * 4u, rows16_lds[threadIdx.x / WAVE], CDAE_DECODE_PASS);
+    decode_rows16<NV, NT, LOSS, ADAGRAD>(hp, hot_rows + (wave - hot_rows) * 4u, (wave - hot_rows) * 4u, rows16_lds[threadIdx.x / WAVE], CDAE_DECODE_PASS);
     trace_end(hp, 4, wave, t0);
   }
 }
@@ -1807,7 +1822,7 @@ decode_gather_kernel(HyperParams hp, uint32_t hot_rows, FusedGeom geo, DecodeLat
     const uint32_t g = geo.cold_map[wg * 4u + (uint32_t)mine];
     if (g == 0xFFFFFFFFu) return;
     const unsigned long long t0 = trace_begin(hp);
-    decode_rows16<NV, NT, LOSS, ADAGRAD, true>(hp, hot_rows + g * 4u, fused_lds + wid * ROWS16_LDS_WORDS, CDAE_DECODE_PASS);
+    decode_rows16<NV, NT, LOSS, ADAGRAD, true>(hp, hot_rows + g * 4u, g * 4u, fused_lds + wid * ROWS16_LDS_WORDS, CDAE_DECODE_PASS);
     trace_end(hp, 4, hot_rows / 4u + g, t0, hp.trace ? hw_place() : 0u);
   } else {
     // ---- hidden-gradient gather of the rows that are not late ----

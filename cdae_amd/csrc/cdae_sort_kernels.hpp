@@ -581,4 +581,52 @@ bucket_sort_kernel(const uint16_t* __restrict__ keys, const uint64_t* __restrict
   }
 }
 
+// ------------------------------------------------------------------------------------------------
+// row_pack_kernel — the batch's rows of the four-rows-per-wavefront decode role (decode_rows16), ordered by THIS batch's segment
+// length.  A wavefront of that role loops to the longest of its four segments and issues every instruction for the groups that have
+// already ended; with four rows of neighbouring popularity rank the actual lengths differ (sums of a few Poisson-like counts) and a
+// fifth of the role's example steps belonged to ended rows.  Sorted by length, four neighbours end together.
+// One workgroup per batch, on the batch's prep lane right behind its sort (either sort path has filled the rank-indexed segment
+// tables for EVERY row, 0,0 for empty ones): a counting sort by n = min(seg end - seg begin, ROW_PACK_BINS - 1), descending, with an LDS
+// histogram.  Rows of one bin are placed by LDS atomics in arrival order — which rows share a wavefront changes no bit of the
+// result (a row's chain touches only its own registers; G, D0 and the correction rows are indexed by example / item).
+// pack[0 .. 4 n_groups): ranks [hot_rows, num_items) as records, then zero-length fill records up to the multiple of four.
+constexpr uint32_t ROW_PACK_THREADS = 1024;
+constexpr uint32_t ROW_PACK_BINS = 1024;                 // longer rows share the top bin (they are the hot rows' business anyway)
+__global__ void __launch_bounds__(ROW_PACK_THREADS)
+row_pack_kernel(const uint32_t* __restrict__ item_order, const uint32_t* __restrict__ segr_begin, const uint32_t* __restrict__ segr_end,
+                uint32_t hot_rows, uint32_t num_items, RowRecord* __restrict__ pack) {
+  static_assert(ROW_PACK_BINS == ROW_PACK_THREADS, "one bin per thread in the scan");
+  __shared__ uint32_t cursor[ROW_PACK_BINS];             // histogram by bin, then the bin's next free slot
+  __shared__ uint32_t wave_sum[ROW_PACK_THREADS / WAVE];
+  const uint32_t t = threadIdx.x;
+  const uint32_t n_rows = num_items - hot_rows;          // (the host launches with hot_rows <= num_items)
+  cursor[t] = 0u;
+  __syncthreads();
+  for (uint32_t r = hot_rows + t; r < num_items; r += ROW_PACK_THREADS)
+    atomicAdd(&cursor[min(segr_end[r] - segr_begin[r], ROW_PACK_BINS - 1u)], 1u);
+  __syncthreads();
+  // exclusive prefix in DESCENDING bin order: thread t owns bin ROW_PACK_BINS - 1 - t
+  const uint32_t bin = ROW_PACK_BINS - 1u - t;
+  const uint32_t mine = cursor[bin];
+  uint32_t incl = mine;
+#pragma unroll
+  for (int d = 1; d < WAVE; d <<= 1) {
+    const uint32_t up = __shfl_up(incl, d, WAVE);
+    if ((t % WAVE) >= (uint32_t)d) incl += up;
+  }
+  if (t % WAVE == WAVE - 1) wave_sum[t / WAVE] = incl;
+  __syncthreads();
+  uint32_t before = 0;
+  for (uint32_t w = 0; w < t / WAVE; ++w) before += wave_sum[w];
+  cursor[bin] = before + incl - mine;
+  __syncthreads();
+  for (uint32_t r = hot_rows + t; r < num_items; r += ROW_PACK_THREADS) {
+    const uint32_t b = segr_begin[r], e = segr_end[r];
+    const uint32_t slot = atomicAdd(&cursor[min(e - b, ROW_PACK_BINS - 1u)], 1u);
+    if (slot < n_rows) pack[slot] = RowRecord{item_order[r], b, e, r};       // (always: the bins' counts add up to n_rows)
+  }
+  for (uint32_t s = n_rows + t; s < ((n_rows + 3u) & ~3u); s += ROW_PACK_THREADS) pack[s] = RowRecord{0u, 0u, 0u, ROW_RECORD_PAD};
+}
+
 }  // namespace cdae

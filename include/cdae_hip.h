@@ -69,7 +69,8 @@ extern "C" {
  *     added under 12 (no existing entry point or structure changed): cdae_hip_recommend_rows, cdae_hip_eval_topn_rows, CDAE_NO_USER —
  *     batched top-k and TOPN for rated sets the caller supplies
  *     added under 12 (no existing entry point or structure changed): cdae_hip_score_rows, CDAE_RANK_CANDIDATES_MAX — batched scores and
- *     ranks of candidate sets the caller supplies */
+ *     ranks of candidate sets the caller supplies
+ *     also under 12, the version unchanged (a test hook beside cdae_hip_debug_sample_batch; nothing existing changed): cdae_hip_debug_row_pack */
 #define CDAE_HIP_ABI_VERSION 12
 
 /* numeric values follow libcf::LossType (/root/reference/src/model/loss.hpp:10-18) */
@@ -260,6 +261,16 @@ int cdae_hip_debug_sample_batch(cdae_hip_t* h, uint64_t seed, uint32_t epoch, ui
                                 uint32_t cidx, uint32_t* ex_item, uint64_t* ex_val, uint32_t* sorted_item,
                                 uint64_t* sorted_val, uint32_t* seg_begin, uint32_t* seg_end, uint32_t* dup_of_pos,
                                 uint32_t* dup_of_ex, uint64_t* n_examples);
+
+/* Test hook beside cdae_hip_debug_sample_batch (tests/test_gpu_row_pack.py): prepares the same ONE batch the way training would and
+ * copies back its ROW PACK — the rows of the decode's four-rows-per-wavefront role, i.e. popularity ranks [hot_rows, num_items)
+ * (cdae_hip_decode_plan), ordered by this batch's segment length, longest first, so that the four rows of a wavefront end together.
+ * out_records holds *n_records records of four uint32 each on return: {item, sorted begin, sorted end, popularity rank}; the count is
+ * num_items - hot_rows rounded up to a multiple of four, the fill records are {0, 0, 0, 0xFFFFFFFF}.  The order among rows of equal
+ * length is arbitrary.  *n_records is the capacity of out_records (in records) on entry; 0 on return for a handle or batch that has
+ * no pack (num_dim > 256, full_output, IMF / BPR, item shards, a batch without examples).  out_records may be NULL. */
+int cdae_hip_debug_row_pack(cdae_hip_t* h, uint64_t seed, uint32_t epoch, uint64_t u_begin, uint32_t n_users, uint32_t cidx,
+                            uint32_t* out_records, uint64_t* n_records);
 
 /* z for `n` users (get_hidden_values, cdae.hpp:373-416).  mode 0: full train row, scale 1 (the
  * inference form, cdae.hpp:169); mode 1: training corruption of (seed, epoch, corruption 0) with the

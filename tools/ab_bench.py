@@ -4,7 +4,7 @@ runs differ by +-4 % between boxes and by a few % with the order they run in).
 
     python tools/ab_bench.py [--reps 5] [--args "--batch-users 256"] NAME=VAR1=x,VAR2=y NAME2= ...
 
-Prints the median / min / max ms_per_step per configuration.
+Prints every run, the mean and the sample standard deviation, and the median / min / max ms_per_step per configuration.
 """
 import argparse
 import json
@@ -39,6 +39,7 @@ def main():
             res[name].append(d["ms_per_step"])
     for name, _ in cfgs:
         v = np.array(res[name])
+        print(f"{name:24s} runs " + " ".join(f"{x:.5f}" for x in v) + f"  mean {v.mean():.5f}  sd {v.std(ddof=1) if len(v) > 1 else 0.0:.5f}")
         print(f"{name:24s} median {np.median(v):.5f} ms  min {v.min():.5f}  max {v.max():.5f}  ({len(v)} runs)  -> {256 / np.median(v):.0f}K users/s at 256" if "--batch-users" not in a.args else
               f"{name:24s} median {np.median(v):.5f} ms  min {v.min():.5f}  max {v.max():.5f}  ({len(v)} runs)")
 
