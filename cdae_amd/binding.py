@@ -97,6 +97,7 @@ EXPORTS = {
     "cdae_hip_recommend_user": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p]),
     "cdae_hip_recommend_rows": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
     "cdae_hip_score_rows": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "cdae_hip_full_rank_rows": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "cdae_hip_eval_topn_rows": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
                                           C.c_void_p, C.c_void_p, C.c_void_p]),
     "cdae_hip_set_test_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -463,6 +464,31 @@ class CDAE:
         _chk(self.lib, self.lib.cdae_hip_score_rows(self.h, n, None if ru is None else ru.ctypes.data, rp.ctypes.data, rc.ctypes.data,
                                                     cp.ctypes.data, cc.ctypes.data, scores.ctypes.data, ranks.ctypes.data if with_ranks else None))
         return (scores, ranks) if with_ranks else scores
+
+    def full_rank_rows(self, row_ptr, col, target_ptr, target_col, uids=None, with_scores: bool = False):
+        """The exact place of named items in each row's WHOLE list (cdae_hip_full_rank_rows): for every target of a second CSR over
+        the same rows (ascending unique items, none of them rated by its row; no cap per row), the number of items outside the row's
+        rated set that precede it in recommend_all's order, 0 the head of the list -> ranks uint32 [nnz_targets] in CSR order, or
+        (ranks, scores) with the fp32 scores the counting used."""
+        rp, rc, ru = self._rows(row_ptr, col, uids)
+        tp, tc, _ = self._rows(target_ptr, target_col, None)
+        if tp.size != rp.size:
+            raise ValueError("the target CSR covers the same rows")
+        n = rp.size - 1
+        total = max(int(tp[-1]), 0) if n else 0
+        ranks = np.empty(total, dtype=np.uint32)
+        scores = np.empty(total, dtype=np.float32) if with_scores else None
+        _chk(self.lib, self.lib.cdae_hip_full_rank_rows(self.h, n, None if ru is None else ru.ctypes.data, rp.ctypes.data, rc.ctypes.data,
+                                                        tp.ctypes.data, tc.ctypes.data, ranks.ctypes.data, scores.ctypes.data if with_scores else None))
+        return (ranks, scores) if with_scores else ranks
+
+    def eval_ranking_rows(self, row_ptr, col, target_ptr, target_col, uids=None, ks=(1, 5, 10, 20, 50, 100)):
+        """Full-catalogue ranking metrics of per-row target sets: full_rank_rows, then metrics.ranking_metrics over the ranks
+        (recall@k, precision@k, ndcg@k, map@k for every k of ks, mrr, auc: means over the rows with targets)."""
+        from .metrics import ranking_metrics
+        rp = np.ascontiguousarray(row_ptr, dtype=np.int64)
+        ranks = self.full_rank_rows(rp, col, target_ptr, target_col, uids)
+        return ranking_metrics(target_ptr, ranks, self.num_items - np.diff(rp), ks)
 
     def set_test_rows(self, test_ptr, test_col):
         """the validation rows TOPN_Evaluation scores against (evaluation.hpp:118-120), CSR over this handle's users"""

@@ -226,6 +226,12 @@ struct cdae_hip {
   uint2* d_cand_tiles = nullptr; size_t cand_tiles_cap = 0;
   float* d_cand_score = nullptr; size_t cand_score_cap = 0; uint32_t* d_cand_rank = nullptr; size_t cand_rank_cap = 0;
   std::vector<uint2> h_cand_tiles;      // host image of the tile table: alive until the call's last synchronisation
+  // cdae_hip_full_rank_rows: the target CSR, its bit rows for one chunk, the virtual-row table of the call, the target scores and
+  // ranks of one chunk (grow-only, freed with the handle)
+  int64_t* d_fr_tptr = nullptr; size_t fr_tptr_cap = 0; uint32_t* d_fr_tcol = nullptr; size_t fr_tcol_cap = 0;
+  uint32_t* d_fr_tbits = nullptr; size_t fr_tbits_cap = 0; uint2* d_fr_vrows = nullptr; size_t fr_vrows_cap = 0;
+  float* d_fr_tscore = nullptr; size_t fr_tscore_cap = 0; uint32_t* d_fr_rank = nullptr; size_t fr_rank_cap = 0;
+  std::vector<uint2> h_fr_vrows;        // host image of the virtual-row table: alive until the call's last synchronisation
   int sort_bits = 1;
   // prep worker: the ~12 launches that sample + sort a batch are issued by a second host thread (the training loop was bound by
   // the HOST's launch rate: ~21 runtime calls x 4.5 us per batch on one thread)
@@ -473,7 +479,8 @@ template <class F> int visit_device_ptrs(cdae_hip* h, F f) {
                      h->d_test_ptr, h->d_test_col, h->d_topn_pu, h->d_topn_out, h->d_bucket_cut, h->d_range_of,
                      h->d_Ghot, h->d_hotdup, h->d_late_bits, h->d_cold_map,
                      h->d_rows_ptr, h->d_rows_uid, h->d_rows_col, h->d_rows_tptr, h->d_rows_pu, h->d_rows_tcol, h->d_rows_out,
-                     h->d_cand_ptr, h->d_cand_col, h->d_cand_tiles, h->d_cand_score, h->d_cand_rank);
+                     h->d_cand_ptr, h->d_cand_col, h->d_cand_tiles, h->d_cand_score, h->d_cand_rank,
+                     h->d_fr_tptr, h->d_fr_tcol, h->d_fr_tbits, h->d_fr_vrows, h->d_fr_tscore, h->d_fr_rank);
 }
 
 void free_all(cdae_hip* h) {
@@ -516,6 +523,7 @@ int free_interaction_state(cdae_hip* h) {
   h->eval_cap = 0; h->eval_unit_cap = 0; h->bits_cap = 0;
   h->rows_ptr_cap = h->rows_uid_cap = h->rows_col_cap = h->rows_tptr_cap = h->rows_pu_cap = h->rows_tcol_cap = 0;
   h->cand_ptr_cap = h->cand_col_cap = h->cand_tiles_cap = h->cand_score_cap = h->cand_rank_cap = 0;
+  h->fr_tptr_cap = h->fr_tcol_cap = h->fr_tbits_cap = h->fr_vrows_cap = h->fr_tscore_cap = h->fr_rank_cap = 0;
   return 0;
 }
 
@@ -2925,6 +2933,128 @@ int score_run(cdae_hip* h, uint64_t R, const uint32_t* uids, const int64_t* row_
 }
 }  // namespace
 
+// ---- exact full-catalogue ranks of named items (cdae_hip_full_rank_rows) -----------------------------------------------------------
+namespace {
+// Chunks: real rows as for the other rows entry points (EVAL_CHUNK on the matrix cores, the Scorer's bounds on the general path), and
+// closed early once they hold FR_TARGET_CHUNK targets, which bounds the per-chunk score / rank buffers (one row may still name every
+// unrated item: a chunk always takes at least one row).  Matrix-core path: a row with n targets is ceil(n / FR_WINDOW) virtual rows in
+// the call's table, and one counting launch takes at most FR_COLS_MAX of them — a row with more is cut across launches that share its z.
+constexpr int64_t FR_TARGET_CHUNK = 1 << 22;
+constexpr uint32_t FR_COLS_MAX = EVAL_CHUNK;
+static_assert(EVAL_CHUNK <= 65536, "a virtual row names its row's slot in 16 bits");
+struct FrChunk { uint64_t c0; uint32_t nu; int64_t p0, p1; size_t v0, v1; };
+
+void full_rank_plan(uint64_t R, const int64_t* tp, uint32_t rows_max, bool mfma, std::vector<uint2>& vrows, std::vector<FrChunk>& chunks) {
+  vrows.clear(); chunks.clear();
+  uint64_t c0 = 0;
+  while (c0 < R) {
+    FrChunk c{c0, 0, tp[c0], tp[c0], vrows.size(), vrows.size()};
+    while (c.c0 + c.nu < R && c.nu < rows_max) {
+      const uint64_t r = c.c0 + c.nu;
+      const int64_t n = tp[r + 1] - tp[r];
+      if (c.nu && (c.p1 - c.p0) + n > FR_TARGET_CHUNK) break;
+      if (mfma)
+        for (int64_t w = 0; w < n; w += cdae::FR_WINDOW)
+          vrows.push_back(make_uint2(c.nu | (uint32_t)(std::min<int64_t>(cdae::FR_WINDOW, n - w) - 1) << 16, (uint32_t)(tp[r] + w - c.p0)));
+      c.p1 = tp[r + 1];
+      ++c.nu;
+    }
+    c.v1 = vrows.size();
+    chunks.push_back(c);
+    c0 += c.nu;
+  }
+}
+
+template <int NCH>
+int launch_full_rank_mfma_as(cdae_hip* h, const FrChunk& c, uint32_t words) {
+  const size_t lds = cdae::recommend_mfma_lds_bytes(NCH);
+  const float* D = (const float*)h->dec();
+  const float* bp = (const float*)h->P(CDAE_P_BP);
+  const uint32_t* tcol = h->d_fr_tcol + c.p0;
+  HIPCHK(hipFuncSetAttribute((const void*)cdae::full_rank_mfma_kernel<NCH, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  HIPCHK(hipFuncSetAttribute((const void*)cdae::full_rank_mfma_kernel<NCH, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  // pass 0: the scores of the targets, a column per row of the chunk
+  hipLaunchKernelGGL((cdae::full_rank_mfma_kernel<NCH, 0>), dim3((c.nu + cdae::REC_USERS_PER_BLOCK - 1) / cdae::REC_USERS_PER_BLOCK), dim3(256), lds,
+                     h->stream, h->hp, (const float*)h->d_zeval, c.nu, (const uint2*)nullptr, D, bp, (const uint32_t*)h->d_fr_tbits, words,
+                     (const int64_t*)h->d_fr_tptr, c.c0, c.p0, tcol, h->d_fr_tscore, (uint32_t*)nullptr);
+  // pass 1: the counts, a column per virtual row
+  for (size_t v = c.v0; v < c.v1; v += FR_COLS_MAX) {
+    const uint32_t ncol = (uint32_t)std::min<size_t>(FR_COLS_MAX, c.v1 - v);
+    hipLaunchKernelGGL((cdae::full_rank_mfma_kernel<NCH, 1>), dim3((ncol + cdae::REC_USERS_PER_BLOCK - 1) / cdae::REC_USERS_PER_BLOCK), dim3(256), lds,
+                       h->stream, h->hp, (const float*)h->d_zeval, ncol, (const uint2*)(h->d_fr_vrows + v), D, bp, (const uint32_t*)h->d_bits, words,
+                       (const int64_t*)nullptr, c.c0, c.p0, tcol, h->d_fr_tscore, h->d_fr_rank);
+  }
+  return 0;
+}
+int launch_full_rank_mfma(cdae_hip* h, const FrChunk& c, uint32_t words) {   // NCH by num_dim as launch_recommend_mfma_nch maps it
+  if (h->K <= 32) return launch_full_rank_mfma_as<4>(h, c, words);
+  if (h->K <= 64) return launch_full_rank_mfma_as<8>(h, c, words);
+  if (h->K <= 128) return launch_full_rank_mfma_as<16>(h, c, words);
+  if (h->K <= 200) return launch_full_rank_mfma_as<25>(h, c, words);
+  return launch_full_rank_mfma_as<32>(h, c, words);
+}
+
+int full_rank_run(cdae_hip* h, uint64_t R, const uint32_t* uids, const int64_t* row_ptr, const uint32_t* col, const int64_t* tp,
+                  const uint32_t* tc, uint32_t* out_ranks, float* out_scores) {
+  HIPCHK(hipSetDevice(h->device));
+  CHK(join_aux(h));
+  CHK(rows_upload(h, R, uids, row_ptr, col));
+  const bool mfma = h->K <= 256;
+  const uint32_t words = (uint32_t)((h->I + 31) / 32);
+  // general path: recommend_kernel's placement of a row's scores (Scorer::prepare)
+  const size_t lds_scores = (size_t)h->I * sizeof(float) + 64;
+  const bool in_lds = lds_scores <= 160 * 1024;
+  const size_t shmem = in_lds ? lds_scores : 64;
+  uint32_t rows_max = EVAL_CHUNK;
+  if (!mfma) rows_max = in_lds ? 4096u : (uint32_t)std::max<uint64_t>(1, (256ull << 20) / ((uint64_t)h->I * sizeof(float)));
+  std::vector<FrChunk> chunks;
+  full_rank_plan(R, tp, rows_max, mfma, h->h_fr_vrows, chunks);
+  size_t rows_cap = 0, targets_cap = 0;
+  for (const FrChunk& c : chunks)
+    if (c.p1 > c.p0) { rows_cap = std::max<size_t>(rows_cap, c.nu); targets_cap = std::max<size_t>(targets_cap, (size_t)(c.p1 - c.p0)); }
+  const size_t total = (size_t)tp[R];
+  CHK(ensure_cap(&h->d_fr_tptr, &h->fr_tptr_cap, R + 1));
+  CHK(ensure_cap(&h->d_fr_tcol, &h->fr_tcol_cap, total));
+  CHK(ensure_cap(&h->d_fr_tscore, &h->fr_tscore_cap, targets_cap));
+  CHK(ensure_cap(&h->d_fr_rank, &h->fr_rank_cap, targets_cap));
+  CHK(ensure_cap(&h->d_zeval, &h->eval_cap, rows_cap, h->Kp));
+  HIPCHK(hipMemcpyAsync(h->d_fr_tptr, tp, (R + 1) * sizeof(int64_t), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(hipMemcpyAsync(h->d_fr_tcol, tc, total * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
+  if (mfma) {
+    CHK(ensure_cap(&h->d_bits, &h->bits_cap, rows_cap * words));
+    CHK(ensure_cap(&h->d_fr_tbits, &h->fr_tbits_cap, rows_cap * words));
+    CHK(ensure_cap(&h->d_fr_vrows, &h->fr_vrows_cap, h->h_fr_vrows.size()));
+    HIPCHK(hipMemcpyAsync(h->d_fr_vrows, h->h_fr_vrows.data(), h->h_fr_vrows.size() * sizeof(uint2), hipMemcpyHostToDevice, h->stream));
+  } else {
+    if (!in_lds) CHK(ensure_cap(&h->d_score, &h->score_cap, rows_cap * h->I));
+    const void* kernel = h->NI == 1 ? (const void*)cdae::full_rank_general_kernel<1> : h->NI == 2 ? (const void*)cdae::full_rank_general_kernel<2>
+                       : h->NI == 4 ? (const void*)cdae::full_rank_general_kernel<4> : (const void*)cdae::full_rank_general_kernel<8>;
+    HIPCHK(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
+  }
+  for (const FrChunk& c : chunks) {
+    if (c.p1 == c.p0) continue;                                    // no row of the chunk has targets: nothing to launch, nothing to write
+    const size_t nt = (size_t)(c.p1 - c.p0);
+    CHK(rows_encode_chunk(h, row_ptr, c.c0, c.nu));
+    if (mfma) {
+      hipLaunchKernelGGL(cdae::rated_bits_kernel, dim3((c.nu + 3) / 4), dim3(256), 0, h->stream, (const int64_t*)h->d_rows_ptr,
+                         (const uint32_t*)h->d_rows_col, c.c0, c.nu, words, h->d_bits);
+      hipLaunchKernelGGL(cdae::rated_bits_kernel, dim3((c.nu + 3) / 4), dim3(256), 0, h->stream, (const int64_t*)h->d_fr_tptr,
+                         (const uint32_t*)h->d_fr_tcol, c.c0, c.nu, words, h->d_fr_tbits);
+      CHK(launch_full_rank_mfma(h, c, words));
+    } else {
+      DISPATCH_NI(h->NI, cdae::full_rank_general_kernel, dim3(c.nu), dim3(256), shmem, h->stream, h->hp, (const int64_t*)h->d_rows_ptr,
+                  (const uint32_t*)h->d_rows_col, (const int64_t*)h->d_fr_tptr, (const uint32_t*)h->d_fr_tcol, c.c0, c.p0, (const float*)h->d_zeval,
+                  (const float*)h->dec(), (const float*)h->P(CDAE_P_BP), in_lds ? (float*)nullptr : h->d_score, h->d_fr_tscore, h->d_fr_rank);
+    }
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(out_ranks + c.p0, h->d_fr_rank, nt * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+    if (out_scores) HIPCHK(hipMemcpyAsync(out_scores + c.p0, h->d_fr_tscore, nt * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));                                                 // one per chunk: the buffers are the next chunk's too
+  }
+  return 0;
+}
+}  // namespace
+
 extern "C" {
 
 int cdae_hip_score_rows(cdae_hip_t* h, uint64_t n_rows, const uint32_t* uids, const int64_t* row_ptr, const uint32_t* col,
@@ -2941,6 +3071,26 @@ int cdae_hip_score_rows(cdae_hip_t* h, uint64_t n_rows, const uint32_t* uids, co
         return fail("cdae_hip_score_rows: candidate row %llu has %lld candidates, ranks are computed for rows of at most %u", (unsigned long long)r,
                     (long long)(cand_row_ptr[r + 1] - cand_row_ptr[r]), CDAE_RANK_CANDIDATES_MAX);
   return score_run(h, n_rows, uids, row_ptr, col, cand_row_ptr, cand_col, out_scores, out_ranks);
+}
+
+int cdae_hip_full_rank_rows(cdae_hip_t* h, uint64_t n_rows, const uint32_t* uids, const int64_t* row_ptr, const uint32_t* col,
+                            const int64_t* target_row_ptr, const uint32_t* target_col, uint32_t* out_ranks, float* out_scores) {
+  const RowsArgs a{n_rows, uids, row_ptr, col, nullptr, nullptr, 0, 1, nullptr, nullptr};
+  CHK(rows_check(h, "cdae_hip_full_rank_rows", a));
+  if (n_rows == 0) return 0;
+  CHK(validate_rows_csr("target", target_row_ptr, target_col, n_rows, h->I));
+  if (target_row_ptr[n_rows] == 0) return 0;
+  if (!out_ranks) return fail("cdae_hip_full_rank_rows: null out_ranks with %lld targets", (long long)target_row_ptr[n_rows]);
+  for (uint64_t r = 0; r < n_rows; ++r) {                          // a rated item has no place in the list (both rows ascend: one merge walk)
+    int64_t p = row_ptr[r];
+    const int64_t pe = row_ptr[r + 1];
+    for (int64_t q = target_row_ptr[r]; q < target_row_ptr[r + 1] && p < pe; ++q) {
+      while (p < pe && col[p] < target_col[q]) ++p;
+      if (p < pe && col[p] == target_col[q])
+        return fail("cdae_hip_full_rank_rows: target row %llu names item %u, which is one of the row's rated items", (unsigned long long)r, target_col[q]);
+    }
+  }
+  return full_rank_run(h, n_rows, uids, row_ptr, col, target_row_ptr, target_col, out_ranks, out_scores);
 }
 
 int cdae_hip_recommend_rows(cdae_hip_t* h, uint64_t n_rows, const uint32_t* uids, const int64_t* row_ptr, const uint32_t* col,

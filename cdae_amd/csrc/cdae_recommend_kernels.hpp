@@ -508,4 +508,223 @@ topn_sum_kernel(const double* __restrict__ per_user, uint64_t num_users, double*
   out[c] = acc;
 }
 
+// ---- exact full-catalogue ranks of named items (cdae_hip_full_rank_rows) -----------------------------------------------------------
+// Where does a held-out item stand in a row's WHOLE list?  rank = the number of items outside the row's rated set that precede the
+// target in cdae_hip_recommend_all's total order (a strictly greater score, or an equal score and a lower item id).  The kernels below
+// COUNT where recommend_mfma_kernel / recommend_kernel keep a list, over the very same scores: two sweeps of the catalogue, the first
+// to learn the targets' scores, the second to count against them, both by the sweep arithmetic of the top-k kernel of the same
+// num_dim — so a target that recommend_rows lists at place j has rank j and the listed score, bit for bit.
+//
+// Matrix-core path (num_dim <= 256): full_rank_mfma_kernel<NCH, PASS> has recommend_mfma_kernel's shape — 256 threads and 128 columns
+// per workgroup, z of the column in bz[NCH], the decoder double-buffered through LDS in 32-item tiles with the 8 NCH + 4 row stride,
+// the same acc layout, the same b' float4 epilogue.  The tile loop, the MFMA chain and the epilogue are recommend_mfma_kernel's, copied
+// unchanged (that kernel is not edited, and nothing here emulates the chain in scalar code).
+//   PASS 0, target scores: a column is a row of the chunk.  A second bit table (rated_bits_kernel over the target CSR) tells the lane
+//     which of its 16 scores of a tile belong to targets; each such score goes to tscore[p], p found by a binary search in the row's
+//     target list (rare: once per target).  Targets are never rated (the host refuses such a call), so the rated bits are not read.
+//   PASS 1, counting: a column is a VIRTUAL row — a row's z slot and rated-bits row plus a window of at most FR_WINDOW of its targets
+//     (table built by the host: x = slot | (targets in the window - 1) << 16, y = offset of the window's first target from the chunk's
+//     first target).  A row with n targets is ceil(n / 16) virtual rows: there is no cap on targets.  A lane keeps the window as 16
+//     64-bit keys and 16 counters in registers.  key(s, item) = ordered(s) << 32 | ~item, ordered() the usual monotone map of fp32 to
+//     uint32 after s + 0.0f has turned -0 into +0: key(a) > key(b) exactly when a precedes b in the total order, so one 64-bit compare
+//     per (score, target) replaces (s > ts) | (s == ts & item < tid), and the target itself compares equal and adds nothing.  A masked
+//     or out-of-range item has key 0, the unused places of the last window the largest key: neither counts anything.  (NaN scores are
+//     unordered in the contract; here they sort by their bits.)  The two lane halves of a column add their counters through LDS at the
+//     end; lane half 0 stores the window's ranks.
+// LDS: at most recommend_mfma_lds_bytes (the counter scratch is 16 KiB).
+constexpr int FR_WINDOW = 16;
+static_assert(FR_WINDOW == REC_TOPK_MAX, "the counter scratch is laid out like the top-k merge scratch");
+
+__device__ __forceinline__ uint32_t fr_ordered(float s) {
+  const uint32_t b = __float_as_uint(s + 0.0f);
+  return b ^ ((uint32_t)((int32_t)b >> 31) | 0x80000000u);
+}
+__device__ __forceinline__ uint64_t fr_key(float s, uint32_t item) { return (uint64_t)fr_ordered(s) << 32 | (uint64_t)(~item); }
+
+template <int NCH, int PASS>
+__global__ void __launch_bounds__(256)
+full_rank_mfma_kernel(HyperParams hp, const float* __restrict__ Z /* [rows of the chunk x Kp] */, uint32_t ncol,
+                      const uint2* __restrict__ vrows /* PASS 1: the launch's virtual rows */, const float* __restrict__ D,
+                      const float* __restrict__ bp, const uint32_t* __restrict__ bits /* PASS 0: target bits; PASS 1: rated bits */,
+                      uint32_t words, const int64_t* __restrict__ tptr /* PASS 0: target row_ptr of the call */, uint64_t row0,
+                      int64_t p0 /* PASS 0: the chunk's first target */, const uint32_t* __restrict__ tcol /* the chunk's */,
+                      float* __restrict__ tscore /* the chunk's */, uint32_t* __restrict__ ranks /* PASS 1: the chunk's */) {
+  constexpr int KC = 8 * NCH;                     // contraction length (>= K; pad columns are zero in Z and D)
+  constexpr int ROW = KC + 4;                     // LDS row stride in floats
+  constexpr int TILE = 32;
+  extern __shared__ __attribute__((aligned(16))) char rec_smem[];   // max(2 tiles, counter scratch): recommend_mfma_lds_bytes
+  float (*tile)[TILE * ROW] = reinterpret_cast<float (*)[TILE * ROW]>(rec_smem);
+  const uint32_t lane = threadIdx.x % WAVE, wave = threadIdx.x / WAVE;
+  const uint32_t col_u = lane & 31u, half = lane >> 5;
+  const uint32_t column = blockIdx.x * REC_USERS_PER_BLOCK + wave * 32u + col_u;
+  const uint32_t column_ld = min(column, ncol - 1u);
+
+  uint32_t user_ld = column_ld;                   // the row's slot in Z and in the bit table
+  uint32_t win_n = 0, win_off = 0;
+  int64_t ta = 0, tb = 0;                         // PASS 0: the row's targets, positions in the chunk's
+  uint64_t tkey[FR_WINDOW];
+  uint32_t cnt[FR_WINDOW];
+  if constexpr (PASS == 1) {
+    const uint2 vr = vrows[column_ld];
+    user_ld = vr.x & 0xFFFFu; win_n = (vr.x >> 16) + 1u; win_off = vr.y;
+#pragma unroll
+    for (int j = 0; j < FR_WINDOW; ++j) {
+      const bool in = (uint32_t)j < win_n;
+      const uint32_t at = win_off + (in ? (uint32_t)j : 0u);
+      tkey[j] = in ? fr_key(tscore[at], tcol[at]) : ~0ull;
+      cnt[j] = 0u;
+    }
+  } else {
+    ta = tptr[row0 + column_ld] - p0; tb = tptr[row0 + column_ld + 1] - p0;
+  }
+
+  // B operand: this lane's row, elements 8c + 4 half .. + 3 of every chunk
+  float4 bz[NCH];
+#pragma unroll
+  for (int c = 0; c < NCH; ++c)
+    bz[c] = *reinterpret_cast<const float4*>(Z + (size_t)user_ld * hp.Kp + 8 * c + 4 * half);
+
+  const uint32_t n_tiles = (hp.num_items + TILE - 1) / TILE;
+  // cooperative tile load: TILE rows x (KC / 4) float4 = 8 NCH float4 per row; thread t takes float4 t, t + 256, ...
+  constexpr int F4_PER_ROW = KC / 4;
+  constexpr int F4_PER_TILE = TILE * F4_PER_ROW;
+  constexpr int F4_PER_THREAD = (F4_PER_TILE + 255) / 256;
+  float4 stage[F4_PER_THREAD];
+  auto fetch = [&](uint32_t t) {
+#pragma unroll
+    for (int q = 0; q < F4_PER_THREAD; ++q) {
+      const uint32_t f = threadIdx.x + 256u * q;
+      const uint32_t r = f / F4_PER_ROW, c4 = f % F4_PER_ROW;
+      const uint32_t item = min(t * TILE + r, hp.num_items - 1u);
+      stage[q] = f < (uint32_t)F4_PER_TILE ? *reinterpret_cast<const float4*>(D + (size_t)item * hp.Kp + 4 * c4)
+                                           : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+  };
+  auto commit = [&](int buf) {
+#pragma unroll
+    for (int q = 0; q < F4_PER_THREAD; ++q) {
+      const uint32_t f = threadIdx.x + 256u * q;
+      const uint32_t r = f / F4_PER_ROW, c4 = f % F4_PER_ROW;
+      if (f < (uint32_t)F4_PER_TILE) *reinterpret_cast<float4*>(&tile[buf][r * ROW + 4 * c4]) = stage[q];
+    }
+  };
+  fetch(0);
+  commit(0);
+  __syncthreads();
+
+  for (uint32_t t = 0; t < n_tiles; ++t) {
+    const int buf = (int)(t & 1u);
+    if (t + 1 < n_tiles) fetch(t + 1);                              // global loads of the next tile fly under the MFMAs
+    const uint32_t word = bits[(size_t)user_ld * words + t];        // PASS 0: the row's targets, PASS 1: its rated items, among the tile's 32
+    floatx16 acc;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+    const float* arow = &tile[buf][col_u * ROW + 4 * half];         // A operand: item row (lane & 31) of the tile
+#pragma unroll
+    for (int c = 0; c < NCH; ++c) {
+      const float4 a = *reinterpret_cast<const float4*>(arow + 8 * c);
+      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, bz[c].x, acc, 0, 0, 0);
+      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, bz[c].y, acc, 0, 0, 0);
+      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.z, bz[c].z, acc, 0, 0, 0);
+      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.w, bz[c].w, acc, 0, 0, 0);
+    }
+    // C[item][column]: lane holds items 8 (r / 4) + 4 half + (r % 4), r = 0..15, of column lane & 31
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const uint32_t i0 = t * TILE + 8u * q + 4u * half;
+      const float4 b4 = i0 + 3u < hp.num_items ? *reinterpret_cast<const float4*>(bp + i0)
+                                                : make_float4(i0 < hp.num_items ? bp[i0] : 0.f, i0 + 1u < hp.num_items ? bp[i0 + 1u] : 0.f,
+                                                              i0 + 2u < hp.num_items ? bp[i0 + 2u] : 0.f, 0.f);
+      const float bb[4] = {b4.x, b4.y, b4.z, b4.w};
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const uint32_t item = i0 + (uint32_t)e;
+        const float s = acc[4 * q + e] + bb[e];
+        const bool bit = (word >> (8u * q + 4u * half + (uint32_t)e)) & 1u;
+        if constexpr (PASS == 0) {
+          if (bit && column < ncol) {                               // (a set bit is an item below num_items)
+            int64_t lo = ta, hi = tb;                               // first position with tcol >= item: the target itself
+            while (lo < hi) { const int64_t mid = (lo + hi) >> 1; if (tcol[mid] < item) lo = mid + 1; else hi = mid; }
+            if (lo < tb) tscore[lo] = s;
+          }
+        } else {
+          const uint64_t key = item < hp.num_items && !bit ? fr_key(s, item) : 0ull;
+#pragma unroll
+          for (int j = 0; j < FR_WINDOW; ++j) cnt[j] += key > tkey[j] ? 1u : 0u;
+          if (e & 1) {                                               // pin the counters every two items: left alone, the compiler gathers
+            asm volatile("" : "+v"(cnt[0]), "+v"(cnt[1]), "+v"(cnt[2]), "+v"(cnt[3]), "+v"(cnt[4]), "+v"(cnt[5]), "+v"(cnt[6]), "+v"(cnt[7]));
+            asm volatile("" : "+v"(cnt[8]), "+v"(cnt[9]), "+v"(cnt[10]), "+v"(cnt[11]), "+v"(cnt[12]), "+v"(cnt[13]), "+v"(cnt[14]), "+v"(cnt[15]));
+          }                                                          // the tile's 256 compare masks first and spills SGPRs by the hundred
+        }
+      }
+    }
+    if (t + 1 < n_tiles) commit(buf ^ 1);
+    __syncthreads();
+  }
+
+  if constexpr (PASS == 1) {
+    // add the counters of the two lanes of every column
+    uint32_t* mc = reinterpret_cast<uint32_t*>(rec_smem);            // [4 waves][64 lanes][16]
+#pragma unroll
+    for (int j = 0; j < FR_WINDOW; ++j) mc[(wave * 64 + lane) * FR_WINDOW + j] = cnt[j];
+    __syncthreads();
+    if (half == 0 && column < ncol) {
+      const uint32_t* ca = mc + (wave * 64 + lane) * FR_WINDOW;
+      const uint32_t* cb = mc + (wave * 64 + lane + 32) * FR_WINDOW;
+      for (uint32_t j = 0; j < win_n; ++j) ranks[win_off + j] = ca[j] + cb[j];
+    }
+  }
+}
+
+// General path (num_dim > 256): recommend_kernel's front half — one workgroup per row of [r0, r0 + gridDim.x), the scores of all items
+// (fmaf chain over the lane's NI elements, wave_sum, + b') to LDS or to the row's workspace row, rated items set to -INFINITY — then
+// each wavefront takes targets of the row in turn: the target's own score is read from the array, the lanes stride over the array
+// counting its predecessors, and the counts are combined with __shfl_xor.  A row without targets leaves at once.
+template <int NI>
+__global__ void __launch_bounds__(256)
+full_rank_general_kernel(HyperParams hp, const int64_t* __restrict__ row_ptr, const uint32_t* __restrict__ col,
+                         const int64_t* __restrict__ tptr, const uint32_t* __restrict__ tcol /* the call's */, uint64_t r0,
+                         int64_t p0 /* the chunk's first target */, const float* __restrict__ Z, const float* __restrict__ D,
+                         const float* __restrict__ bp, float* __restrict__ score_ws /* [gridDim.x][num_items] or nullptr */,
+                         float* __restrict__ tscore /* the chunk's */, uint32_t* __restrict__ ranks /* the chunk's */) {
+  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+  const uint32_t slot = blockIdx.x;
+  float* score = score_ws ? score_ws + (size_t)slot * hp.num_items : reinterpret_cast<float*>(smem_raw + 64);
+  const uint64_t row = r0 + slot;
+  const int64_t ta = tptr[row], tb = tptr[row + 1];
+  if (ta == tb) return;                                            // (workgroup-uniform, before any barrier)
+  const uint32_t lane = threadIdx.x % WAVE, wid = threadIdx.x / WAVE, nw = blockDim.x / WAVE;
+  const uint32_t lo = lane * NI;
+  float z[NI];
+  vload<NI>(z, Z + (size_t)slot * hp.Kp + lo);
+  for (uint32_t item = wid; item < hp.num_items; item += nw) {
+    float d[NI];
+    vload<NI>(d, D + (size_t)item * hp.Kp + lo);
+    float dot = 0.f;
+#pragma unroll
+    for (int i = 0; i < NI; ++i) dot = fmaf(d[i], z[i], dot);
+    const float y = wave_sum(dot) + bp[item];
+    if (lane == 0) score[item] = y;
+  }
+  __syncthreads();
+  {
+    const int64_t a = row_ptr[row];
+    const uint32_t n = (uint32_t)(row_ptr[row + 1] - a);
+    for (uint32_t p = threadIdx.x; p < n; p += blockDim.x) score[col[a + p]] = -INFINITY;   // cdae.hpp:177-179
+  }
+  __syncthreads();
+  for (int64_t p = ta + wid; p < tb; p += nw) {                     // (wave-uniform)
+    const uint32_t tid = tcol[p];
+    const float ts = score[tid];
+    uint32_t before = 0;
+    for (uint32_t item = lane; item < hp.num_items; item += WAVE) {
+      const float v = score[item];
+      before += (v > ts || (v == ts && item < tid)) ? 1u : 0u;
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) before += __shfl_xor(before, off, WAVE);
+    if (lane == 0) { ranks[p - p0] = before; tscore[p - p0] = ts; }
+  }
+}
+
 }  // namespace cdae

@@ -25,6 +25,8 @@
  *   CDAE::recommend (all users, top-k)   cdae.hpp:162-196    cdae_hip_recommend_all
  *   CDAE::recommend (any rated sets)     cdae.hpp:162-196    cdae_hip_recommend_rows, cdae_hip_eval_topn_rows (batched),
  *                                                            cdae_hip_recommend_user (one user)
+ *   CDAE::recommend (place of named items in the whole list)
+ *                                        cdae.hpp:162-196    cdae_hip_full_rank_rows
  *   CDAE::get_output_values              cdae.hpp:418-426    cdae_hip_score_rows
  *   TOPN_Evaluation::evaluate            evaluation.hpp:113-181, evaluate_rec_list :183-219
  *                                                            cdae_hip_set_test_rows + cdae_hip_eval_topn
@@ -70,7 +72,9 @@ extern "C" {
  *     batched top-k and TOPN for rated sets the caller supplies
  *     added under 12 (no existing entry point or structure changed): cdae_hip_score_rows, CDAE_RANK_CANDIDATES_MAX — batched scores and
  *     ranks of candidate sets the caller supplies
- *     also under 12, the version unchanged (a test hook beside cdae_hip_debug_sample_batch; nothing existing changed): cdae_hip_debug_row_pack */
+ *     also under 12, the version unchanged (a test hook beside cdae_hip_debug_sample_batch; nothing existing changed): cdae_hip_debug_row_pack
+ *     also under 12, the version unchanged (a new entry point; nothing existing changed): cdae_hip_full_rank_rows — exact ranks of named
+ *     items in a row's whole list (full-catalogue Recall@k / NDCG@k / MRR / AUC without sampling) */
 #define CDAE_HIP_ABI_VERSION 12
 
 /* numeric values follow libcf::LossType (/root/reference/src/model/loss.hpp:10-18) */
@@ -384,6 +388,44 @@ int cdae_hip_eval_topn_rows(cdae_hip_t* h, uint64_t n_rows, const uint32_t* uids
 #define CDAE_RANK_CANDIDATES_MAX 4096u
 int cdae_hip_score_rows(cdae_hip_t* h, uint64_t n_rows, const uint32_t* uids, const int64_t* row_ptr, const uint32_t* col,
                         const int64_t* cand_row_ptr, const uint32_t* cand_col, float* out_scores, uint32_t* out_ranks);
+
+/* Where does a named item stand in a row's WHOLE list?  The exact rank of every target item among ALL items outside the row's rated
+ * set — what full-catalogue Recall@k / NDCG@k / MRR / AUC are computed from, for any k, without sampling candidates.
+ *   rows, uids, hidden, order of the input sum
+ *            exactly cdae_hip_recommend_rows's, validated alike and encoded by the same launches: the z of a row is bit for bit the
+ *            z cdae_hip_recommend_rows ranks from (CDAE_NO_USER, uids == NULL and corruption_ratio == 1 mean what they mean there).
+ *   targets  target_row_ptr[n_rows + 1] / target_col: a second host CSR over the same rows, items ascending and unique inside a row
+ *            (validated: an unsorted, duplicate or out-of-range target is an error that names the row); a row may be empty.  A target
+ *            that is one of its row's rated items is an error that names the row, raised before anything is launched: a rated item
+ *            has no place in the list.  There is no cap on the targets of a row: it may name every one of its unrated items.
+ *   out_ranks
+ *            [target_row_ptr[n_rows]], required when there is at least one target: out_ranks[p] = the number of items OUTSIDE the
+ *            row's rated set that precede target p in cdae_hip_recommend_all's total order — a strictly greater score, or an equal
+ *            score and a lower item id.  The row's other targets count like any other item.  0 is the head of the list: the rank is
+ *            the place the item takes in that row's cdae_hip_recommend_rows list of unbounded length.
+ *   out_scores
+ *            NULL or [target_row_ptr[n_rows]]: the fp32 score the counting used for the target.
+ *   which arithmetic (part of the contract)
+ *            Two sweeps over the catalogue: the first learns the targets' scores, the second counts against them; both compute every
+ *            score the way the top-k kernel of the same num_dim does, so ranks and scores agree by construction.
+ *            num_dim <= 256: the scores are the matrix-core top-k path's, bit for bit — the same contraction length per num_dim
+ *            (32 / 64 / 128 / 200 / 256 for num_dim <= 32 / 64 / 128 / 200 / 256), the same chain of v_mfma_f32_32x32x2_f32 over the
+ *            same operands in the same order, b' added last.  For every topk <= 16, an id that cdae_hip_recommend_rows lists at
+ *            place j, given as a target, gets rank j and the listed score, bit for bit.
+ *            num_dim > 256: the scores are the general path's (a fused multiply-add chain over the lane's elements, the wavefront
+ *            sum, b' added last), and the same holds for every topk.
+ *            (A score that is NaN has no place in the order; its rank is unspecified.)
+ *   position independence
+ *            a row's ranks and scores do not depend on what else the call holds, on its place in the call, or on the chunking.
+ * n_rows == 0 succeeds and touches nothing; rows without targets succeed and write nothing.
+ * Refused (the handle stays usable): IMF / BPR handles, item shards, calls before cdae_hip_set_interactions, a null out_ranks with
+ * targets present.
+ * The caller's arrays are copied into grow-only device buffers of the handle (freed with it): a steady-state call allocates nothing.
+ * Rows are taken in chunks of at most 32 768 (fewer once a chunk holds 4 194 304 targets) with one host synchronisation per chunk;
+ * on the matrix cores a row with n targets takes ceil(n / 16) columns of the counting launches, at most 32 768 columns per launch.
+ * Cost: two sweeps of the decoder per chunk plus 16 compares per (column, item). */
+int cdae_hip_full_rank_rows(cdae_hip_t* h, uint64_t n_rows, const uint32_t* uids, const int64_t* row_ptr, const uint32_t* col,
+                            const int64_t* target_row_ptr, const uint32_t* target_col, uint32_t* out_ranks, float* out_scores);
 
 /* ---- data-parallel exchange (north star: RCCL all-reduce of the shared W / W' / bias gradients;
  * Wu never leaves its GPU).  Each rank trains its own users from a common snapshot, then

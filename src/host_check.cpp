@@ -193,6 +193,18 @@ int main(int argc, char* argv[]) {
     }
     CHECK(std::isfinite(scores[n_train_rows].back())) << "a candidate inside the rated set must be scored";
     LOG(INFO) << "score_rows OK (" << scores.size() << " rows)";
+    // full_rank_rows(): the place of named items in each row's whole list.  The ids of every list above, handed over in REVERSE
+    // list order (the method sorts them and returns the ranks in the caller's order), must get rank == place.
+    std::vector<std::vector<size_t>> targets(lists);
+    for (auto& t : targets) std::reverse(t.begin(), t.end());
+    const std::vector<std::vector<size_t>> ranks = trained->full_rank_rows(row_uids, sets, targets);
+    CHECK_EQ(ranks.size(), lists.size());
+    for (size_t r = 0; r < lists.size(); ++r) {
+      CHECK_EQ(ranks[r].size(), lists[r].size());
+      for (size_t i = 0; i < lists[r].size(); ++i)
+        CHECK_EQ(ranks[r][i], lists[r].size() - 1 - i) << "full_rank_rows: row " << r << ", item " << targets[r][i];
+    }
+    LOG(INFO) << "full_rank_rows OK (" << ranks.size() << " rows)";
   }
   LOG(INFO) << "host layer OK";
   return 0;

@@ -334,6 +334,51 @@ class CDAE : public RecsysModelBase {
     return out;
   }
 
+  // The exact place of named items in each row's WHOLE list, in ONE device call (cdae_hip_full_rank_rows): row r is encoded from
+  // rated_sets[r] with the user node of uids[r] (kNoUser: none), exactly as recommend_rows() encodes it, and ranks[r][i] is the
+  // number of items outside rated_sets[r] that precede target_sets[r][i] in recommend()'s order — 0 is the head of the list, so an
+  // item recommend_rows() lists at place j has rank j.  Targets in the caller's order; duplicates and rated items refused.  What
+  // full-catalogue Recall@k / NDCG@k / MRR / AUC are computed from.  Single-handle models only; serialised on the handle's mutex.
+  std::vector<std::vector<size_t>> full_rank_rows(const std::vector<size_t>& uids, const std::vector<std::vector<size_t>>& rated_sets,
+                                                  const std::vector<std::vector<size_t>>& target_sets) const {
+    CHECK_EQ(uids.size(), rated_sets.size());
+    CHECK_EQ(target_sets.size(), rated_sets.size());
+    CHECK(!multi_) << "full_rank_rows() is provided for a model on one device";
+    const size_t n = rated_sets.size();
+    std::vector<uint32_t> u(n), col, tcol;
+    std::vector<int64_t> ptr(n + 1, 0), tptr(n + 1, 0);
+    std::vector<size_t> where;                                     // where[p]: the place in target_sets[r] of sorted position p
+    for (size_t r = 0; r < n; ++r) {
+      if (uids[r] != kNoUser) CHECK_LT(uids[r], num_users_);
+      u[r] = uids[r] == kNoUser ? CDAE_NO_USER : static_cast<uint32_t>(uids[r]);
+      const size_t at = col.size();
+      for (size_t i : rated_sets[r]) { CHECK_LT(i, num_items_); col.push_back(static_cast<uint32_t>(i)); }
+      std::sort(col.begin() + at, col.end());                    // the device CSR is ascending inside a row (duplicates: its error)
+      ptr[r + 1] = static_cast<int64_t>(col.size());
+      const std::vector<size_t>& tg = target_sets[r];
+      const size_t tat = where.size();
+      for (size_t i = 0; i < tg.size(); ++i) { CHECK_LT(tg[i], num_items_); where.push_back(i); }
+      std::sort(where.begin() + tat, where.end(), [&tg](size_t a, size_t b) { return tg[a] < tg[b]; });
+      for (size_t p = tat; p < where.size(); ++p) {
+        CHECK(p == tat || tg[where[p]] != tg[where[p - 1]]) << "target " << tg[where[p]] << " is listed twice in row " << r;
+        tcol.push_back(static_cast<uint32_t>(tg[where[p]]));
+      }
+      tptr[r + 1] = static_cast<int64_t>(tcol.size());
+    }
+    std::vector<uint32_t> rk(tcol.size());
+    {
+      std::lock_guard<std::mutex> lk(*mu_);
+      CHECK(ready()) << "reset() must be called first";
+      CDAE_HIP_CHECK(cdae_hip_full_rank_rows(dev_.get(), n, u.data(), ptr.data(), col.data(), tptr.data(), tcol.data(), rk.data(), nullptr));
+    }
+    std::vector<std::vector<size_t>> out(n);
+    for (size_t r = 0; r < n; ++r) {
+      out[r].resize(target_sets[r].size());
+      for (int64_t p = tptr[r]; p < tptr[r + 1]; ++p) out[r][where[p]] = rk[p];
+    }
+    return out;
+  }
+
   // recommend() for the user's own train row — what Evaluation asks for — without the caller building a hashtable
   // per user per epoch (evaluation.hpp:118-123): TOPN_Evaluation detects this method and uses it.
   std::vector<size_t> recommend_train_row(size_t uid, size_t topk) const {
