@@ -35,6 +35,15 @@ NO_USER = 0xFFFFFFFF           # CDAE_NO_USER (include/cdae_hip.h): a row of rec
 DEFAULT_BATCH_USERS = 0        # 0 = the library's default (cdae_hip_default_batch_users: num_users / 160, within [32, 256])
 
 
+def GUEST_USER(i):
+    """CDAE_GUEST_USER(i) (include/cdae_hip.h): the uid of node i of a handle's guest table; scalars and arrays alike -> uint32"""
+    i = np.asarray(i)
+    if i.size and (i.min() < 0 or i.max() > 0x7FFFFFFE):
+        raise ValueError("guest index out of range")
+    g = (i.astype(np.uint32) | np.uint32(0x80000000)).astype(np.uint32)
+    return g if g.ndim else np.uint32(g)
+
+
 class _Config(C.Structure):
     _fields_ = [(n, C.c_uint32) for n in (
         "struct_size", "num_dim", "num_neg", "num_corruptions", "loss_type", "using_adagrad",
@@ -100,6 +109,10 @@ EXPORTS = {
     "cdae_hip_full_rank_rows": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "cdae_hip_eval_topn_rows": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
                                           C.c_void_p, C.c_void_p, C.c_void_p]),
+    "cdae_hip_fold_in_rows": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint64,
+                                        C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "cdae_hip_set_guest_nodes": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "cdae_hip_guest_nodes": (C.c_uint64, [C.c_void_p]),
     "cdae_hip_set_test_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "cdae_hip_eval_topn": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "cdae_hip_stream": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
@@ -489,6 +502,43 @@ class CDAE:
         rp = np.ascontiguousarray(row_ptr, dtype=np.int64)
         ranks = self.full_rank_rows(rp, col, target_ptr, target_col, uids)
         return ranking_metrics(target_ptr, ranks, self.num_items - np.diff(rp), ks)
+
+    def fold_in_rows(self, row_ptr, col, uids=None, *, seed: int = 0, epoch_begin: int = 0, n_epochs: int = 10, stream_id_base: int = 0,
+                     install: bool = False, with_accumulators: bool = False):
+        """Fit the user node of many rows that are no train rows, everything shared frozen (cdae_hip_fold_in_rows): CSR rows with
+        ascending unique items; uids[r] the node row r starts from (a user: a copy of its rows; NO_USER / None: zeros and ones;
+        GUEST_USER(i): guest i).  Row r draws the masks and negatives of user id stream_id_base + r in epochs [epoch_begin,
+        epoch_begin + n_epochs).  install: the fitted nodes become the handle's guest table, row r as GUEST_USER(r).
+        -> wu [n_rows, num_dim] float32, or (wu, uu) under linear_function; with_accumulators: (wu, wu_ag), or (wu, wu_ag, uu, uu_ag)."""
+        rp, rc, ru = self._rows(row_ptr, col, uids)
+        n, K = rp.size - 1, self.cfg.num_dim
+        lf = bool(getattr(self.cfg, "linear_function", False))
+        wu = np.empty((n, K), dtype=np.float32)
+        wa = np.empty((n, K), dtype=np.float32) if with_accumulators else None
+        uu = np.empty((n, K), dtype=np.float32) if lf else None
+        ua = np.empty((n, K), dtype=np.float32) if lf and with_accumulators else None
+        _chk(self.lib, self.lib.cdae_hip_fold_in_rows(self.h, n, None if ru is None else ru.ctypes.data, rp.ctypes.data, rc.ctypes.data, seed,
+                                                      epoch_begin, n_epochs, stream_id_base, int(bool(install)),
+                                                      *[None if a is None else a.ctypes.data for a in (wu, wa, uu, ua)]))
+        out = tuple(a for a in (wu, wa, uu, ua) if a is not None)
+        return out[0] if len(out) == 1 else out
+
+    def set_guest_nodes(self, wu, wu_ag=None, uu=None, uu_ag=None):
+        """Replace the handle's guest table by host rows (cdae_hip_set_guest_nodes): wu [n, num_dim]; an array left None stands for
+        its "no node" value (accumulators 1e-4, uu ones).  n == 0 clears the table."""
+        arrs = [None if a is None else np.ascontiguousarray(a, dtype=np.float32) for a in (wu, wu_ag, uu, uu_ag)]
+        given = [a for a in arrs if a is not None]
+        if not given:
+            raise ValueError("set_guest_nodes needs at least one array (its rows are the table's size)")
+        n = given[0].shape[0] if given[0].ndim == 2 else 0
+        if any(a.shape != (n, self.cfg.num_dim) for a in given):
+            raise ValueError("guest node arrays are [n_guests, num_dim]")
+        _chk(self.lib, self.lib.cdae_hip_set_guest_nodes(self.h, n, *[None if a is None else a.ctypes.data for a in arrs]))
+
+    @property
+    def num_guest_nodes(self) -> int:
+        """rows of the handle's guest table (cdae_hip_guest_nodes)"""
+        return int(self.lib.cdae_hip_guest_nodes(self.h))
 
     def set_test_rows(self, test_ptr, test_col):
         """the validation rows TOPN_Evaluation scores against (evaluation.hpp:118-120), CSR over this handle's users"""

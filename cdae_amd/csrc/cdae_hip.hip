@@ -30,6 +30,7 @@
 #include "cdae_kernels.hpp"
 #include "cdae_full_kernels.hpp"
 #include "cdae_recommend_kernels.hpp"
+#include "cdae_foldin_kernels.hpp"
 #include "cdae_sort_kernels.hpp"
 #include "cdae_mf_kernels.hpp"
 
@@ -232,6 +233,15 @@ struct cdae_hip {
   uint32_t* d_fr_tbits = nullptr; size_t fr_tbits_cap = 0; uint2* d_fr_vrows = nullptr; size_t fr_vrows_cap = 0;
   float* d_fr_tscore = nullptr; size_t fr_tscore_cap = 0; uint32_t* d_fr_rank = nullptr; size_t fr_rank_cap = 0;
   std::vector<uint2> h_fr_vrows;        // host image of the virtual-row table: alive until the call's last synchronisation
+  // Guest table (cdae_hip_set_guest_nodes, cdae_hip_fold_in_rows with install): a second user table, rows wu | wu_ag | uu | uu_ag of
+  // [n_guests x Kp] each, that the rows entry points address as CDAE_GUEST_USER(i).  d_fold: the staging rows the fold-in kernel writes
+  // (a chunk's, or the whole call's when it installs); installing EXCHANGES the two sets, so a failed call leaves the table as it was.
+  // Grow-only, freed with the handle.  d_fold_long: the long rows' slots of every chunk of a call (cdae_foldin_kernels.hpp).
+  float* d_guest[4] = {nullptr, nullptr, nullptr, nullptr}; size_t guest_cap[4] = {0, 0, 0, 0}; uint64_t n_guests = 0;
+  float* d_fold[4] = {nullptr, nullptr, nullptr, nullptr}; size_t fold_cap[4] = {0, 0, 0, 0};
+  uint32_t* d_fold_long = nullptr; size_t fold_long_cap = 0;
+  std::vector<uint32_t> h_fold_long;    // host image of that list: alive until the call's last synchronisation
+  std::vector<size_t> h_fold_long_off;  // where every chunk's slots begin in it (kept here so that a steady-state call allocates no host memory either)
   int sort_bits = 1;
   // prep worker: the ~12 launches that sample + sort a batch are issued by a second host thread (the training loop was bound by
   // the HOST's launch rate: ~21 runtime calls x 4.5 us per batch on one thread)
@@ -480,7 +490,9 @@ template <class F> int visit_device_ptrs(cdae_hip* h, F f) {
                      h->d_Ghot, h->d_hotdup, h->d_late_bits, h->d_cold_map,
                      h->d_rows_ptr, h->d_rows_uid, h->d_rows_col, h->d_rows_tptr, h->d_rows_pu, h->d_rows_tcol, h->d_rows_out,
                      h->d_cand_ptr, h->d_cand_col, h->d_cand_tiles, h->d_cand_score, h->d_cand_rank,
-                     h->d_fr_tptr, h->d_fr_tcol, h->d_fr_tbits, h->d_fr_vrows, h->d_fr_tscore, h->d_fr_rank);
+                     h->d_fr_tptr, h->d_fr_tcol, h->d_fr_tbits, h->d_fr_vrows, h->d_fr_tscore, h->d_fr_rank,
+                     h->d_guest[0], h->d_guest[1], h->d_guest[2], h->d_guest[3], h->d_fold[0], h->d_fold[1], h->d_fold[2], h->d_fold[3],
+                     h->d_fold_long);
 }
 
 void free_all(cdae_hip* h) {
@@ -524,6 +536,8 @@ int free_interaction_state(cdae_hip* h) {
   h->rows_ptr_cap = h->rows_uid_cap = h->rows_col_cap = h->rows_tptr_cap = h->rows_pu_cap = h->rows_tcol_cap = 0;
   h->cand_ptr_cap = h->cand_col_cap = h->cand_tiles_cap = h->cand_score_cap = h->cand_rank_cap = 0;
   h->fr_tptr_cap = h->fr_tcol_cap = h->fr_tbits_cap = h->fr_vrows_cap = h->fr_tscore_cap = h->fr_rank_cap = 0;
+  for (int k = 0; k < 4; ++k) h->guest_cap[k] = h->fold_cap[k] = 0;
+  h->n_guests = 0; h->fold_long_cap = 0;
   return 0;
 }
 
@@ -2760,6 +2774,23 @@ int validate_rows_csr(const char* what, const int64_t* row_ptr, const uint32_t* 
     }
   return 0;
 }
+// uids[r]: CDAE_NO_USER, a local user, or — top bit set on a handle that can hold a guest table — a row of that table
+constexpr uint64_t GUEST_USERS_MAX = 0x7FFFFFFFull;     // with more users than this a user id may carry the top bit: no guest table
+int rows_check_uids(cdae_hip* h, const char* fn, const uint32_t* uids, uint64_t n_rows) {
+  if (!uids) return 0;
+  for (uint64_t r = 0; r < n_rows; ++r) {
+    const uint32_t u = uids[r];
+    if (u == cdae::ROW_NO_USER) continue;
+    if ((u & cdae::ROW_GUEST) && h->U <= GUEST_USERS_MAX) {
+      const uint32_t g = u & ~cdae::ROW_GUEST;
+      if (h->n_guests == 0) return fail("%s: row %llu names guest %u, but the handle has no guest table", fn, (unsigned long long)r, g);
+      if (g >= h->n_guests) return fail("%s: row %llu names guest %u of %llu", fn, (unsigned long long)r, g, (unsigned long long)h->n_guests);
+    } else if (u >= h->U) {
+      return fail("%s: row %llu names user %u of %llu", fn, (unsigned long long)r, u, (unsigned long long)h->U);
+    }
+  }
+  return 0;
+}
 int rows_check(cdae_hip* h, const char* fn, const RowsArgs& a) {
   if (!h) return fail("%s: null handle", fn);
   if (h->mf) return fail("%s does not apply to an IMF / BPR handle (its score does not depend on the rated set)", fn);
@@ -2768,10 +2799,7 @@ int rows_check(cdae_hip* h, const char* fn, const RowsArgs& a) {
   if (a.topk == 0 || a.topk > h->I) return fail("%s: topk must be in [1, num_items]", fn);
   if (a.n_rows == 0) return 0;
   CHK(validate_rows_csr("rated", a.row_ptr, a.col, a.n_rows, h->I));
-  if (a.uids)
-    for (uint64_t r = 0; r < a.n_rows; ++r)
-      if (a.uids[r] != cdae::ROW_NO_USER && a.uids[r] >= h->U) return fail("%s: row %llu names user %u of %llu", fn, (unsigned long long)r, a.uids[r], (unsigned long long)h->U);
-  return 0;
+  return rows_check_uids(h, fn, a.uids, a.n_rows);
 }
 // the part every rows entry point shares: the rated-set CSR and the uids to the handle's grow-only buffers (on h->stream) ...
 int rows_upload(cdae_hip* h, uint64_t R, const uint32_t* uids, const int64_t* row_ptr, const uint32_t* col) {
@@ -2789,16 +2817,18 @@ inline uint32_t rows_empty_input(const cdae_hip* h) { return h->hp.keep_thr == 0
 // ... and z of rows [c0, c0 + nu) of that CSR to h->d_zeval (nu rows of Kp floats, allocated by the caller)
 int rows_encode_chunk(cdae_hip* h, const int64_t* row_ptr, uint64_t c0, uint32_t nu) {
   const uint32_t empty_input = rows_empty_input(h);
+  const float* Gwu = h->n_guests ? h->d_guest[0] : nullptr;   // the guest table's Wu / Uu rows (uids with the top bit), if there is one
+  const float* Guu = h->n_guests ? h->d_guest[2] : nullptr;
   // rows of at most one summation group: a wavefront each; longer ones (if the chunk has any): a workgroup each
   bool any_long = false;
   for (uint64_t r = c0; r < c0 + nu && !any_long && !empty_input; ++r) any_long = row_ptr[r + 1] - row_ptr[r] > (int64_t)h->hp.unit_pos;
   DISPATCH_NI(h->NI, cdae::encode_rows_kernel, dim3((nu + cdae::ENC_ROWS_WAVES - 1) / cdae::ENC_ROWS_WAVES), dim3(cdae::ENC_ROWS_WAVES * cdae::WAVE),
               0, h->stream, h->hp, (const int64_t*)h->d_rows_ptr, (const uint32_t*)h->d_rows_col, (const uint32_t*)h->d_rows_uid, c0, nu, empty_input,
-              (const float*)h->P(CDAE_P_W), (const float*)h->d_Wu, (const float*)h->d_Uu, (const float*)h->P(CDAE_P_B), h->d_zeval);
+              (const float*)h->P(CDAE_P_W), (const float*)h->d_Wu, (const float*)h->d_Uu, (const float*)h->P(CDAE_P_B), h->d_zeval, Gwu, Guu);
   if (any_long)
     DISPATCH_NI(h->NI, cdae::encode_rows_long_kernel, dim3(nu), dim3(cdae::ENC_ROWS_WAVES * cdae::WAVE), 0, h->stream, h->hp,
                 (const int64_t*)h->d_rows_ptr, (const uint32_t*)h->d_rows_col, (const uint32_t*)h->d_rows_uid, c0, empty_input,
-                (const float*)h->P(CDAE_P_W), (const float*)h->d_Wu, (const float*)h->d_Uu, (const float*)h->P(CDAE_P_B), h->d_zeval);
+                (const float*)h->P(CDAE_P_W), (const float*)h->d_Wu, (const float*)h->d_Uu, (const float*)h->P(CDAE_P_B), h->d_zeval, Gwu, Guu);
   return 0;
 }
 int rows_run(cdae_hip* h, const RowsArgs& a) {
@@ -3054,6 +3084,130 @@ int full_rank_run(cdae_hip* h, uint64_t R, const uint32_t* uids, const int64_t* 
   return 0;
 }
 }  // namespace
+
+// ---- fold-in of user nodes for rows outside the training set (cdae_hip_fold_in_rows) and the guest table ------------------------------
+namespace {
+constexpr float NODE_INIT[4] = {0.f, cdae::FOLD_AG_INIT, 1.f, cdae::FOLD_AG_INIT};     // wu | wu_ag | uu | uu_ag of a row without a node
+int fold_check(cdae_hip* h, const char* fn) {
+  if (!h) return fail("%s: null handle", fn);
+  if (h->mf) return fail("%s does not apply to an IMF / BPR handle (its users are trained rows, not input nodes)", fn);
+  if (h->item_shard) return fail("%s applies to a whole model, not to an item shard", fn);
+  if (!h->d_shared) return fail("%s: cdae_hip_set_interactions first", fn);
+  if (h->cfg.full_output) return fail("%s: a full_output handle decodes densely; a dense fold-in is not implemented", fn);
+  if (!h->cfg.user_factor && !h->cfg.linear_function)
+    return fail("%s: the handle has neither user_factor nor linear_function: there is no user node to fit", fn);
+  return 0;
+}
+int guest_table_check(cdae_hip* h, const char* fn, uint64_t n) {
+  if (h->U > GUEST_USERS_MAX) return fail("%s: a handle with %llu users has no room for guest ids (at most %llu users)", fn, (unsigned long long)h->U, (unsigned long long)GUEST_USERS_MAX);
+  if (n > GUEST_USERS_MAX) return fail("%s: at most %llu guest nodes, got %llu", fn, (unsigned long long)GUEST_USERS_MAX, (unsigned long long)n);
+  return 0;
+}
+int ensure_nodes(cdae_hip* h, float* (&p)[4], size_t (&cap)[4], size_t rows) {
+  for (int k = 0; k < 4; ++k) CHK(ensure_cap(&p[k], &cap[k], rows, h->Kp));
+  return 0;
+}
+void install_staged(cdae_hip* h, uint64_t n) {       // the staging rows become the table (and the old table the next call's staging rows)
+  for (int k = 0; k < 4; ++k) { std::swap(h->d_guest[k], h->d_fold[k]); std::swap(h->guest_cap[k], h->fold_cap[k]); }
+  h->n_guests = n;
+}
+struct FoldCall {
+  uint64_t seed; uint32_t epoch_begin, n_epochs; uint64_t stream_id_base; bool install;
+  float* out[4];
+};
+int fold_run(cdae_hip* h, uint64_t R, const uint32_t* uids, const int64_t* row_ptr, const uint32_t* col, const FoldCall& f) {
+  HIPCHK(hipSetDevice(h->device));
+  CHK(join_aux(h));
+  CHK(rows_upload(h, R, uids, row_ptr, col));
+  const uint32_t UC = (uint32_t)std::min<uint64_t>(R, EVAL_CHUNK);
+  CHK(ensure_nodes(h, h->d_fold, h->fold_cap, f.install ? (size_t)R : (size_t)UC));
+  // the long rows of every chunk, as slots inside their chunk: they take the leading workgroups of the chunk's launch
+  std::vector<size_t>& long_off = h->h_fold_long_off;
+  long_off.clear();
+  h->h_fold_long.clear();
+  for (uint64_t c0 = 0; c0 < R; c0 += UC) {
+    long_off.push_back(h->h_fold_long.size());
+    for (uint64_t r = c0; r < std::min<uint64_t>(R, c0 + UC); ++r)
+      if (cdae::fold_row_is_long((uint64_t)(row_ptr[r + 1] - row_ptr[r]), h->hp.num_neg)) h->h_fold_long.push_back((uint32_t)(r - c0));
+  }
+  long_off.push_back(h->h_fold_long.size());
+  CHK(ensure_cap(&h->d_fold_long, &h->fold_long_cap, std::max<size_t>(h->h_fold_long.size(), 1)));
+  if (!h->h_fold_long.empty())
+    HIPCHK(hipMemcpyAsync(h->d_fold_long, h->h_fold_long.data(), h->h_fold_long.size() * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
+  const cdae::FoldArgs a{f.seed, f.stream_id_base, f.epoch_begin, f.n_epochs, h->cfg.num_corruptions};
+  const bool g = h->n_guests != 0;
+  const cdae::FoldNodes nd{h->d_Wu, h->d_Wu_ag, h->d_Uu, h->d_Uu_ag, g ? h->d_guest[0] : nullptr, g ? h->d_guest[1] : nullptr,
+                           g ? h->d_guest[2] : nullptr, g ? h->d_guest[3] : nullptr};
+  size_t chunk = 0;
+  for (uint64_t c0 = 0; c0 < R; c0 += UC, ++chunk) {
+    const uint32_t nu = (uint32_t)std::min<uint64_t>(UC, R - c0);
+    const uint32_t n_long = (uint32_t)(long_off[chunk + 1] - long_off[chunk]);
+    const size_t so = f.install ? (size_t)c0 * h->Kp : 0;          // an installing call keeps every chunk: the table changes after the last one
+    const cdae::FoldOut out{h->d_fold[0] + so, h->d_fold[1] + so, h->d_fold[2] + so, h->d_fold[3] + so};
+    DISPATCH_NI(h->NI, cdae::fold_in_rows_kernel, dim3(n_long + (nu + cdae::FOLD_WAVES - 1) / cdae::FOLD_WAVES), dim3(cdae::FOLD_WAVES * cdae::WAVE), 0,
+                h->stream, h->hp, a, (const int64_t*)h->d_rows_ptr, (const uint32_t*)h->d_rows_col, (const uint32_t*)h->d_rows_uid, c0, nu,
+                (const uint32_t*)(h->d_fold_long + long_off[chunk]), n_long, (const float*)h->P(CDAE_P_W), (const float*)h->dec(),
+                (const float*)h->P(CDAE_P_B), (const float*)h->P(CDAE_P_BP), nd, out);
+    HIPCHK(hipGetLastError());
+    const float* src[4] = {out.wu, out.wu_ag, out.uu, out.uu_ag};
+    for (int k = 0; k < 4; ++k)
+      if (f.out[k])
+        HIPCHK(hipMemcpy2DAsync(f.out[k] + (size_t)c0 * h->K, h->K * sizeof(float), src[k], h->Kp * sizeof(float), h->K * sizeof(float), nu,
+                                hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));                         // one per chunk: the staging rows are the next chunk's too
+  }
+  if (f.install) install_staged(h, R);
+  return 0;
+}
+}  // namespace
+
+extern "C" {
+
+int cdae_hip_fold_in_rows(cdae_hip_t* h, uint64_t n_rows, const uint32_t* uids, const int64_t* row_ptr, const uint32_t* col, uint64_t seed,
+                          uint32_t epoch_begin, uint32_t n_epochs, uint64_t stream_id_base, int install, float* out_wu, float* out_wu_ag,
+                          float* out_uu, float* out_uu_ag) {
+  const char* fn = "cdae_hip_fold_in_rows";
+  CHK(fold_check(h, fn));
+  if (install) CHK(guest_table_check(h, fn, n_rows));
+  if (n_rows == 0) {
+    if (install) h->n_guests = 0;
+    return 0;
+  }
+  CHK(validate_rows_csr("fold-in", row_ptr, col, n_rows, h->I));
+  CHK(rows_check_uids(h, fn, uids, n_rows));
+  for (uint64_t r = 0; r < n_rows; ++r)
+    if ((uint64_t)(row_ptr[r + 1] - row_ptr[r]) >= h->I)
+      return fail("%s: row %llu holds all %llu items: the negative sampler needs an unrated one", fn, (unsigned long long)r, (unsigned long long)h->I);
+  const FoldCall f{seed, epoch_begin, n_epochs, stream_id_base, install != 0, {out_wu, out_wu_ag, out_uu, out_uu_ag}};
+  return fold_run(h, n_rows, uids, row_ptr, col, f);
+}
+
+int cdae_hip_set_guest_nodes(cdae_hip_t* h, uint64_t n_guests, const float* wu, const float* wu_ag, const float* uu, const float* uu_ag) {
+  const char* fn = "cdae_hip_set_guest_nodes";
+  CHK(fold_check(h, fn));
+  CHK(guest_table_check(h, fn, n_guests));
+  if (n_guests == 0) { h->n_guests = 0; return 0; }
+  HIPCHK(hipSetDevice(h->device));
+  CHK(join_aux(h));
+  CHK(ensure_nodes(h, h->d_fold, h->fold_cap, (size_t)n_guests));
+  const float* host[4] = {wu, wu_ag, uu, uu_ag};
+  const size_t count = (size_t)n_guests * h->Kp;
+  for (int k = 0; k < 4; ++k) {
+    hipLaunchKernelGGL(cdae::fold_fill_kernel, dim3((uint32_t)std::min<size_t>((count + 255) / 256, 4096)), dim3(256), 0, h->stream, h->d_fold[k], count,
+                       NODE_INIT[k]);
+    HIPCHK(hipGetLastError());
+    if (host[k])
+      HIPCHK(hipMemcpy2DAsync(h->d_fold[k], h->Kp * sizeof(float), host[k], h->K * sizeof(float), h->K * sizeof(float), n_guests,
+                              hipMemcpyHostToDevice, h->stream));
+  }
+  HIPCHK(hipStreamSynchronize(h->stream));
+  install_staged(h, n_guests);
+  return 0;
+}
+
+uint64_t cdae_hip_guest_nodes(const cdae_hip_t* h) { return h ? h->n_guests : 0; }
+
+}  // extern "C"
 
 extern "C" {
 

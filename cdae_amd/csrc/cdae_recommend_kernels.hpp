@@ -121,16 +121,23 @@ __device__ __forceinline__ void enc_rows_group_sum(const HyperParams& hp, const 
   }
 }
 
-// one wavefront: what the finish of a row needs — b, and the user's private rows (zeros / ones for a row without a user node)
+// one wavefront: what the finish of a row needs — b, and the user's private rows (zeros / ones for a row without a user node).  A uid
+// with ROW_GUEST set names a row of the handle's guest table (cdae_hip_set_guest_nodes, cdae_hip_fold_in_rows) when there is one
+// (Gwu != nullptr; the host has checked the index): only the base pointer and the index change, so every uid without the bit loads
+// what it always did.
+constexpr uint32_t ROW_GUEST = 0x80000000u;
 template <int NI>
 __device__ __forceinline__ void enc_rows_user(const HyperParams& hp, uint32_t uid, const float* __restrict__ Wu, const float* __restrict__ Uu,
+                                              const float* __restrict__ Gwu, const float* __restrict__ Guu,
                                               const float* __restrict__ b, uint32_t lane, float (&bb)[NI], float (&wu)[NI], float (&uu)[NI]) {
   const uint32_t lo = lane * NI;
 #pragma unroll
   for (int i = 0; i < NI; ++i) { wu[i] = 0.f; uu[i] = 1.f; }
   vload<NI>(bb, b + lo);
-  if (hp.user_factor && uid != ROW_NO_USER) vload<NI>(wu, Wu + (size_t)uid * hp.Kp + lo);
-  if (hp.linear_function && uid != ROW_NO_USER) vload<NI>(uu, Uu + (size_t)uid * hp.Kp + lo);
+  const bool guest = Gwu != nullptr && (uid & ROW_GUEST) != 0u;      // (wave-uniform)
+  const size_t o = (size_t)(guest ? uid & ~ROW_GUEST : uid) * hp.Kp + lo;
+  if (hp.user_factor && uid != ROW_NO_USER) vload<NI>(wu, (guest ? Gwu : Wu) + o);
+  if (hp.linear_function && uid != ROW_NO_USER) vload<NI>(uu, (guest ? Guu : Uu) + o);
 }
 
 // one wavefront: z = act(acc (.) uu + b + wu) to zrow, pad elements 0
@@ -157,7 +164,8 @@ __global__ void __launch_bounds__(ENC_ROWS_WAVES * WAVE)
 encode_rows_kernel(HyperParams hp, const int64_t* __restrict__ row_ptr, const uint32_t* __restrict__ col,
                    const uint32_t* __restrict__ uids, uint64_t r0, uint32_t nu, uint32_t empty_input, const float* __restrict__ W,
                    const float* __restrict__ Wu, const float* __restrict__ Uu, const float* __restrict__ b,
-                   float* __restrict__ Z /* [nu][Kp] */) {
+                   float* __restrict__ Z /* [nu][Kp] */, const float* __restrict__ Gwu /* the guest table's rows, or nullptr */,
+                   const float* __restrict__ Guu) {
 #pragma clang fp contract(off)
   const uint32_t wid = threadIdx.x / WAVE, lane = threadIdx.x % WAVE;
   const uint32_t slot = blockIdx.x * ENC_ROWS_WAVES + wid;
@@ -167,7 +175,7 @@ encode_rows_kernel(HyperParams hp, const int64_t* __restrict__ row_ptr, const ui
   const uint32_t n = empty_input ? 0u : (uint32_t)(row_ptr[row + 1] - p0);
   if (n > hp.unit_pos) return;                                     // encode_rows_long_kernel's
   float bb[NI], wu[NI], uu[NI], acc[NI], ua[NI];
-  enc_rows_user<NI>(hp, uids[row], Wu, Uu, b, lane, bb, wu, uu);  // requested before the sum
+  enc_rows_user<NI>(hp, uids[row], Wu, Uu, Gwu, Guu, b, lane, bb, wu, uu);  // requested before the sum
 #pragma unroll
   for (int i = 0; i < NI; ++i) acc[i] = 0.f;
   if (n) {
@@ -184,7 +192,8 @@ __global__ void __launch_bounds__(ENC_ROWS_WAVES * WAVE)
 encode_rows_long_kernel(HyperParams hp, const int64_t* __restrict__ row_ptr, const uint32_t* __restrict__ col,
                         const uint32_t* __restrict__ uids, uint64_t r0, uint32_t empty_input, const float* __restrict__ W,
                         const float* __restrict__ Wu, const float* __restrict__ Uu, const float* __restrict__ b,
-                        float* __restrict__ Z /* [gridDim.x][Kp] */) {
+                        float* __restrict__ Z /* [gridDim.x][Kp] */, const float* __restrict__ Gwu /* the guest table's rows, or nullptr */,
+                        const float* __restrict__ Guu) {
 #pragma clang fp contract(off)
   __shared__ float part[ENC_ROWS_WAVES][64 * NI];
   const uint32_t slot = blockIdx.x, wid = threadIdx.x / WAVE, lane = threadIdx.x % WAVE;
@@ -198,7 +207,7 @@ encode_rows_long_kernel(HyperParams hp, const int64_t* __restrict__ row_ptr, con
   float bb[NI], wu[NI], uu[NI], acc[NI];
 #pragma unroll
   for (int i = 0; i < NI; ++i) acc[i] = 0.f;
-  if (wid == 0) enc_rows_user<NI>(hp, uids[row], Wu, Uu, b, lane, bb, wu, uu);   // requested before the sums
+  if (wid == 0) enc_rows_user<NI>(hp, uids[row], Wu, Uu, Gwu, Guu, b, lane, bb, wu, uu);   // requested before the sums
   for (uint32_t g0 = 0; g0 < n_groups; g0 += ENC_ROWS_WAVES) {     // (workgroup-uniform trip count)
     const uint32_t g = g0 + wid;
     if (g < n_groups) {

@@ -19,6 +19,8 @@
  *     sample_negative_item               recsys_model_base.hpp:46-57  (device, include/cdae_rng.h)
  *     train_one_user_corruption          cdae.hpp:198-358      (device kernels; explicit-input form:
  *                                                           cdae_hip_train_one_user_corruption)
+ *     train_one_user_corruption with the shared parameters frozen
+ *                                        cdae.hpp:198-358    cdae_hip_fold_in_rows
  *   CDAE::get_hidden_values              cdae.hpp:373-416    cdae_hip_encode
  *   CDAE::data_loss                      cdae.hpp:78-101     cdae_hip_data_loss
  *   CDAE::penalty_loss                   cdae.hpp:103-107    cdae_hip_penalty_loss
@@ -74,7 +76,10 @@ extern "C" {
  *     ranks of candidate sets the caller supplies
  *     also under 12, the version unchanged (a test hook beside cdae_hip_debug_sample_batch; nothing existing changed): cdae_hip_debug_row_pack
  *     also under 12, the version unchanged (a new entry point; nothing existing changed): cdae_hip_full_rank_rows — exact ranks of named
- *     items in a row's whole list (full-catalogue Recall@k / NDCG@k / MRR / AUC without sampling) */
+ *     items in a row's whole list (full-catalogue Recall@k / NDCG@k / MRR / AUC without sampling)
+ *     also under 12, the version unchanged (new entry points; nothing existing changed): cdae_hip_fold_in_rows, cdae_hip_set_guest_nodes,
+ *     cdae_hip_guest_nodes, CDAE_GUEST_USER — batched fold-in of user nodes for rows outside the training set, and a guest table that serves the fitted nodes
+ *     to the rows entry points */
 #define CDAE_HIP_ABI_VERSION 12
 
 /* numeric values follow libcf::LossType (/root/reference/src/model/loss.hpp:10-18) */
@@ -323,7 +328,9 @@ int cdae_hip_recommend_user(cdae_hip_t* h, uint64_t uid, const uint32_t* rated_i
  *            (cdae_hip_eval_topn_rows with n_rows == 0 has no row with targets: its error below).
  *   uids     uids[r] = the local user whose Wu row (and Uu row under linear_function) row r takes; any user any number of times.
  *            CDAE_NO_USER: the row has no user node — a Wu row of zeros that is still added and a Uu row of ones, i.e. the arithmetic
- *            of a real user with those rows.  uids == NULL: every row is CDAE_NO_USER.  Any other id >= num_users is an error.
+ *            of a real user with those rows.  uids == NULL: every row is CDAE_NO_USER.  CDAE_GUEST_USER(i): node i of the handle's guest
+ *            table (below: cdae_hip_set_guest_nodes, cdae_hip_fold_in_rows) — an error when i is at or beyond the table's size or no
+ *            table is set.  Any other id >= num_users is an error.
  *   hidden   get_hidden_values(uid, rated_set) with scale 1 (cdae.hpp:169, :373-416): z = act(sum_{k in row} W[k] (.) Uu[uid] + b + Wu[uid]);
  *            corruption_ratio == 1 encodes the empty input (:168-172) and still excludes the row.
  *   order    of the input sum (part of the contract): the one cdae_hip_encode(mode 0) takes for a train row — groups of `unit`
@@ -426,6 +433,63 @@ int cdae_hip_score_rows(cdae_hip_t* h, uint64_t n_rows, const uint32_t* uids, co
  * Cost: two sweeps of the decoder per chunk plus 16 compares per (column, item). */
 int cdae_hip_full_rank_rows(cdae_hip_t* h, uint64_t n_rows, const uint32_t* uids, const int64_t* row_ptr, const uint32_t* col,
                             const int64_t* target_row_ptr, const uint32_t* target_col, uint32_t* out_ranks, float* out_scores);
+
+/* Fold-in: fit the user node of MANY rows that are no train rows, with everything shared frozen — the strong-generalisation protocol
+ * (train on some users; for an unseen user fit only their own node on part of their history, rank the rest), and the warm re-fit of a
+ * user whose session changed.  This is train_one_user_corruption (cdae.hpp:198-358) with every update of a shared parameter removed:
+ * W, V, b and b' are read, never written; all that moves is the row's own (wu, wu_ag) and, under linear_function, (uu, uu_ag).
+ *   rows     row_ptr[n_rows + 1] / col: a host CSR as for cdae_hip_recommend_rows (items ascending and unique inside a row, validated alike:
+ *            the error names the row); a row may be empty.  A row that holds all num_items items is an error that names the row, raised
+ *            before anything is launched: the negative sampler needs an unrated item.
+ *   start    the node row r starts from, chosen by uids[r] exactly as the rows entry points choose a row's node:
+ *              a local user              copies of that user's Wu / Wu_ag / Uu / Uu_ag rows (the handle's own rows are not written);
+ *              CDAE_NO_USER, uids NULL   wu = 0, uu = 1, both accumulators 1e-4 (reset()'s values, cdae.hpp:109-134);
+ *              CDAE_GUEST_USER(i)        node i of the guest table (continue an earlier fit).
+ *   stream   s = stream_id_base + r takes the place of the global user id in cdae_rng_key (include/cdae_rng.h).
+ *   loop     with R the row's items, n = |R|, m = n num_neg: for e = epoch_begin .. epoch_begin + n_epochs - 1, and inside it for
+ *            c = 0 .. num_corruptions - 1:
+ *              kept  = the R[pos] with cdae_keep(cdae_rng_draw(key(seed, e, s, CDAE_STREAM_CORRUPT), c n + pos), thr);
+ *              S     = sum_{j in kept} W[j], unscaled;
+ *              h     = scale S ((.) uu under linear_function) + b (+ wu under user_factor);  z = act(h) with the reference's clamps,
+ *                      z' = act'(z) (cdae.hpp:208-215);
+ *              N_i   = cdae_sample_negative(key(seed, e, s, CDAE_STREAM_NEGATIVE), c m + i, R, n, num_items) for i < m: the draws
+ *                      training makes for a user with id s and that row;
+ *              hg    = sum_{j in R} loss'(D[j].z + b'[j], 1) D[j] + sum_i loss'(D[N_i].z + b'[N_i], 0) D[N_i], D = V when asymmetric,
+ *                      else W; every term from the frozen rows, a duplicate negative counted once per occurrence;
+ *              delta = hg (.) z';
+ *              user_factor:      one AdaGrad (or SGD) step of (wu, wu_ag) with gradient delta + lambda wu (cdae.hpp:317-331);
+ *              linear_function:  one step of (uu, uu_ag) with gradient lambda uu + delta (.) S, S unscaled as in the reference
+ *                                (cdae.hpp:295-299, :340, :351-357);
+ *              both gradients formed from the values before either step.
+ *            An empty row takes no step and returns its start node; n_epochs == 0 returns the start nodes.
+ *   contract the handle's parameters are not written.  A row's result is a function of (its items, its start node, s, seed, the epoch
+ *            range, the frozen parameters) only: the same bits whatever else the call holds, wherever the row sits, however the call is
+ *            chunked, and on every repeat (a fixed summation order, no atomics).  No particular order is promised beyond that.
+ *   out      out_wu / out_wu_ag / out_uu / out_uu_ag: each NULL or [n_rows x num_dim] on the host.  Without linear_function out_uu /
+ *            out_uu_ag are written with ones / 1e-4; without user_factor out_wu / out_wu_ag with zeros / 1e-4.
+ *   install  != 0: after the WHOLE call has succeeded the guest table is exactly the n_rows fitted nodes, row r as guest r — on the
+ *            device, nothing crosses PCIe for it, and only then: a row may start from the guest slot another row of the same call
+ *            replaces.  On any error the table is as it was.  (The library keeps an installing call's fitted rows in a second set of
+ *            arrays and EXCHANGES that set with the table at the end instead of copying into it: such a call holds n_rows staged
+ *            rows, not one chunk's, and the two sets reach their steady sizes after two installing calls of a given size.)
+ * n_rows == 0 succeeds and touches nothing, except that with install it clears the table.
+ * Refused (the handle stays usable): IMF / BPR handles, item shards, calls before cdae_hip_set_interactions, full_output handles (their
+ * decode is dense; a dense fold-in is not implemented), a handle with neither user_factor nor linear_function (nothing to fit).
+ * The caller's arrays are copied into grow-only device buffers of the handle (freed with it): a steady-state call allocates nothing.
+ * Rows are taken in chunks of at most 32 768, ONE launch per chunk for all its epochs, one host synchronisation per chunk.
+ *
+ * The guest table: a second user table the handle owns — four device arrays [n_guests x row stride] (wu, wu_ag, uu, uu_ag), grow-only,
+ * freed with the handle, dropped by cdae_hip_set_interactions.  cdae_hip_recommend_rows, cdae_hip_eval_topn_rows, cdae_hip_score_rows,
+ * cdae_hip_full_rank_rows and cdae_hip_fold_in_rows resolve uids[r] = CDAE_GUEST_USER(i) to guest i.  cdae_hip_set_guest_nodes replaces
+ * the table by n_guests host rows ([n_guests x num_dim] each; a NULL array stands for zeros / 1e-4 / ones / 1e-4); n_guests == 0 clears
+ * it.  cdae_hip_guest_nodes: its size.  A handle with more than 0x7FFFFFFF users refuses a table (its user ids need the top bit), and
+ * the refusals of cdae_hip_fold_in_rows apply. */
+#define CDAE_GUEST_USER(i) (0x80000000u | (uint32_t)(i))
+int cdae_hip_fold_in_rows(cdae_hip_t* h, uint64_t n_rows, const uint32_t* uids, const int64_t* row_ptr, const uint32_t* col,
+                          uint64_t seed, uint32_t epoch_begin, uint32_t n_epochs, uint64_t stream_id_base, int install,
+                          float* out_wu, float* out_wu_ag, float* out_uu, float* out_uu_ag);
+int cdae_hip_set_guest_nodes(cdae_hip_t* h, uint64_t n_guests, const float* wu, const float* wu_ag, const float* uu, const float* uu_ag);
+uint64_t cdae_hip_guest_nodes(const cdae_hip_t* h);
 
 /* ---- data-parallel exchange (north star: RCCL all-reduce of the shared W / W' / bias gradients;
  * Wu never leaves its GPU).  Each rank trains its own users from a common snapshot, then
