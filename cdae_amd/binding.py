@@ -105,6 +105,8 @@ EXPORTS = {
     "cdae_hip_recommend_all": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint32, C.c_void_p]),
     "cdae_hip_recommend_user": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p]),
     "cdae_hip_recommend_rows": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "cdae_hip_recommend_rows_filtered": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                                   C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p]),
     "cdae_hip_score_rows": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "cdae_hip_full_rank_rows": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "cdae_hip_eval_topn_rows": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
@@ -444,6 +446,32 @@ class CDAE:
         scores = np.empty((n, topk), dtype=np.float32) if with_scores else None
         _chk(self.lib, self.lib.cdae_hip_recommend_rows(self.h, n, None if ru is None else ru.ctypes.data, rp.ctypes.data, rc.ctypes.data,
                                                         topk, ids.ctypes.data, scores.ctypes.data if with_scores else None))
+        return (ids, scores) if with_scores else ids
+
+    def recommend_rows_filtered(self, row_ptr, col, uids=None, topk: int = 10, exclude=None, allow=None, exclude_rated: bool = True,
+                                with_scores: bool = False):
+        """recommend_rows with the excluded set cut loose from the input set (cdae_hip_recommend_rows_filtered).  exclude: a
+        (ptr, col) CSR over the same rows of items that must not be listed but do not enter z (None: none); allow: ONE ascending
+        unique item list for the whole call, the only items that may be listed (None: the whole catalogue); exclude_rated=False:
+        a row's own items are candidates too.  Row r's list is recommend_rows' unbounded list with the items outside
+        allow minus exclude[r] (minus rated[r]) deleted, the same fp32 scores -> ids [n_rows, topk] uint32 of original item ids
+        (0xFFFFFFFF beyond a row's candidates), or (ids, scores)."""
+        rp, rc, ru = self._rows(row_ptr, col, uids)
+        n = rp.size - 1
+        ep = ec = None
+        if exclude is not None:
+            ep, ec, _ = self._rows(exclude[0], exclude[1], None)
+            if ep.size != rp.size:
+                raise ValueError("the exclude CSR covers the same rows")
+        al = None if allow is None else np.ascontiguousarray(allow, dtype=np.uint32).reshape(-1)
+        al_buf = al if al is None or al.size else np.zeros(1, dtype=np.uint32)      # an empty list is still a list: the library refuses it
+        ids = np.empty((n, topk), dtype=np.uint32)
+        scores = np.empty((n, topk), dtype=np.float32) if with_scores else None
+        _chk(self.lib, self.lib.cdae_hip_recommend_rows_filtered(
+            self.h, n, None if ru is None else ru.ctypes.data, rp.ctypes.data, rc.ctypes.data,
+            None if ep is None else ep.ctypes.data, None if ep is None else ec.ctypes.data, 1 if exclude_rated else 0,
+            None if al is None else al_buf.ctypes.data, 0 if al is None else al.size, topk, ids.ctypes.data,
+            scores.ctypes.data if with_scores else None))
         return (ids, scores) if with_scores else ids
 
     def eval_topn_rows(self, row_ptr, col, target_ptr, target_col, uids=None, topk: int = 10, with_ids: bool = False):

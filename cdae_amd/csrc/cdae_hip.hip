@@ -233,6 +233,11 @@ struct cdae_hip {
   uint32_t* d_fr_tbits = nullptr; size_t fr_tbits_cap = 0; uint2* d_fr_vrows = nullptr; size_t fr_vrows_cap = 0;
   float* d_fr_tscore = nullptr; size_t fr_tscore_cap = 0; uint32_t* d_fr_rank = nullptr; size_t fr_rank_cap = 0;
   std::vector<uint2> h_fr_vrows;        // host image of the virtual-row table: alive until the call's last synchronisation
+  // cdae_hip_recommend_rows_filtered: the excl CSR, the allow list, its inverse (item -> place, [num_items]) and the packed copy of the
+  // allowed decoder rows and of their b' (rebuilt by every call that has an allow list); grow-only, freed with the handle
+  int64_t* d_flt_eptr = nullptr; size_t flt_eptr_cap = 0; uint32_t* d_flt_ecol = nullptr; size_t flt_ecol_cap = 0;
+  uint32_t* d_flt_allow = nullptr; size_t flt_allow_cap = 0; uint32_t* d_flt_pos = nullptr; size_t flt_pos_cap = 0;
+  float* d_flt_D = nullptr; size_t flt_D_cap = 0; float* d_flt_bp = nullptr; size_t flt_bp_cap = 0;
   // Guest table (cdae_hip_set_guest_nodes, cdae_hip_fold_in_rows with install): a second user table, rows wu | wu_ag | uu | uu_ag of
   // [n_guests x Kp] each, that the rows entry points address as CDAE_GUEST_USER(i).  d_fold: the staging rows the fold-in kernel writes
   // (a chunk's, or the whole call's when it installs); installing EXCHANGES the two sets, so a failed call leaves the table as it was.
@@ -491,6 +496,7 @@ template <class F> int visit_device_ptrs(cdae_hip* h, F f) {
                      h->d_rows_ptr, h->d_rows_uid, h->d_rows_col, h->d_rows_tptr, h->d_rows_pu, h->d_rows_tcol, h->d_rows_out,
                      h->d_cand_ptr, h->d_cand_col, h->d_cand_tiles, h->d_cand_score, h->d_cand_rank,
                      h->d_fr_tptr, h->d_fr_tcol, h->d_fr_tbits, h->d_fr_vrows, h->d_fr_tscore, h->d_fr_rank,
+                     h->d_flt_eptr, h->d_flt_ecol, h->d_flt_allow, h->d_flt_pos, h->d_flt_D, h->d_flt_bp,
                      h->d_guest[0], h->d_guest[1], h->d_guest[2], h->d_guest[3], h->d_fold[0], h->d_fold[1], h->d_fold[2], h->d_fold[3],
                      h->d_fold_long);
 }
@@ -536,6 +542,7 @@ int free_interaction_state(cdae_hip* h) {
   h->rows_ptr_cap = h->rows_uid_cap = h->rows_col_cap = h->rows_tptr_cap = h->rows_pu_cap = h->rows_tcol_cap = 0;
   h->cand_ptr_cap = h->cand_col_cap = h->cand_tiles_cap = h->cand_score_cap = h->cand_rank_cap = 0;
   h->fr_tptr_cap = h->fr_tcol_cap = h->fr_tbits_cap = h->fr_vrows_cap = h->fr_tscore_cap = h->fr_rank_cap = 0;
+  h->flt_eptr_cap = h->flt_ecol_cap = h->flt_allow_cap = h->flt_pos_cap = h->flt_D_cap = h->flt_bp_cap = 0;
   for (int k = 0; k < 4; ++k) h->guest_cap[k] = h->fold_cap[k] = 0;
   h->n_guests = 0; h->fold_long_cap = 0;
   return 0;
@@ -2288,25 +2295,48 @@ void topn_chunk(cdae_hip* h, uint32_t topk, uint64_t u0, uint32_t nu) {
 // user's score row sits in LDS where num_items floats fit; otherwise the scores of a launch go to a global workspace of <= 256 MiB,
 // which bounds the users of one launch.  prepare(): that decision, the workspaces (lists in d_rec; with_scores: their scores in
 // d_rec_score) and the dynamic-LDS attribute; launch(): one chunk of at most `chunk` users.
+// prepare(..., items, true) + launch_bits(): the same over `items` rows of any decoder image, masked from a bit table
+// (recommend_kernel<NI, true>: cdae_hip_recommend_rows_filtered); a score row is then `items` floats.
 struct Scorer {
   bool in_lds = false, with_scores = false;
   size_t shmem = 0;
   uint32_t chunk = 0, topk = 0;
-  int prepare(cdae_hip* h, uint32_t users, uint32_t topk_, bool with_scores_) {
-    const size_t lds_scores = (size_t)h->I * sizeof(float) + 64;
+  int prepare(cdae_hip* h, uint32_t users, uint32_t topk_, bool with_scores_, uint64_t items = 0, bool bits_form = false) {
+    if (items == 0) items = h->I;
+    const size_t lds_scores = (size_t)items * sizeof(float) + 64;
     in_lds = lds_scores <= 160 * 1024;
     shmem = in_lds ? lds_scores : 64;
     chunk = users; topk = topk_; with_scores = with_scores_;
     if (!in_lds) {
-      chunk = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(users, (256ull << 20) / ((uint64_t)h->I * sizeof(float))));
-      CHK(ensure_cap(&h->d_score, &h->score_cap, (size_t)chunk * h->I));
+      chunk = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(users, (256ull << 20) / (items * sizeof(float))));
+      CHK(ensure_cap(&h->d_score, &h->score_cap, (size_t)chunk * items));
     }
     CHK(ensure_cap(&h->d_rec, &h->rec_cap, (size_t)chunk * topk));
     if (with_scores) CHK(ensure_cap(&h->d_rec_score, &h->rec_score_cap, (size_t)chunk * topk));
     const void* kernel = h->NI == 1 ? (const void*)cdae::recommend_kernel<1> : h->NI == 2 ? (const void*)cdae::recommend_kernel<2>
                        : h->NI == 4 ? (const void*)cdae::recommend_kernel<4> : (const void*)cdae::recommend_kernel<8>;
+    if (bits_form)
+      kernel = h->NI == 1 ? (const void*)cdae::recommend_kernel<1, true> : h->NI == 2 ? (const void*)cdae::recommend_kernel<2, true>
+             : h->NI == 4 ? (const void*)cdae::recommend_kernel<4, true> : (const void*)cdae::recommend_kernel<8, true>;
     HIPCHK(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
     return 0;
+  }
+  // nb hidden rows z over hp.num_items rows of the decoder image (D, bp), row r masked from words [r words, (r + 1) words) of `bits`
+  template <int NI>
+  void launch_bits_as(cdae_hip* h, const cdae::HyperParams& hp, uint32_t nb, const float* z, const float* D, const float* bp,
+                      const uint32_t* bits, uint32_t words) const {
+    hipLaunchKernelGGL((cdae::recommend_kernel<NI, true>), dim3(nb), dim3(256), shmem, h->stream, hp, (const int64_t*)nullptr,
+                       (const uint32_t*)nullptr, (uint64_t)0, z, D, bp, topk, h->d_rec, in_lds ? (float*)nullptr : h->d_score, bits, words,
+                       with_scores ? h->d_rec_score : (float*)nullptr);
+  }
+  void launch_bits(cdae_hip* h, const cdae::HyperParams& hp, uint32_t nb, const float* z, const float* D, const float* bp,
+                   const uint32_t* bits, uint32_t words) const {
+    switch (h->NI) {
+      case 1: launch_bits_as<1>(h, hp, nb, z, D, bp, bits, words); break;
+      case 2: launch_bits_as<2>(h, hp, nb, z, D, bp, bits, words); break;
+      case 4: launch_bits_as<4>(h, hp, nb, z, D, bp, bits, words); break;
+      default: launch_bits_as<8>(h, hp, nb, z, D, bp, bits, words); break;
+    }
   }
   // users [u0, u0 + nb) with hidden rows z; d_rated != nullptr: the caller's input set instead of the train row (one user);
   // rows_ptr != nullptr: rows [u0, u0 + nb) of that device CSR are the masks instead of the train rows (cdae_hip_recommend_rows)
@@ -2363,26 +2393,31 @@ int recommend_general(cdae_hip* h, uint64_t u_begin, uint64_t u_end, uint32_t to
 // recommend(), matrix-core path (topk <= REC_TOPK_MAX, num_dim <= 256): recommend_mfma_kernel over nu hidden rows z and their bit
 // rows in h->d_bits, lists to h->d_rec.  The one place that maps num_dim to the kernel's contraction length.  d_score == nullptr:
 // the instantiations cdae_hip_recommend_all has always launched; otherwise the SCORES ones (cdae_hip_recommend_rows with out_scores).
+// src != nullptr (cdae_hip_recommend_rows_filtered with an allow list): the sweep runs over src->hp.num_items rows of that decoder
+// image instead of the handle's; the bit table in h->d_bits is then in that index space, and so are the ids of the lists.
 bool mfma_path(const cdae_hip* h, uint32_t topk) { return topk <= (uint32_t)cdae::REC_TOPK_MAX && h->K <= 256; }
+struct SweepSrc { cdae::HyperParams hp; const float* D; const float* bp; };
 template <int NCH, bool SCORES>
-int launch_recommend_mfma_as(cdae_hip* h, const float* z, uint32_t nu, uint32_t words, uint32_t topk, float* d_score) {
+int launch_recommend_mfma_as(cdae_hip* h, const float* z, uint32_t nu, uint32_t words, uint32_t topk, float* d_score, const SweepSrc* src) {
   const size_t lds = cdae::recommend_mfma_lds_bytes(NCH);
   const dim3 grid((nu + cdae::REC_USERS_PER_BLOCK - 1) / cdae::REC_USERS_PER_BLOCK);
   HIPCHK(hipFuncSetAttribute((const void*)cdae::recommend_mfma_kernel<NCH, SCORES>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  hipLaunchKernelGGL((cdae::recommend_mfma_kernel<NCH, SCORES>), grid, dim3(256), lds, h->stream, h->hp, z, nu, (const float*)h->dec(),
-                     (const float*)h->P(CDAE_P_BP), (const uint32_t*)h->d_bits, words, topk, h->d_rec, d_score);
+  hipLaunchKernelGGL((cdae::recommend_mfma_kernel<NCH, SCORES>), grid, dim3(256), lds, h->stream, src ? src->hp : h->hp, z, nu,
+                     src ? src->D : (const float*)h->dec(), src ? src->bp : (const float*)h->P(CDAE_P_BP), (const uint32_t*)h->d_bits, words,
+                     topk, h->d_rec, d_score);
   return 0;
 }
 template <bool SCORES>
-int launch_recommend_mfma_nch(cdae_hip* h, const float* z, uint32_t nu, uint32_t words, uint32_t topk, float* d_score) {
-  if (h->K <= 32) return launch_recommend_mfma_as<4, SCORES>(h, z, nu, words, topk, d_score);
-  if (h->K <= 64) return launch_recommend_mfma_as<8, SCORES>(h, z, nu, words, topk, d_score);
-  if (h->K <= 128) return launch_recommend_mfma_as<16, SCORES>(h, z, nu, words, topk, d_score);
-  if (h->K <= 200) return launch_recommend_mfma_as<25, SCORES>(h, z, nu, words, topk, d_score);
-  return launch_recommend_mfma_as<32, SCORES>(h, z, nu, words, topk, d_score);
+int launch_recommend_mfma_nch(cdae_hip* h, const float* z, uint32_t nu, uint32_t words, uint32_t topk, float* d_score, const SweepSrc* src) {
+  if (h->K <= 32) return launch_recommend_mfma_as<4, SCORES>(h, z, nu, words, topk, d_score, src);
+  if (h->K <= 64) return launch_recommend_mfma_as<8, SCORES>(h, z, nu, words, topk, d_score, src);
+  if (h->K <= 128) return launch_recommend_mfma_as<16, SCORES>(h, z, nu, words, topk, d_score, src);
+  if (h->K <= 200) return launch_recommend_mfma_as<25, SCORES>(h, z, nu, words, topk, d_score, src);
+  return launch_recommend_mfma_as<32, SCORES>(h, z, nu, words, topk, d_score, src);
 }
-int launch_recommend_mfma(cdae_hip* h, const float* z, uint32_t nu, uint32_t words, uint32_t topk, float* d_score) {
-  return d_score ? launch_recommend_mfma_nch<true>(h, z, nu, words, topk, d_score) : launch_recommend_mfma_nch<false>(h, z, nu, words, topk, nullptr);
+int launch_recommend_mfma(cdae_hip* h, const float* z, uint32_t nu, uint32_t words, uint32_t topk, float* d_score, const SweepSrc* src = nullptr) {
+  return d_score ? launch_recommend_mfma_nch<true>(h, z, nu, words, topk, d_score, src)
+                 : launch_recommend_mfma_nch<false>(h, z, nu, words, topk, nullptr, src);
 }
 }  // namespace
 
@@ -2885,6 +2920,85 @@ int rows_run(cdae_hip* h, const RowsArgs& a) {
   return 0;
 }
 
+// ---- filtered top-k (cdae_hip_recommend_rows_filtered) --------------------------------------------------------------------------------
+// rows_run's shape with the mask as a table of its own: filter_bits_kernel builds a chunk's exclusion rows (rated rows if the call
+// excludes them | excl rows) and both top-k paths mask from them.  With an allow list the call first packs the allowed decoder rows
+// (once, not per chunk; rebuilt by every call: the decoder can change behind the library's back through cdae_hip_param_device_ptr),
+// the sweeps run over the pack with a by-value copy of hp whose num_items is n_allow, and the lists' places are mapped back to ids.
+struct FilterArgs { const int64_t* excl_ptr; const uint32_t* excl_col; bool exclude_rated; const uint32_t* allow; uint64_t n_allow; };
+int validate_allow(const char* fn, const uint32_t* allow, uint64_t n_allow, uint64_t I) {
+  if (!allow) return n_allow ? fail("%s: null allow_items with n_allow = %llu", fn, (unsigned long long)n_allow) : 0;
+  if (n_allow == 0) return fail("%s: an allow list with n_allow = 0 (pass allow_items = NULL for the whole catalogue)", fn);
+  for (uint64_t p = 0; p < n_allow; ++p) {
+    if (allow[p] >= I) return fail("%s: allow_items[%llu] = %u is out of range", fn, (unsigned long long)p, allow[p]);
+    if (p && allow[p] <= allow[p - 1])
+      return fail("%s: allow_items is not ascending and unique at position %llu (item %u after %u)", fn, (unsigned long long)p, allow[p], allow[p - 1]);
+  }
+  return 0;
+}
+int rows_filtered_run(cdae_hip* h, const RowsArgs& a, const FilterArgs& f) {
+  HIPCHK(hipSetDevice(h->device));
+  CHK(join_aux(h));
+  const uint64_t R = a.n_rows;
+  CHK(rows_upload(h, R, a.uids, a.row_ptr, a.col));
+  if (f.excl_ptr) {
+    const size_t ennz = (size_t)f.excl_ptr[R];
+    CHK(ensure_cap(&h->d_flt_eptr, &h->flt_eptr_cap, R + 1));
+    CHK(ensure_cap(&h->d_flt_ecol, &h->flt_ecol_cap, std::max<size_t>(ennz, 1)));
+    HIPCHK(hipMemcpyAsync(h->d_flt_eptr, f.excl_ptr, (R + 1) * sizeof(int64_t), hipMemcpyHostToDevice, h->stream));
+    if (ennz) HIPCHK(hipMemcpyAsync(h->d_flt_ecol, f.excl_col, ennz * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
+  }
+  const uint64_t n = f.allow ? f.n_allow : h->I;                   // the index space of the sweep
+  SweepSrc src{h->hp, h->dec(), h->P(CDAE_P_BP)};
+  if (f.allow) {
+    const uint32_t na = (uint32_t)f.n_allow;
+    CHK(ensure_cap(&h->d_flt_allow, &h->flt_allow_cap, na));
+    CHK(ensure_cap(&h->d_flt_pos, &h->flt_pos_cap, h->I));
+    CHK(ensure_cap(&h->d_flt_D, &h->flt_D_cap, na, h->Kp));
+    CHK(ensure_cap(&h->d_flt_bp, &h->flt_bp_cap, na));
+    HIPCHK(hipMemcpyAsync(h->d_flt_allow, f.allow, na * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemsetAsync(h->d_flt_pos, 0xFF, h->I * sizeof(uint32_t), h->stream));
+    hipLaunchKernelGGL(cdae::allow_pos_kernel, dim3((na + 255) / 256), dim3(256), 0, h->stream, (const uint32_t*)h->d_flt_allow, na, h->d_flt_pos);
+    DISPATCH_NI(h->NI, cdae::pack_decoder_kernel, dim3((na + cdae::PACK_WAVES - 1) / cdae::PACK_WAVES), dim3(cdae::PACK_WAVES * cdae::WAVE), 0,
+                h->stream, (const uint32_t*)h->d_flt_allow, na, h->Kp, src.D, src.bp, h->d_flt_D, h->d_flt_bp);
+    HIPCHK(hipGetLastError());
+    src.hp.num_items = na; src.D = h->d_flt_D; src.bp = h->d_flt_bp;
+  }
+  const uint32_t topk = a.topk;
+  const bool with_scores = a.out_scores != nullptr;
+  const bool mfma = mfma_path(h, topk);
+  const uint32_t words = (uint32_t)((n + 31) / 32);
+  Scorer sc;
+  uint32_t UC = (uint32_t)std::min<uint64_t>(R, EVAL_CHUNK);
+  if (mfma) {
+    CHK(ensure_cap(&h->d_rec, &h->rec_cap, (size_t)UC * topk));
+    if (with_scores) CHK(ensure_cap(&h->d_rec_score, &h->rec_score_cap, (size_t)UC * topk));
+  } else {
+    CHK(sc.prepare(h, (uint32_t)std::min<uint64_t>(R, 4096u), topk, with_scores, n, true));
+    UC = sc.chunk;
+  }
+  CHK(ensure_cap(&h->d_bits, &h->bits_cap, (size_t)UC * words));
+  CHK(ensure_cap(&h->d_zeval, &h->eval_cap, UC, h->Kp));
+  for (uint64_t c0 = 0; c0 < R; c0 += UC) {
+    const uint32_t nu = (uint32_t)std::min<uint64_t>(UC, R - c0);
+    CHK(rows_encode_chunk(h, a.row_ptr, c0, nu));
+    hipLaunchKernelGGL(cdae::filter_bits_kernel, dim3((nu + 3) / 4), dim3(256), 0, h->stream,
+                       f.exclude_rated ? (const int64_t*)h->d_rows_ptr : (const int64_t*)nullptr, (const uint32_t*)h->d_rows_col,
+                       f.excl_ptr ? (const int64_t*)h->d_flt_eptr : (const int64_t*)nullptr, (const uint32_t*)h->d_flt_ecol,
+                       f.allow ? (const uint32_t*)h->d_flt_pos : (const uint32_t*)nullptr, c0, nu, words, h->d_bits);
+    if (mfma) CHK(launch_recommend_mfma(h, h->d_zeval, nu, words, topk, with_scores ? h->d_rec_score : nullptr, f.allow ? &src : nullptr));
+    else sc.launch_bits(h, src.hp, nu, h->d_zeval, src.D, src.bp, h->d_bits, words);
+    if (f.allow)
+      hipLaunchKernelGGL(cdae::remap_ids_kernel, dim3((uint32_t)(((size_t)nu * topk + 255) / 256)), dim3(256), 0, h->stream,
+                         (const uint32_t*)h->d_flt_allow, (size_t)nu * topk, h->d_rec);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(a.out_ids + c0 * topk, h->d_rec, (size_t)nu * topk * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+    if (with_scores) HIPCHK(hipMemcpyAsync(a.out_scores + c0 * topk, h->d_rec_score, (size_t)nu * topk * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));                       // one per chunk: d_rec is the next chunk's too
+  }
+  return 0;
+}
+
 // ---- scores and ranks of caller-supplied candidates (cdae_hip_score_rows) ------------------------------------------------------------
 // Candidates per chunk: a chunk takes whole candidate rows while they fit; a row of more candidates than this (scores only: ranks stop
 // at CDAE_RANK_CANDIDATES_MAX) is cut into chunks of exactly this many, so a row of num_items candidates fits whatever num_items is.
@@ -3254,6 +3368,19 @@ int cdae_hip_recommend_rows(cdae_hip_t* h, uint64_t n_rows, const uint32_t* uids
   if (n_rows == 0) return 0;
   if (!out_ids) return fail("cdae_hip_recommend_rows: null out_ids");
   return rows_run(h, a);
+}
+
+int cdae_hip_recommend_rows_filtered(cdae_hip_t* h, uint64_t n_rows, const uint32_t* uids, const int64_t* row_ptr, const uint32_t* col,
+                                     const int64_t* excl_row_ptr, const uint32_t* excl_col, int exclude_rated,
+                                     const uint32_t* allow_items, uint64_t n_allow, uint32_t topk, uint32_t* out_ids, float* out_scores) {
+  const char* fn = "cdae_hip_recommend_rows_filtered";
+  const RowsArgs a{n_rows, uids, row_ptr, col, nullptr, nullptr, 0, topk, out_ids, out_scores};
+  CHK(rows_check(h, fn, a));
+  CHK(validate_allow(fn, allow_items, n_allow, h->I));
+  if (n_rows == 0) return 0;
+  if (excl_row_ptr) CHK(validate_rows_csr("excl", excl_row_ptr, excl_col, n_rows, h->I));
+  if (!out_ids) return fail("%s: null out_ids", fn);
+  return rows_filtered_run(h, a, FilterArgs{excl_row_ptr, excl_col, exclude_rated != 0, allow_items, n_allow});
 }
 
 int cdae_hip_eval_topn_rows(cdae_hip_t* h, uint64_t n_rows, const uint32_t* uids, const int64_t* row_ptr, const uint32_t* col,

@@ -2304,7 +2304,11 @@ sqnorm_kernel(const float* __restrict__ x, size_t n, double* __restrict__ out) {
 // topk * num_items / 256 reads instead of topk passes.
 // rated_override != nullptr (one user per launch): the caller's rated set replaces the train row as the mask
 // (recommend(uid, topk, rated_item_set) with a set that is not the train row).
-template <int NI>
+// BITS (cdae_hip_recommend_rows_filtered): the mask is a row of a bit table instead of a CSR row — rated_override is the table of the
+// launch, [gridDim.x][n_override] words in the index space the sweep runs in (filter_bits_kernel), row_ptr / col are not read.  The
+// scores, the arg-max loop, its tie rule and its sentinel are the same code; the default instantiation is the one every other caller
+// has always launched.
+template <int NI, bool BITS = false>
 __global__ void __launch_bounds__(256)
 recommend_kernel(HyperParams hp, const int64_t* __restrict__ row_ptr, const uint32_t* __restrict__ col,
                  uint64_t u0, const float* __restrict__ Z, const float* __restrict__ D,
@@ -2332,7 +2336,14 @@ recommend_kernel(HyperParams hp, const int64_t* __restrict__ row_ptr, const uint
     if (lane == 0) score[item] = y;
   }
   __syncthreads();
-  if (rated_override) {
+  if constexpr (BITS) {
+    const uint32_t* wrow = rated_override + (size_t)slot * n_override;
+    for (uint32_t w = threadIdx.x; w < n_override; w += blockDim.x)
+      for (uint32_t m = wrow[w]; m; m &= m - 1u) {
+        const uint32_t item = 32u * w + (uint32_t)__builtin_ctz(m);
+        if (item < hp.num_items) score[item] = -INFINITY;
+      }
+  } else if (rated_override) {
     for (uint32_t p = threadIdx.x; p < n_override; p += blockDim.x) score[rated_override[p]] = -INFINITY;
   } else {
     const int64_t r0 = row_ptr[uid];

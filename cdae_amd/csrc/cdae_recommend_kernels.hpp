@@ -736,4 +736,101 @@ full_rank_general_kernel(HyperParams hp, const int64_t* __restrict__ row_ptr, co
   }
 }
 
+// ---- filtered top-k (cdae_hip_recommend_rows_filtered): an item allow list for the call, per-row exclusions that are no inputs --------
+// The top-k kernels take the exclusion as data and do not care where a decoder row sits in memory: the score of (row, item) is a
+// function of z, D[item] and b'[item] only.  So a filter is served exactly.  filter_bits_kernel is the ONE place where the filter is
+// interpreted: it writes the chunk's exclusion table in the index space the sweep runs in, and recommend_mfma_kernel and
+// recommend_kernel<NI, true> both mask from that table.  With an allow list the sweep runs over a packed copy of the allowed decoder
+// rows (pack_decoder_kernel, once per call) with num_items := n_allow: ascending places in the pack are ascending item ids, so the tie
+// rule survives, and remap_ids_kernel turns the places of the lists back into item ids.
+//
+// filter_bits_kernel: bits[(r - r0) * words + x / 32] |= 1 << (x % 32) for every item of row r of up to two CSRs (the rated rows when
+// the call excludes them, the excl rows when it has any; a null row_ptr leaves a CSR out), x = the item, or pos[item] when there is an
+// allow list (0xFFFFFFFF: the item is not allowed, so it is no candidate anyway and is skipped).  rated_bits_kernel's two forms and
+// its reasons: one wavefront per row, no memset launch in front, the row of words built in LDS and written once when it fits, else
+// cleared in global memory by its own wavefront, which waits for its own stores (s_waitcnt: same-wave order is all that is needed; no
+// agent-scope fence, which would write back the L2 under whatever the other streams run) before its atomics.
+// one wavefront: the items of row `row` of up to two CSRs, mapped through pos, ORed into the row of words w (LDS or global memory:
+// inlined into either form, so each keeps the atomics of its own address space)
+__device__ __forceinline__ void filter_mark(const int64_t* __restrict__ rated_ptr, const uint32_t* __restrict__ rated_col,
+                                            const int64_t* __restrict__ excl_ptr, const uint32_t* __restrict__ excl_col,
+                                            const uint32_t* __restrict__ pos, uint64_t row, uint32_t lane, uint32_t* w) {
+#pragma unroll
+  for (int c = 0; c < 2; ++c) {
+    const int64_t* ptr = c ? excl_ptr : rated_ptr;
+    const uint32_t* col = c ? excl_col : rated_col;
+    if (!ptr) continue;                                            // (uniform over the launch)
+    const int64_t a = ptr[row], b = ptr[row + 1];
+    for (int64_t p = a + lane; p < b; p += WAVE) {
+      uint32_t x = col[p];
+      if (pos) x = pos[x];
+      if (x != 0xFFFFFFFFu) atomicOr(&w[x >> 5], 1u << (x & 31u));
+    }
+  }
+}
+__global__ void __launch_bounds__(256)
+filter_bits_kernel(const int64_t* __restrict__ rated_ptr, const uint32_t* __restrict__ rated_col, const int64_t* __restrict__ excl_ptr,
+                   const uint32_t* __restrict__ excl_col, const uint32_t* __restrict__ pos, uint64_t r0, uint32_t nu, uint32_t words,
+                   uint32_t* __restrict__ bits) {
+  __shared__ uint32_t lrow[4][RATED_LDS_WORDS];
+  const uint32_t wid = threadIdx.x / WAVE;
+  const uint32_t slot = blockIdx.x * (blockDim.x / WAVE) + wid;
+  const uint32_t lane = threadIdx.x % WAVE;
+  if (slot >= nu) return;                                          // (no workgroup barrier in this kernel)
+  uint32_t* out = bits + (size_t)slot * words;
+  if (words <= RATED_LDS_WORDS) {
+    uint32_t* w = lrow[wid];
+    for (uint32_t i = lane; i < words; i += WAVE) w[i] = 0u;
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    filter_mark(rated_ptr, rated_col, excl_ptr, excl_col, pos, r0 + slot, lane, w);          // LDS
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    for (uint32_t i = lane; i < words; i += WAVE) out[i] = w[i];
+    return;
+  }
+  {                                                                // 16-byte stores over the aligned middle of the row, words at its ends
+    const uint32_t head = min(words, (uint32_t)((16u - ((uintptr_t)out & 15u)) & 15u) / 4u), quads = (words - head) / 4u;
+    for (uint32_t i = lane; i < head; i += WAVE) out[i] = 0u;
+    uint4* o4 = reinterpret_cast<uint4*>(out + head);
+    for (uint32_t i = lane; i < quads; i += WAVE) o4[i] = make_uint4(0u, 0u, 0u, 0u);
+    for (uint32_t i = head + 4u * quads + lane; i < words; i += WAVE) out[i] = 0u;
+  }
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  filter_mark(rated_ptr, rated_col, excl_ptr, excl_col, pos, r0 + slot, lane, out);
+}
+
+// pos[allow[p]] = p over a 0xFF fill of pos[num_items] (hipMemsetAsync in front): item -> place in the allow list
+__global__ void __launch_bounds__(256)
+allow_pos_kernel(const uint32_t* __restrict__ allow, uint32_t n_allow, uint32_t* __restrict__ pos) {
+  const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
+  if (p < n_allow) pos[allow[p]] = p;
+}
+
+// Dp[p] = D[allow[p]] (whole rows of Kp floats, pad elements included: a wave load and a wave store per row, a wavefront per row,
+// PACK_WAVES rows to a workgroup, no LDS and no barrier) and bpp[p] = b'[allow[p]].
+constexpr int PACK_WAVES = 4;
+template <int NI>
+__global__ void __launch_bounds__(PACK_WAVES * WAVE)
+pack_decoder_kernel(const uint32_t* __restrict__ allow, uint32_t n_allow, uint32_t Kp, const float* __restrict__ D,
+                    const float* __restrict__ bp, float* __restrict__ Dp, float* __restrict__ bpp) {
+  const uint32_t wid = threadIdx.x / WAVE, lane = threadIdx.x % WAVE;
+  const uint32_t p = blockIdx.x * PACK_WAVES + wid;
+  if (p >= n_allow) return;
+  const uint32_t item = allow[p];
+  float v[NI];
+  vload<NI>(v, D + (size_t)item * Kp + lane * NI);
+  vstore<NI>(Dp + (size_t)p * Kp + lane * NI, v);
+  if (lane == 0) bpp[p] = bp[item];
+}
+
+// ids[i] = allow[ids[i]] over the [n] places of a chunk's lists; the sentinel stays the sentinel
+__global__ void __launch_bounds__(256)
+remap_ids_kernel(const uint32_t* __restrict__ allow, size_t n, uint32_t* __restrict__ ids) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const uint32_t p = ids[i];
+  if (p != 0xFFFFFFFFu) ids[i] = allow[p];
+}
+
 }  // namespace cdae

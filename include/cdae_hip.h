@@ -27,6 +27,8 @@
  *   CDAE::recommend (all users, top-k)   cdae.hpp:162-196    cdae_hip_recommend_all
  *   CDAE::recommend (any rated sets)     cdae.hpp:162-196    cdae_hip_recommend_rows, cdae_hip_eval_topn_rows (batched),
  *                                                            cdae_hip_recommend_user (one user)
+ *   CDAE::recommend (allow list, exclusions apart from the inputs)
+ *                                        cdae.hpp:162-196    cdae_hip_recommend_rows_filtered
  *   CDAE::recommend (place of named items in the whole list)
  *                                        cdae.hpp:162-196    cdae_hip_full_rank_rows
  *   CDAE::get_output_values              cdae.hpp:418-426    cdae_hip_score_rows
@@ -79,7 +81,9 @@ extern "C" {
  *     items in a row's whole list (full-catalogue Recall@k / NDCG@k / MRR / AUC without sampling)
  *     also under 12, the version unchanged (new entry points; nothing existing changed): cdae_hip_fold_in_rows, cdae_hip_set_guest_nodes,
  *     cdae_hip_guest_nodes, CDAE_GUEST_USER — batched fold-in of user nodes for rows outside the training set, and a guest table that serves the fitted nodes
- *     to the rows entry points */
+ *     to the rows entry points
+ *     also under 12, the version unchanged (a new entry point; nothing existing changed): cdae_hip_recommend_rows_filtered — batched top-k
+ *     with an item allow list for the call and per-row exclusions that are not inputs (or inputs that are not exclusions) */
 #define CDAE_HIP_ABI_VERSION 12
 
 /* numeric values follow libcf::LossType (/root/reference/src/model/loss.hpp:10-18) */
@@ -433,6 +437,47 @@ int cdae_hip_score_rows(cdae_hip_t* h, uint64_t n_rows, const uint32_t* uids, co
  * Cost: two sweeps of the decoder per chunk plus 16 compares per (column, item). */
 int cdae_hip_full_rank_rows(cdae_hip_t* h, uint64_t n_rows, const uint32_t* uids, const int64_t* row_ptr, const uint32_t* col,
                             const int64_t* target_row_ptr, const uint32_t* target_col, uint32_t* out_ranks, float* out_scores);
+
+/* cdae_hip_recommend_rows with the excluded set cut loose from the input set, and an item allow list: a category page ("top 10 among
+ * these 600 items"), items that must not be listed but were never inputs (shown and ignored, out of stock, blocked), and repeat
+ * consumption (a rated item may be listed again).
+ *   rows, uids, hidden, order of the input sum
+ *            exactly cdae_hip_recommend_rows's, validated alike and encoded by the same launches: the z of a row is bit for bit the
+ *            z cdae_hip_recommend_rows ranks from (CDAE_NO_USER, CDAE_GUEST_USER(i), uids == NULL and corruption_ratio == 1 mean what
+ *            they mean there).  Neither excl nor allow enters z.
+ *   excl     excl_row_ptr[n_rows + 1] / excl_col: a second host CSR over the same rows, items ascending and unique inside a row
+ *            (validated: an unsorted, duplicate or out-of-range item is an error that names the row); a row may be empty.
+ *            excl_row_ptr == NULL: no extra exclusions.  An excluded item may also be rated; it may also lie outside the allow list,
+ *            where it has no effect.
+ *   exclude_rated
+ *            != 0: a row's rated items are excluded as in cdae_hip_recommend_rows.  0: they are candidates like any other item; the
+ *            row's list then comes from all (allowed) items minus excl.
+ *   allow    allow_items[n_allow]: ONE list for the whole call, ascending and unique (an unsorted, duplicate or out-of-range id is an
+ *            error that names the position).  allow_items == NULL (then n_allow must be 0): the whole catalogue.  allow_items != NULL
+ *            with n_allow == 0 is an error.
+ *   result   row r's list is the first topk items of its candidate set C_r = allow \ excl_r (\ rated_r when exclude_rated) in
+ *            cdae_hip_recommend_all's total order: descending score, equal scores by ascending ORIGINAL item id.  out_ids holds
+ *            original item ids; a row with |C_r| < topk gets 0xFFFFFFFF in the surplus places (-INFINITY in out_scores, which may be
+ *            NULL).  topk in [1, num_items] whatever the allow list's size.
+ *   which arithmetic (part of the contract)
+ *            the path is chosen as for cdae_hip_recommend_rows: num_dim <= 256 and topk <= 16 run on the matrix cores, anything else
+ *            on the general path.  On either path the score of (row, item) is the bits that path of cdae_hip_recommend_rows computes
+ *            for that pair: with excl == NULL, allow == NULL and exclude_rated != 0 the call returns cdae_hip_recommend_rows' ids and
+ *            scores bit for bit; with a filter it returns the list cdae_hip_recommend_rows would give at unbounded length with the
+ *            items outside C_r deleted, scores bit for bit.  (With an allow list the sweep runs over a packed copy of the allowed
+ *            decoder rows, made once per call and rebuilt by every call; a score does not depend on where its decoder row sits.)
+ *   position independence
+ *            a row's list and scores do not depend on what else the call holds, on the row's place in the call, or on the chunking.
+ * n_rows == 0 succeeds and touches nothing.
+ * Refused (the handle stays usable): IMF / BPR handles, item shards, calls before cdae_hip_set_interactions.  Every validation error is
+ * raised before anything is launched.
+ * The caller's arrays, the allow list's inverse and the packed decoder rows live in grow-only device buffers of the handle (freed with
+ * it): a steady-state call allocates nothing.  Rows are taken in chunks of at most 32 768 (the general path's chunk is that of
+ * cdae_hip_recommend_rows' general path, sized by the swept item count) with one host synchronisation per chunk. */
+int cdae_hip_recommend_rows_filtered(cdae_hip_t* h, uint64_t n_rows, const uint32_t* uids, const int64_t* row_ptr, const uint32_t* col,
+                                     const int64_t* excl_row_ptr, const uint32_t* excl_col, int exclude_rated,
+                                     const uint32_t* allow_items, uint64_t n_allow,
+                                     uint32_t topk, uint32_t* out_ids, float* out_scores);
 
 /* Fold-in: fit the user node of MANY rows that are no train rows, with everything shared frozen — the strong-generalisation protocol
  * (train on some users; for an unseen user fit only their own node on part of their history, rank the rest), and the warm re-fit of a

@@ -289,6 +289,52 @@ class CDAE : public RecsysModelBase {
     return out;
   }
 
+  // recommend_rows() with the excluded set cut loose from the input set, in ONE device call (cdae_hip_recommend_rows_filtered): row r is
+  // encoded from rated_sets[r] with the user node of uids[r] (kNoUser: none), exactly as recommend_rows() encodes it;
+  // excluded_sets[r] are items that must not be listed but do not enter the hidden layer (empty vector of sets: none anywhere);
+  // allow, when not empty, is ONE item list for the whole call — the only items that may be listed ("top 10 of this category");
+  // exclude_rated = false makes a row's own items candidates again (repeat consumption).  Lists as recommend_rows() returns them:
+  // its unbounded list with the items outside allow \ excluded_sets[r] (\ rated_sets[r]) deleted, cut at topk, shorter when fewer
+  // candidates are left.  Single-handle models only; serialised on the handle's mutex like recommend().
+  std::vector<std::vector<size_t>> recommend_rows_filtered(const std::vector<size_t>& uids, const std::vector<std::vector<size_t>>& rated_sets,
+                                                           const std::vector<std::vector<size_t>>& excluded_sets,
+                                                           const std::vector<size_t>& allow, size_t topk, bool exclude_rated = true) const {
+    CHECK_EQ(uids.size(), rated_sets.size());
+    CHECK(excluded_sets.empty() || excluded_sets.size() == rated_sets.size());
+    CHECK(!multi_) << "recommend_rows_filtered() is provided for a model on one device";
+    const size_t n = rated_sets.size();
+    std::vector<uint32_t> u(n), col, ecol, al;
+    std::vector<int64_t> ptr(n + 1, 0), eptr(n + 1, 0);
+    for (size_t r = 0; r < n; ++r) {
+      if (uids[r] != kNoUser) CHECK_LT(uids[r], num_users_);
+      u[r] = uids[r] == kNoUser ? CDAE_NO_USER : static_cast<uint32_t>(uids[r]);
+      const size_t at = col.size();
+      for (size_t i : rated_sets[r]) { CHECK_LT(i, num_items_); col.push_back(static_cast<uint32_t>(i)); }
+      std::sort(col.begin() + at, col.end());                    // the device CSRs are ascending inside a row (duplicates: its error)
+      ptr[r + 1] = static_cast<int64_t>(col.size());
+      if (!excluded_sets.empty()) {
+        const size_t eat = ecol.size();
+        for (size_t i : excluded_sets[r]) { CHECK_LT(i, num_items_); ecol.push_back(static_cast<uint32_t>(i)); }
+        std::sort(ecol.begin() + eat, ecol.end());
+        eptr[r + 1] = static_cast<int64_t>(ecol.size());
+      }
+    }
+    for (size_t i : allow) { CHECK_LT(i, num_items_); al.push_back(static_cast<uint32_t>(i)); }
+    std::sort(al.begin(), al.end());                               // one ascending list (duplicates: the device call's error)
+    std::vector<uint32_t> ids(n * topk);
+    {
+      std::lock_guard<std::mutex> lk(*mu_);
+      CHECK(ready()) << "reset() must be called first";
+      CDAE_HIP_CHECK(cdae_hip_recommend_rows_filtered(dev_.get(), n, u.data(), ptr.data(), col.data(), excluded_sets.empty() ? nullptr : eptr.data(),
+                                                      ecol.data(), exclude_rated ? 1 : 0, al.empty() ? nullptr : al.data(), al.size(),
+                                                      static_cast<uint32_t>(topk), ids.data(), nullptr));
+    }
+    std::vector<std::vector<size_t>> out(n);
+    for (size_t r = 0; r < n; ++r)
+      for (size_t i = 0; i < topk && ids[r * topk + i] != 0xFFFFFFFFu; ++i) out[r].push_back(ids[r * topk + i]);
+    return out;
+  }
+
   // get_output_values(z, idx) (cdae.hpp:418-426 of the reference) for many rows in ONE device call (cdae_hip_score_rows): row r is
   // encoded from rated_sets[r] with the user node of uids[r] (kNoUser: none), exactly as recommend_rows() encodes it, and
   // candidate_sets[r] are the items whose scores are wanted — in the caller's order, rated items allowed (nothing is excluded),
