@@ -14,6 +14,8 @@
 #include <functional>
 #include <mutex>
 #include <thread>
+#include <type_traits>
+#include <utility>
 #include <chrono>
 #include <cmath>
 #include <cstdarg>
@@ -77,6 +79,46 @@ int fail(const char* fmt, ...) {
       default: hipLaunchKernelGGL(KERNEL<8>, grid, block, shmem, stream, __VA_ARGS__); break;     \
     }                                                                                             \
   } while (0)
+// address of `KERNEL<NI, ...>` for the handle's NI (hipFuncSetAttribute)
+#define KERNEL_OF_NI(ni, KERNEL, ...)                                                                       \
+  ((ni) == 1 ? (const void*)KERNEL<1, ##__VA_ARGS__> : (ni) == 2 ? (const void*)KERNEL<2, ##__VA_ARGS__>    \
+   : (ni) == 4 ? (const void*)KERNEL<4, ##__VA_ARGS__> : (const void*)KERNEL<8, ##__VA_ARGS__>)
+
+// f(std::integral_constant<int, NCH>) for the contraction length NCH of the matrix-core sweeps (recommend_mfma_kernel,
+// full_rank_mfma_kernel) at num_dim K <= 256: the one place that maps num_dim to it
+template <class F> int dispatch_nch(uint32_t K, F&& f) {
+  if (K <= 32) return f(std::integral_constant<int, 4>{});
+  if (K <= 64) return f(std::integral_constant<int, 8>{});
+  if (K <= 128) return f(std::integral_constant<int, 16>{});
+  if (K <= 200) return f(std::integral_constant<int, 25>{});
+  return f(std::integral_constant<int, 32>{});
+}
+
+template <class T> int dev_alloc(T** p, size_t n) {
+  HIPCHK(hipMalloc((void**)p, std::max<size_t>(n, 1) * sizeof(T)));
+  return 0;
+}
+// Grow-only device workspace that owns its capacity: p holds at least cap units of `per` elements (the `per` of the ensure() calls
+// that grew it).  drop() is the only way either member is cleared, so a freed buffer can never keep a capacity that ensure() would
+// believe.  Every DevBuf of a handle is listed once, in drop_dev_bufs().
+template <class T> struct DevBuf {
+  T* p = nullptr;
+  size_t cap = 0;
+  int ensure(size_t n, size_t per = 1) {
+    if (cap >= n) return 0;
+    CHK(drop());
+    CHK(dev_alloc(&p, n * per));
+    cap = n;
+    return 0;
+  }
+  int drop() {                  // both members are cleared whatever hipFree answers
+    T* const old = p;
+    p = nullptr; cap = 0;
+    if (old) HIPCHK(hipFree(old));
+    return 0;
+  }
+  operator T*() const { return p; }
+};
 
 constexpr uint32_t MF_SEQ_USERS = 256;     // IMF / BPR sequential default: users per launch window (cdae_hip::mf_seq)
 // batches above this many users take the two-launch encode (a workgroup of 16 wavefronts per user is mostly idle wavefronts;
@@ -207,44 +249,46 @@ struct cdae_hip {
   uint32_t* d_touched = nullptr;
   double* d_scalar = nullptr;
   uint32_t* d_uids = nullptr;
-  uint32_t* d_rec = nullptr; size_t rec_cap = 0;
-  float* d_score = nullptr; size_t score_cap = 0;      // recommend, general path: score rows when num_items * 4 B exceed the LDS
-  float* d_zeval = nullptr; float* d_hpart_eval = nullptr; uint32_t eval_cap = 0, eval_unit_cap = 0;   // evaluation workspace
-  uint32_t* d_bits = nullptr; size_t bits_cap = 0;                                                     // recommend: rated-item bitmap
+  // Grow-only workspaces of the evaluation and serving entry points (DevBuf, listed in drop_dev_bufs): a steady-state call allocates nothing
+  DevBuf<uint32_t> d_rec;               // the lists of one chunk
+  DevBuf<float> d_score;                // recommend, general path: score rows when num_items * 4 B exceed the LDS
+  DevBuf<float> d_zeval, d_hpart_eval;  // evaluation workspace: [users][Kp] hidden rows, [units][Kp] encode partial sums
+  DevBuf<uint32_t> d_bits;              // recommend: rated-item bitmap
   // TOPN metrics on the device (cdae_hip_set_test_rows / cdae_hip_eval_topn): the validation rows as CSR, per-user metric terms
   int64_t* d_test_ptr = nullptr; uint32_t* d_test_col = nullptr; double* d_topn_pu = nullptr; double* d_topn_out = nullptr;
   uint64_t test_users_with_rows = 0;
   bool topn_active = false;             // recommend paths: score every chunk's lists with topn_user_kernel (cdae_hip_eval_topn)
   // cdae_hip_recommend_rows / cdae_hip_eval_topn_rows: the caller's rated sets (CSR + user of every row), target sets and per-row metric
   // terms; grow-only (capacities in rows / items), so a steady-state call allocates nothing
-  int64_t* d_rows_ptr = nullptr; size_t rows_ptr_cap = 0; uint32_t* d_rows_uid = nullptr; size_t rows_uid_cap = 0;
-  uint32_t* d_rows_col = nullptr; size_t rows_col_cap = 0;
-  int64_t* d_rows_tptr = nullptr; size_t rows_tptr_cap = 0; double* d_rows_pu = nullptr; size_t rows_pu_cap = 0;
-  uint32_t* d_rows_tcol = nullptr; size_t rows_tcol_cap = 0;
+  DevBuf<int64_t> d_rows_ptr, d_rows_tptr;
+  DevBuf<uint32_t> d_rows_uid, d_rows_col, d_rows_tcol;
+  DevBuf<double> d_rows_pu;
   double* d_rows_out = nullptr;         // [16]: the eight means, then the three hit counts
   // cdae_hip_score_rows: the candidate CSR, the tile table of the call, the scores and ranks of one chunk (grow-only, freed with the handle)
-  int64_t* d_cand_ptr = nullptr; size_t cand_ptr_cap = 0; uint32_t* d_cand_col = nullptr; size_t cand_col_cap = 0;
-  uint2* d_cand_tiles = nullptr; size_t cand_tiles_cap = 0;
-  float* d_cand_score = nullptr; size_t cand_score_cap = 0; uint32_t* d_cand_rank = nullptr; size_t cand_rank_cap = 0;
+  DevBuf<int64_t> d_cand_ptr;
+  DevBuf<uint32_t> d_cand_col, d_cand_rank;
+  DevBuf<uint2> d_cand_tiles;
+  DevBuf<float> d_cand_score;
   std::vector<uint2> h_cand_tiles;      // host image of the tile table: alive until the call's last synchronisation
   // cdae_hip_full_rank_rows: the target CSR, its bit rows for one chunk, the virtual-row table of the call, the target scores and
   // ranks of one chunk (grow-only, freed with the handle)
-  int64_t* d_fr_tptr = nullptr; size_t fr_tptr_cap = 0; uint32_t* d_fr_tcol = nullptr; size_t fr_tcol_cap = 0;
-  uint32_t* d_fr_tbits = nullptr; size_t fr_tbits_cap = 0; uint2* d_fr_vrows = nullptr; size_t fr_vrows_cap = 0;
-  float* d_fr_tscore = nullptr; size_t fr_tscore_cap = 0; uint32_t* d_fr_rank = nullptr; size_t fr_rank_cap = 0;
+  DevBuf<int64_t> d_fr_tptr;
+  DevBuf<uint32_t> d_fr_tcol, d_fr_tbits, d_fr_rank;
+  DevBuf<uint2> d_fr_vrows;
+  DevBuf<float> d_fr_tscore;
   std::vector<uint2> h_fr_vrows;        // host image of the virtual-row table: alive until the call's last synchronisation
   // cdae_hip_recommend_rows_filtered: the excl CSR, the allow list, its inverse (item -> place, [num_items]) and the packed copy of the
   // allowed decoder rows and of their b' (rebuilt by every call that has an allow list); grow-only, freed with the handle
-  int64_t* d_flt_eptr = nullptr; size_t flt_eptr_cap = 0; uint32_t* d_flt_ecol = nullptr; size_t flt_ecol_cap = 0;
-  uint32_t* d_flt_allow = nullptr; size_t flt_allow_cap = 0; uint32_t* d_flt_pos = nullptr; size_t flt_pos_cap = 0;
-  float* d_flt_D = nullptr; size_t flt_D_cap = 0; float* d_flt_bp = nullptr; size_t flt_bp_cap = 0;
+  DevBuf<int64_t> d_flt_eptr;
+  DevBuf<uint32_t> d_flt_ecol, d_flt_allow, d_flt_pos;
+  DevBuf<float> d_flt_D, d_flt_bp;
   // Guest table (cdae_hip_set_guest_nodes, cdae_hip_fold_in_rows with install): a second user table, rows wu | wu_ag | uu | uu_ag of
   // [n_guests x Kp] each, that the rows entry points address as CDAE_GUEST_USER(i).  d_fold: the staging rows the fold-in kernel writes
   // (a chunk's, or the whole call's when it installs); installing EXCHANGES the two sets, so a failed call leaves the table as it was.
   // Grow-only, freed with the handle.  d_fold_long: the long rows' slots of every chunk of a call (cdae_foldin_kernels.hpp).
-  float* d_guest[4] = {nullptr, nullptr, nullptr, nullptr}; size_t guest_cap[4] = {0, 0, 0, 0}; uint64_t n_guests = 0;
-  float* d_fold[4] = {nullptr, nullptr, nullptr, nullptr}; size_t fold_cap[4] = {0, 0, 0, 0};
-  uint32_t* d_fold_long = nullptr; size_t fold_long_cap = 0;
+  DevBuf<float> d_guest[4]; uint64_t n_guests = 0;
+  DevBuf<float> d_fold[4];
+  DevBuf<uint32_t> d_fold_long;
   std::vector<uint32_t> h_fold_long;    // host image of that list: alive until the call's last synchronisation
   std::vector<size_t> h_fold_long_off;  // where every chunk's slots begin in it (kept here so that a steady-state call allocates no host memory either)
   int sort_bits = 1;
@@ -314,8 +358,9 @@ struct cdae_hip {
   // possibly with no local item.  The two per-user sums that cross shards live in d_Hsum (input sums) and d_HG (hidden gradient).
   bool item_shard = false; uint64_t item0 = 0, I_global = 0;
   uint32_t* d_gpos = nullptr;           // item shard: per user (length of the whole row, position of the first local item): the dropout stream's index space
-  float* d_Hsum = nullptr; float* d_hsum_eval = nullptr; uint32_t* d_iota_eval = nullptr; float* d_rec_score = nullptr; size_t rec_score_cap = 0;
-  uint32_t hsum_eval_cap = 0;
+  float* d_Hsum = nullptr; uint32_t* d_iota_eval = nullptr;
+  DevBuf<float> d_hsum_eval;            // item shard, evaluation: [users][SHARD_BLOCKS x Kp] input-sum all-reduce buffer of a chunk
+  DevBuf<float> d_rec_score;            // the scores of d_rec's lists (item-sharded top-k merge, the rows entry points' out_scores)
   uint64_t fs_prepped = 0;              // item-sharded training: batches whose example lists have been prepared (buffer set = parity)
   // item shard: users [own_u0, own_u1) keep their private rows (Wu, Wu_ag, Uu, Uu_ag) HERE, table row 0 = user own_u0 (SURVEY.md
   // §8(e): the user node is sharded by user; the rows of a batch's users reach the other shards through the input-sum all-reduce)
@@ -487,22 +532,30 @@ template <class F> int visit_device_ptrs(cdae_hip* h, F f) {
                     b.item_count, b.prefix, b.rank, b.bucketed, b.tile_hist, b.block_total, b.wg_state, b.cells, b.cell_flag, b.pack));
   return visit_slots(f, h->d_row_ptr, h->d_col, h->d_item_order, h->d_shared, h->d_Wu, h->d_Wu_ag, h->d_D0, h->d_HGpart, h->d_sort_tmp,
                      h->d_unit_ptr, h->d_Hpart, h->d_uptr_tmp, h->d_Zb, h->d_ZTb, h->d_Db, h->d_DTb, h->d_Gb, h->d_GTb, h->d_dD, h->d_has_in,
-                     h->d_Z, h->d_Dz, h->d_HG, h->d_G, h->d_touched, h->d_uids, h->d_rec, h->d_base, h->d_delta, h->d_recv, h->d_snap,
-                     h->d_dup_corr, h->d_unit_user, h->d_zeval, h->d_bits, h->d_hpart_eval, h->d_iota, h->d_bits_train,
-                     h->d_Uu, h->d_Uu_ag, h->d_Ssum, h->d_delta_rows, h->d_score, h->d_Hsum, h->d_hsum_eval, h->d_iota_eval, h->d_rec_score,
+                     h->d_Z, h->d_Dz, h->d_HG, h->d_G, h->d_touched, h->d_uids, h->d_base, h->d_delta, h->d_recv, h->d_snap,
+                     h->d_dup_corr, h->d_unit_user, h->d_iota, h->d_bits_train,
+                     h->d_Uu, h->d_Uu_ag, h->d_Ssum, h->d_delta_rows, h->d_Hsum, h->d_iota_eval,
                      h->d_gpos, h->d_ub, h->d_ub_ag, h->d_UVpre, h->d_rank_of, h->d_grow_ptr, h->d_gcol, h->d_gunit_ptr, h->d_gunit_user,
                      h->d_test_ptr, h->d_test_col, h->d_topn_pu, h->d_topn_out, h->d_bucket_cut, h->d_range_of,
-                     h->d_Ghot, h->d_hotdup, h->d_late_bits, h->d_cold_map,
-                     h->d_rows_ptr, h->d_rows_uid, h->d_rows_col, h->d_rows_tptr, h->d_rows_pu, h->d_rows_tcol, h->d_rows_out,
-                     h->d_cand_ptr, h->d_cand_col, h->d_cand_tiles, h->d_cand_score, h->d_cand_rank,
-                     h->d_fr_tptr, h->d_fr_tcol, h->d_fr_tbits, h->d_fr_vrows, h->d_fr_tscore, h->d_fr_rank,
-                     h->d_flt_eptr, h->d_flt_ecol, h->d_flt_allow, h->d_flt_pos, h->d_flt_D, h->d_flt_bp,
-                     h->d_guest[0], h->d_guest[1], h->d_guest[2], h->d_guest[3], h->d_fold[0], h->d_fold[1], h->d_fold[2], h->d_fold[3],
-                     h->d_fold_long);
+                     h->d_Ghot, h->d_hotdup, h->d_late_bits, h->d_cold_map, h->d_rows_out);
+}
+// ... and every grow-only workspace (DevBuf), freed with its capacity.  A new one is added HERE only.  A hipFree error is returned after all have been dropped.
+int drop_dev_bufs(cdae_hip* h) {
+  int rc = 0;
+  auto drop = [&](auto&... b) { ((rc = b.drop() || rc), ...); };
+  drop(h->d_rec, h->d_rec_score, h->d_score, h->d_bits, h->d_zeval, h->d_hpart_eval, h->d_hsum_eval,
+       h->d_rows_ptr, h->d_rows_uid, h->d_rows_col, h->d_rows_tptr, h->d_rows_pu, h->d_rows_tcol,
+       h->d_cand_ptr, h->d_cand_col, h->d_cand_tiles, h->d_cand_score, h->d_cand_rank,
+       h->d_fr_tptr, h->d_fr_tcol, h->d_fr_tbits, h->d_fr_vrows, h->d_fr_tscore, h->d_fr_rank,
+       h->d_flt_eptr, h->d_flt_ecol, h->d_flt_allow, h->d_flt_pos, h->d_flt_D, h->d_flt_bp,
+       h->d_guest[0], h->d_guest[1], h->d_guest[2], h->d_guest[3], h->d_fold[0], h->d_fold[1], h->d_fold[2], h->d_fold[3],
+       h->d_fold_long);
+  return rc;
 }
 
 void free_all(cdae_hip* h) {
   (void)visit_device_ptrs(h, [](void** p) { if (*p) (void)hipFree(*p); *p = nullptr; return 0; });   // (errors ignored: the handle goes away)
+  (void)drop_dev_bufs(h);
   if (h->d_scalar) (void)hipFree(h->d_scalar);
   for (auto& b : h->ex) {
     if (b.ready) (void)hipEventDestroy(b.ready);
@@ -536,29 +589,9 @@ int free_interaction_state(cdae_hip* h) {
     if (*p) { HIPCHK(hipFree(*p)); *p = nullptr; }
     return 0;
   }));
-  h->rec_cap = 0; h->score_cap = 0; h->rec_score_cap = 0; h->hsum_eval_cap = 0;
+  CHK(drop_dev_bufs(h));
   h->db_valid = false; h->db_rows_valid = false; h->zb_rows = 0xFFFFFFFFu;
-  h->eval_cap = 0; h->eval_unit_cap = 0; h->bits_cap = 0;
-  h->rows_ptr_cap = h->rows_uid_cap = h->rows_col_cap = h->rows_tptr_cap = h->rows_pu_cap = h->rows_tcol_cap = 0;
-  h->cand_ptr_cap = h->cand_col_cap = h->cand_tiles_cap = h->cand_score_cap = h->cand_rank_cap = 0;
-  h->fr_tptr_cap = h->fr_tcol_cap = h->fr_tbits_cap = h->fr_vrows_cap = h->fr_tscore_cap = h->fr_rank_cap = 0;
-  h->flt_eptr_cap = h->flt_ecol_cap = h->flt_allow_cap = h->flt_pos_cap = h->flt_D_cap = h->flt_bp_cap = 0;
-  for (int k = 0; k < 4; ++k) h->guest_cap[k] = h->fold_cap[k] = 0;
-  h->n_guests = 0; h->fold_long_cap = 0;
-  return 0;
-}
-
-template <class T> int dev_alloc(T** p, size_t n) {
-  HIPCHK(hipMalloc((void**)p, std::max<size_t>(n, 1) * sizeof(T)));
-  return 0;
-}
-// grow-only workspace: *p holds at least n units of `per` elements, *cap is the number of units it was allocated for
-template <class T, class S> int ensure_cap(T** p, S* cap, size_t n, size_t per = 1) {
-  if (*cap >= n) return 0;
-  if (*p) HIPCHK(hipFree(*p));
-  *p = nullptr; *cap = 0;
-  CHK(dev_alloc(p, n * per));
-  *cap = (S)n;
+  h->n_guests = 0;
   return 0;
 }
 
@@ -1298,8 +1331,8 @@ constexpr uint32_t EVAL_CHUNK = 32768;
 constexpr uint32_t SHARD_BLOCKS = 3;
 inline uint32_t shard_blocks_of(const cdae_hip* h) { return 1u + (h->cfg.user_factor ? 1u : 0u) + (h->cfg.linear_function ? 1u : 0u); }
 int ensure_eval_ws(cdae_hip* h, uint32_t users, uint32_t units) {
-  CHK(ensure_cap(&h->d_zeval, &h->eval_cap, users, h->Kp));
-  return ensure_cap(&h->d_hpart_eval, &h->eval_unit_cap, units, h->Kp);
+  CHK(h->d_zeval.ensure(users, h->Kp));
+  return h->d_hpart_eval.ensure(units, h->Kp);
 }
 
 inline bool is_user_indexed(uint32_t which) {
@@ -2291,10 +2324,37 @@ void topn_chunk(cdae_hip* h, uint32_t topk, uint64_t u0, uint32_t nu) {
                      (const int64_t*)h->d_test_ptr, (const uint32_t*)h->d_test_col, (double)h->test_users_with_rows, h->d_topn_pu,
                      reinterpret_cast<unsigned long long*>(h->d_topn_out + 8));
 }
-// recommend_kernel over this handle's item rows, for the single handle's general path and an item shard's local lists alike.  A
-// user's score row sits in LDS where num_items floats fit; otherwise the scores of a launch go to a global workspace of <= 256 MiB,
-// which bounds the users of one launch.  prepare(): that decision, the workspaces (lists in d_rec; with_scores: their scores in
-// d_rec_score) and the dynamic-LDS attribute; launch(): one chunk of at most `chunk` users.
+// The tail of both TOPN entry points: the per-row terms `pu` of n rows summed in row order into out16[0, 8) (its hit counts are already
+// in [8, 11)), then the sixteen doubles to the host.
+int topn_finish(cdae_hip* h, const double* pu, uint64_t n, double* out16, double* rets8, uint64_t* hits3) {
+  hipLaunchKernelGGL(cdae::topn_sum_kernel, dim3(1), dim3(64), 0, h->stream, pu, n, out16);
+  HIPCHK(hipGetLastError());
+  double host[16];
+  HIPCHK(hipMemcpyAsync(host, out16, sizeof host, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  for (int c = 0; c < 8; ++c) rets8[c] = host[c];
+  if (hits3) std::memcpy(hits3, host + 8, 3 * sizeof(uint64_t));
+  return 0;
+}
+// The n places of a chunk's lists in d_rec (and their scores in d_rec_score) to the caller's arrays, either of which may be null, then
+// one synchronisation: the two buffers are the next chunk's too.
+int copy_lists_out(cdae_hip* h, size_t n, uint32_t* ids, float* scores) {
+  if (ids) HIPCHK(hipMemcpyAsync(ids, h->d_rec, n * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+  if (scores) HIPCHK(hipMemcpyAsync(scores, h->d_rec_score, n * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+  if (ids || scores) HIPCHK(hipStreamSynchronize(h->stream));
+  return 0;
+}
+// Where the general-path kernels (recommend_kernel, full_rank_general_kernel) keep a row's `items` scores: in LDS where that many
+// floats fit; otherwise the scores of a launch go to a global workspace of <= 256 MiB, which bounds the rows of one launch.
+struct ScorePlace { bool in_lds; size_t shmem; uint32_t rows; };
+ScorePlace score_place(uint64_t items, uint32_t rows) {
+  const size_t lds_scores = (size_t)items * sizeof(float) + 64;
+  if (lds_scores <= 160 * 1024) return {true, lds_scores, rows};
+  return {false, 64, (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(rows, (256ull << 20) / (items * sizeof(float))))};
+}
+// recommend_kernel over this handle's item rows, for the single handle's general path and an item shard's local lists alike.
+// prepare(): score_place's decision, the workspaces (lists in d_rec; with_scores: their scores in d_rec_score) and the dynamic-LDS
+// attribute; launch(): one chunk of at most `chunk` users.
 // prepare(..., items, true) + launch_bits(): the same over `items` rows of any decoder image, masked from a bit table
 // (recommend_kernel<NI, true>: cdae_hip_recommend_rows_filtered); a score row is then `items` floats.
 struct Scorer {
@@ -2303,21 +2363,13 @@ struct Scorer {
   uint32_t chunk = 0, topk = 0;
   int prepare(cdae_hip* h, uint32_t users, uint32_t topk_, bool with_scores_, uint64_t items = 0, bool bits_form = false) {
     if (items == 0) items = h->I;
-    const size_t lds_scores = (size_t)items * sizeof(float) + 64;
-    in_lds = lds_scores <= 160 * 1024;
-    shmem = in_lds ? lds_scores : 64;
-    chunk = users; topk = topk_; with_scores = with_scores_;
-    if (!in_lds) {
-      chunk = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(users, (256ull << 20) / (items * sizeof(float))));
-      CHK(ensure_cap(&h->d_score, &h->score_cap, (size_t)chunk * items));
-    }
-    CHK(ensure_cap(&h->d_rec, &h->rec_cap, (size_t)chunk * topk));
-    if (with_scores) CHK(ensure_cap(&h->d_rec_score, &h->rec_score_cap, (size_t)chunk * topk));
-    const void* kernel = h->NI == 1 ? (const void*)cdae::recommend_kernel<1> : h->NI == 2 ? (const void*)cdae::recommend_kernel<2>
-                       : h->NI == 4 ? (const void*)cdae::recommend_kernel<4> : (const void*)cdae::recommend_kernel<8>;
-    if (bits_form)
-      kernel = h->NI == 1 ? (const void*)cdae::recommend_kernel<1, true> : h->NI == 2 ? (const void*)cdae::recommend_kernel<2, true>
-             : h->NI == 4 ? (const void*)cdae::recommend_kernel<4, true> : (const void*)cdae::recommend_kernel<8, true>;
+    const ScorePlace sp = score_place(items, users);
+    in_lds = sp.in_lds; shmem = sp.shmem; chunk = sp.rows;
+    topk = topk_; with_scores = with_scores_;
+    if (!in_lds) CHK(h->d_score.ensure((size_t)chunk * items));
+    CHK(h->d_rec.ensure((size_t)chunk * topk));
+    if (with_scores) CHK(h->d_rec_score.ensure((size_t)chunk * topk));
+    const void* kernel = bits_form ? KERNEL_OF_NI(h->NI, cdae::recommend_kernel, true) : KERNEL_OF_NI(h->NI, cdae::recommend_kernel);
     HIPCHK(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
     return 0;
   }
@@ -2376,23 +2428,22 @@ int recommend_general(cdae_hip* h, uint64_t u_begin, uint64_t u_end, uint32_t to
                   h->P(CDAE_P_B), (const uint32_t*)nullptr, s0, 1u, 0, h->d_Z, (float*)nullptr, (float*)nullptr, h->d_Uu, (float*)nullptr);
     } else if (!h->mf) {
       rc = ensure_eval_ws(h, nb, h->h_unit_ptr[s0 + nb] - h->h_unit_ptr[s0]);
-      if (!rc) rc = encode_chunk(h, nullptr, s0, nb, 0, CDAE_STREAM_CORRUPT, 0, 0, 0, 0, h->d_zeval, h->d_hpart_eval, h->eval_unit_cap);      // cdae.hpp:167-172
+      if (!rc) rc = encode_chunk(h, nullptr, s0, nb, 0, CDAE_STREAM_CORRUPT, 0, 0, 0, 0, h->d_zeval, h->d_hpart_eval, (uint32_t)h->d_hpart_eval.cap);      // cdae.hpp:167-172
       if (rc) break;
     }
     sc.launch(h, s0, nb, h->mf ? h->d_Wu + (size_t)s0 * h->Kp : (rated ? h->d_Z : h->d_zeval), d_rated, n_rated);
     hipError_t e = hipGetLastError();
     if (e == hipSuccess && h->topn_active) { topn_chunk(h, topk, s0, nb); e = hipGetLastError(); }
-    if (e == hipSuccess && out) e = hipMemcpyAsync(out + (s0 - u_begin) * topk, h->d_rec, (size_t)nb * topk * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream);
-    if (e == hipSuccess && out) e = hipStreamSynchronize(h->stream);
     if (e != hipSuccess) rc = fail("recommend: %s", hipGetErrorString(e));
+    else if (out) rc = copy_lists_out(h, (size_t)nb * topk, out + (s0 - u_begin) * topk, nullptr);
   }
   if (d_rated) (void)hipFree(d_rated);
   return rc;
 }
 
 // recommend(), matrix-core path (topk <= REC_TOPK_MAX, num_dim <= 256): recommend_mfma_kernel over nu hidden rows z and their bit
-// rows in h->d_bits, lists to h->d_rec.  The one place that maps num_dim to the kernel's contraction length.  d_score == nullptr:
-// the instantiations cdae_hip_recommend_all has always launched; otherwise the SCORES ones (cdae_hip_recommend_rows with out_scores).
+// rows in h->d_bits, lists to h->d_rec, the contraction length by dispatch_nch.  d_score == nullptr: the instantiations
+// cdae_hip_recommend_all has always launched; otherwise the SCORES ones (cdae_hip_recommend_rows with out_scores).
 // src != nullptr (cdae_hip_recommend_rows_filtered with an allow list): the sweep runs over src->hp.num_items rows of that decoder
 // image instead of the handle's; the bit table in h->d_bits is then in that index space, and so are the ids of the lists.
 bool mfma_path(const cdae_hip* h, uint32_t topk) { return topk <= (uint32_t)cdae::REC_TOPK_MAX && h->K <= 256; }
@@ -2407,17 +2458,12 @@ int launch_recommend_mfma_as(cdae_hip* h, const float* z, uint32_t nu, uint32_t 
                      topk, h->d_rec, d_score);
   return 0;
 }
-template <bool SCORES>
-int launch_recommend_mfma_nch(cdae_hip* h, const float* z, uint32_t nu, uint32_t words, uint32_t topk, float* d_score, const SweepSrc* src) {
-  if (h->K <= 32) return launch_recommend_mfma_as<4, SCORES>(h, z, nu, words, topk, d_score, src);
-  if (h->K <= 64) return launch_recommend_mfma_as<8, SCORES>(h, z, nu, words, topk, d_score, src);
-  if (h->K <= 128) return launch_recommend_mfma_as<16, SCORES>(h, z, nu, words, topk, d_score, src);
-  if (h->K <= 200) return launch_recommend_mfma_as<25, SCORES>(h, z, nu, words, topk, d_score, src);
-  return launch_recommend_mfma_as<32, SCORES>(h, z, nu, words, topk, d_score, src);
-}
 int launch_recommend_mfma(cdae_hip* h, const float* z, uint32_t nu, uint32_t words, uint32_t topk, float* d_score, const SweepSrc* src = nullptr) {
-  return d_score ? launch_recommend_mfma_nch<true>(h, z, nu, words, topk, d_score, src)
-                 : launch_recommend_mfma_nch<false>(h, z, nu, words, topk, nullptr, src);
+  return dispatch_nch(h->K, [&](auto nch) {
+    constexpr int NCH = decltype(nch)::value;
+    return d_score ? launch_recommend_mfma_as<NCH, true>(h, z, nu, words, topk, d_score, src)
+                   : launch_recommend_mfma_as<NCH, false>(h, z, nu, words, topk, nullptr, src);
+  });
 }
 }  // namespace
 
@@ -2636,7 +2682,7 @@ int cdae_hip_data_loss(cdae_hip_t* h, uint64_t seed, uint32_t epoch, double* out
     const uint32_t n_units = h->h_unit_ptr[s0 + nb] - h->h_unit_ptr[s0];
     CHK(ensure_eval_ws(h, nb, n_units));
     for (uint32_t c = 0; c < h->cfg.num_corruptions; ++c) {       // cdae.hpp:86
-      CHK(encode_chunk(h, nullptr, s0, nb, 1, CDAE_STREAM_LOSS_CORRUPT, c, seed, epoch, 0, h->d_zeval, h->d_hpart_eval, h->eval_unit_cap));
+      CHK(encode_chunk(h, nullptr, s0, nb, 1, CDAE_STREAM_LOSS_CORRUPT, c, seed, epoch, 0, h->d_zeval, h->d_hpart_eval, (uint32_t)h->d_hpart_eval.cap));
       DISPATCH_NI(h->NI, cdae::data_loss_kernel, dim3((n_units + 3) / 4), dim3(256), 0, h->stream, h->hp, h->d_row_ptr, h->d_col,
                   h->d_unit_ptr + s0, n_units, (const uint32_t*)h->d_unit_user, s0, nb, h->d_zeval, h->dec(), h->P(CDAE_P_BP), h->d_scalar);
     }
@@ -2682,22 +2728,19 @@ int cdae_hip_recommend_all(cdae_hip_t* h, uint64_t u_begin, uint64_t u_end, uint
     const uint32_t words = (uint32_t)((h->I + 31) / 32);
     const uint64_t n_all = u_end - u_begin;
     const uint32_t UC = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(n_all, 1), EVAL_CHUNK);
-    CHK(ensure_cap(&h->d_bits, &h->bits_cap, (size_t)UC * words));
-    CHK(ensure_cap(&h->d_rec, &h->rec_cap, (size_t)UC * topk));
+    CHK(h->d_bits.ensure((size_t)UC * words));
+    CHK(h->d_rec.ensure((size_t)UC * topk));
     for (uint64_t c0 = u_begin; c0 < u_end; c0 += UC) {
       const uint32_t nu = (uint32_t)std::min<uint64_t>(UC, u_end - c0);
       if (!h->mf) CHK(ensure_eval_ws(h, nu, h->h_unit_ptr[c0 + nu] - h->h_unit_ptr[c0]));
       hipLaunchKernelGGL(cdae::rated_bits_kernel, dim3((nu + 3) / 4), dim3(256), 0, h->stream, h->d_row_ptr, h->d_col, c0, nu, words, h->d_bits);
       const float* zsrc = h->d_zeval;
       if (h->mf) zsrc = h->d_Wu + (size_t)c0 * h->Kp;      // IMF / BPR: score = ub + ib + uv . iv (imf.hpp:117-119); ub does not rank
-      else CHK(encode_chunk(h, nullptr, c0, nu, 0, CDAE_STREAM_CORRUPT, 0, 0, 0, 0, h->d_zeval, h->d_hpart_eval, h->eval_unit_cap));   // cdae.hpp:167-172, full rows
+      else CHK(encode_chunk(h, nullptr, c0, nu, 0, CDAE_STREAM_CORRUPT, 0, 0, 0, 0, h->d_zeval, h->d_hpart_eval, (uint32_t)h->d_hpart_eval.cap));   // cdae.hpp:167-172, full rows
       CHK(launch_recommend_mfma(h, zsrc, nu, words, topk, nullptr));
       HIPCHK(hipGetLastError());
       if (h->topn_active) { topn_chunk(h, topk, c0, nu); HIPCHK(hipGetLastError()); }
-      if (out) {
-        HIPCHK(hipMemcpyAsync(out + (c0 - u_begin) * topk, h->d_rec, (size_t)nu * topk * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(hipStreamSynchronize(h->stream));
-      }
+      if (out) CHK(copy_lists_out(h, (size_t)nu * topk, out + (c0 - u_begin) * topk, nullptr));
     }
     return 0;
   }
@@ -2742,7 +2785,7 @@ int cdae_hip_eval_topn(cdae_hip_t* h, uint32_t topk, double* rets8, uint64_t* hi
     CHK(cdae_hip_recommend_all(h, 0, h->U, topk, all.data()));
     if (ids_out) std::copy(all.begin(), all.end(), ids_out);
     const uint32_t UC = (uint32_t)std::min<uint64_t>(h->U, EVAL_CHUNK);
-    CHK(ensure_cap(&h->d_rec, &h->rec_cap, (size_t)UC * topk));
+    CHK(h->d_rec.ensure((size_t)UC * topk));
     HIPCHK(hipMemsetAsync(h->d_topn_out, 0, 16 * sizeof(double), h->stream));
     for (uint64_t c0 = 0; c0 < h->U; c0 += UC) {
       const uint32_t nu = (uint32_t)std::min<uint64_t>(UC, h->U - c0);
@@ -2757,14 +2800,7 @@ int cdae_hip_eval_topn(cdae_hip_t* h, uint32_t topk, double* rets8, uint64_t* hi
     h->topn_active = false;
     if (rc) return rc;
   }
-  hipLaunchKernelGGL(cdae::topn_sum_kernel, dim3(1), dim3(64), 0, h->stream, (const double*)h->d_topn_pu, h->U, h->d_topn_out);
-  HIPCHK(hipGetLastError());
-  double host[16];
-  HIPCHK(hipMemcpyAsync(host, h->d_topn_out, sizeof host, hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipStreamSynchronize(h->stream));
-  for (int c = 0; c < 8; ++c) rets8[c] = host[c];
-  if (hits3) std::memcpy(hits3, host + 8, 3 * sizeof(uint64_t));
-  return 0;
+  return topn_finish(h, h->d_topn_pu, h->U, h->d_topn_out, rets8, hits3);
 }
 
 int cdae_hip_recommend_user(cdae_hip_t* h, uint64_t uid, const uint32_t* rated_items, size_t n_rated, uint32_t topk, uint32_t* out) {
@@ -2836,14 +2872,19 @@ int rows_check(cdae_hip* h, const char* fn, const RowsArgs& a) {
   CHK(validate_rows_csr("rated", a.row_ptr, a.col, a.n_rows, h->I));
   return rows_check_uids(h, fn, a.uids, a.n_rows);
 }
+// a host CSR over R rows to a pair of grow-only buffers, on h->stream; one with no items still gets a col buffer, and nothing is copied to it
+int upload_csr(cdae_hip* h, DevBuf<int64_t>& ptr, DevBuf<uint32_t>& col, const int64_t* host_ptr, const uint32_t* host_col, uint64_t R) {
+  const size_t nnz = (size_t)host_ptr[R];
+  CHK(ptr.ensure(R + 1));
+  CHK(col.ensure(std::max<size_t>(nnz, 1)));
+  HIPCHK(hipMemcpyAsync(ptr, host_ptr, (R + 1) * sizeof(int64_t), hipMemcpyHostToDevice, h->stream));
+  if (nnz) HIPCHK(hipMemcpyAsync(col, host_col, nnz * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
+  return 0;
+}
 // the part every rows entry point shares: the rated-set CSR and the uids to the handle's grow-only buffers (on h->stream) ...
 int rows_upload(cdae_hip* h, uint64_t R, const uint32_t* uids, const int64_t* row_ptr, const uint32_t* col) {
-  const size_t nnz = (size_t)row_ptr[R];
-  CHK(ensure_cap(&h->d_rows_ptr, &h->rows_ptr_cap, R + 1));
-  CHK(ensure_cap(&h->d_rows_uid, &h->rows_uid_cap, R));
-  CHK(ensure_cap(&h->d_rows_col, &h->rows_col_cap, std::max<size_t>(nnz, 1)));
-  HIPCHK(hipMemcpyAsync(h->d_rows_ptr, row_ptr, (R + 1) * sizeof(int64_t), hipMemcpyHostToDevice, h->stream));
-  if (nnz) HIPCHK(hipMemcpyAsync(h->d_rows_col, col, nnz * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
+  CHK(upload_csr(h, h->d_rows_ptr, h->d_rows_col, row_ptr, col, R));
+  CHK(h->d_rows_uid.ensure(R));
   if (uids) HIPCHK(hipMemcpyAsync(h->d_rows_uid, uids, R * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
   else HIPCHK(hipMemsetAsync(h->d_rows_uid, 0xFF, R * sizeof(uint32_t), h->stream));          // every row: no user node
   return 0;
@@ -2852,8 +2893,8 @@ inline uint32_t rows_empty_input(const cdae_hip* h) { return h->hp.keep_thr == 0
 // ... and z of rows [c0, c0 + nu) of that CSR to h->d_zeval (nu rows of Kp floats, allocated by the caller)
 int rows_encode_chunk(cdae_hip* h, const int64_t* row_ptr, uint64_t c0, uint32_t nu) {
   const uint32_t empty_input = rows_empty_input(h);
-  const float* Gwu = h->n_guests ? h->d_guest[0] : nullptr;   // the guest table's Wu / Uu rows (uids with the top bit), if there is one
-  const float* Guu = h->n_guests ? h->d_guest[2] : nullptr;
+  const float* Gwu = h->n_guests ? h->d_guest[0].p : nullptr;   // the guest table's Wu / Uu rows (uids with the top bit), if there is one
+  const float* Guu = h->n_guests ? h->d_guest[2].p : nullptr;
   // rows of at most one summation group: a wavefront each; longer ones (if the chunk has any): a workgroup each
   bool any_long = false;
   for (uint64_t r = c0; r < c0 + nu && !any_long && !empty_input; ++r) any_long = row_ptr[r + 1] - row_ptr[r] > (int64_t)h->hp.unit_pos;
@@ -2866,66 +2907,20 @@ int rows_encode_chunk(cdae_hip* h, const int64_t* row_ptr, uint64_t c0, uint32_t
                 (const float*)h->P(CDAE_P_W), (const float*)h->d_Wu, (const float*)h->d_Uu, (const float*)h->P(CDAE_P_B), h->d_zeval, Gwu, Guu);
   return 0;
 }
-int rows_run(cdae_hip* h, const RowsArgs& a) {
-  HIPCHK(hipSetDevice(h->device));
-  CHK(join_aux(h));
-  const uint64_t R = a.n_rows;
-  CHK(rows_upload(h, R, a.uids, a.row_ptr, a.col));
-  if (a.t_ptr) {
-    const size_t tnnz = (size_t)a.t_ptr[R];
-    CHK(ensure_cap(&h->d_rows_tptr, &h->rows_tptr_cap, R + 1));
-    CHK(ensure_cap(&h->d_rows_pu, &h->rows_pu_cap, R, 8));
-    CHK(ensure_cap(&h->d_rows_tcol, &h->rows_tcol_cap, std::max<size_t>(tnnz, 1)));
-    if (!h->d_rows_out) CHK(dev_alloc(&h->d_rows_out, 16));
-    HIPCHK(hipMemcpyAsync(h->d_rows_tptr, a.t_ptr, (R + 1) * sizeof(int64_t), hipMemcpyHostToDevice, h->stream));
-    if (tnnz) HIPCHK(hipMemcpyAsync(h->d_rows_tcol, a.t_col, tnnz * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemsetAsync(h->d_rows_out, 0, 16 * sizeof(double), h->stream));
-  }
-  const uint32_t topk = a.topk;
-  const bool with_scores = a.out_scores != nullptr;
-  const bool mfma = mfma_path(h, topk);
-  const uint32_t words = (uint32_t)((h->I + 31) / 32);
-  Scorer sc;
-  uint32_t UC = (uint32_t)std::min<uint64_t>(R, EVAL_CHUNK);
-  if (mfma) {
-    CHK(ensure_cap(&h->d_bits, &h->bits_cap, (size_t)UC * words));
-    CHK(ensure_cap(&h->d_rec, &h->rec_cap, (size_t)UC * topk));
-    if (with_scores) CHK(ensure_cap(&h->d_rec_score, &h->rec_score_cap, (size_t)UC * topk));
-  } else {
-    CHK(sc.prepare(h, (uint32_t)std::min<uint64_t>(R, 4096u), topk, with_scores));
-    UC = sc.chunk;
-  }
-  CHK(ensure_cap(&h->d_zeval, &h->eval_cap, UC, h->Kp));
-  for (uint64_t c0 = 0; c0 < R; c0 += UC) {
-    const uint32_t nu = (uint32_t)std::min<uint64_t>(UC, R - c0);
-    CHK(rows_encode_chunk(h, a.row_ptr, c0, nu));
-    if (mfma) {
-      hipLaunchKernelGGL(cdae::rated_bits_kernel, dim3((nu + 3) / 4), dim3(256), 0, h->stream, (const int64_t*)h->d_rows_ptr,
-                         (const uint32_t*)h->d_rows_col, c0, nu, words, h->d_bits);
-      CHK(launch_recommend_mfma(h, h->d_zeval, nu, words, topk, with_scores ? h->d_rec_score : nullptr));
-    } else {
-      sc.launch(h, c0, nu, h->d_zeval, nullptr, 0, h->d_rows_ptr, h->d_rows_col);
-    }
-    HIPCHK(hipGetLastError());
-    if (a.t_ptr) {
-      hipLaunchKernelGGL(cdae::topn_user_kernel, dim3((nu + 255) / 256), dim3(256), 0, h->stream, (const uint32_t*)h->d_rec, topk, c0, nu,
-                         (const int64_t*)h->d_rows_tptr, (const uint32_t*)h->d_rows_tcol, (double)a.with_targets, h->d_rows_pu,
-                         reinterpret_cast<unsigned long long*>(h->d_rows_out + 8));
-      HIPCHK(hipGetLastError());
-    }
-    if (a.out_ids) HIPCHK(hipMemcpyAsync(a.out_ids + c0 * topk, h->d_rec, (size_t)nu * topk * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
-    if (with_scores) HIPCHK(hipMemcpyAsync(a.out_scores + c0 * topk, h->d_rec_score, (size_t)nu * topk * sizeof(float), hipMemcpyDeviceToHost, h->stream));
-    if (a.out_ids || with_scores) HIPCHK(hipStreamSynchronize(h->stream));                   // one per chunk: d_rec is the next chunk's too
-  }
-  return 0;
-}
-
-// ---- filtered top-k (cdae_hip_recommend_rows_filtered) --------------------------------------------------------------------------------
-// rows_run's shape with the mask as a table of its own: filter_bits_kernel builds a chunk's exclusion rows (rated rows if the call
-// excludes them | excl rows) and both top-k paths mask from them.  With an allow list the call first packs the allowed decoder rows
-// (once, not per chunk; rebuilt by every call: the decoder can change behind the library's back through cdae_hip_param_device_ptr),
-// the sweeps run over the pack with a by-value copy of hp whose num_items is n_allow, and the lists' places are mapped back to ids.
-struct FilterArgs { const int64_t* excl_ptr; const uint32_t* excl_col; bool exclude_rated; const uint32_t* allow; uint64_t n_allow; };
+// ---- the top-k run of every rows entry point (cdae_hip_recommend_rows, cdae_hip_eval_topn_rows, cdae_hip_recommend_rows_filtered) ------
+// A chunk's rows are encoded, filter_bits_kernel builds their exclusion rows (rated rows if the call excludes them | excl rows) as a bit
+// table and both top-k paths mask from it; the unfiltered entry points are the run with "exclude rated, no excl rows, no allow list".
+// A run with exactly that filter masks from the rated CSR as it is — rated_bits_kernel in front of the matrix cores, recommend_kernel's
+// own CSR mask on the general path, the kernels those entry points have always launched: through the bit table the general path took
+// 0.7 % longer, outside the spread of two runs of the old code (profiles/rows_refactor_ab.txt).  The lists are the same bits either way
+// (tests/test_gpu_rows_filtered.py::test_no_filter_is_recommend_rows).
+// With an allow list the call first packs the allowed decoder rows (once, not per chunk; rebuilt by every call: the decoder can change
+// behind the library's back through cdae_hip_param_device_ptr), the sweeps run over the pack with a by-value copy of hp whose
+// num_items is n_allow, and the lists' places are mapped back to ids.  With targets every chunk's lists are scored on the device.
+struct FilterArgs {
+  const int64_t* excl_ptr = nullptr; const uint32_t* excl_col = nullptr; bool exclude_rated = true;
+  const uint32_t* allow = nullptr; uint64_t n_allow = 0;
+};
 int validate_allow(const char* fn, const uint32_t* allow, uint64_t n_allow, uint64_t I) {
   if (!allow) return n_allow ? fail("%s: null allow_items with n_allow = %llu", fn, (unsigned long long)n_allow) : 0;
   if (n_allow == 0) return fail("%s: an allow list with n_allow = 0 (pass allow_items = NULL for the whole catalogue)", fn);
@@ -2936,65 +2931,75 @@ int validate_allow(const char* fn, const uint32_t* allow, uint64_t n_allow, uint
   }
   return 0;
 }
-int rows_filtered_run(cdae_hip* h, const RowsArgs& a, const FilterArgs& f) {
+int rows_run(cdae_hip* h, const RowsArgs& a, const FilterArgs& f = FilterArgs{}) {
   HIPCHK(hipSetDevice(h->device));
   CHK(join_aux(h));
   const uint64_t R = a.n_rows;
   CHK(rows_upload(h, R, a.uids, a.row_ptr, a.col));
-  if (f.excl_ptr) {
-    const size_t ennz = (size_t)f.excl_ptr[R];
-    CHK(ensure_cap(&h->d_flt_eptr, &h->flt_eptr_cap, R + 1));
-    CHK(ensure_cap(&h->d_flt_ecol, &h->flt_ecol_cap, std::max<size_t>(ennz, 1)));
-    HIPCHK(hipMemcpyAsync(h->d_flt_eptr, f.excl_ptr, (R + 1) * sizeof(int64_t), hipMemcpyHostToDevice, h->stream));
-    if (ennz) HIPCHK(hipMemcpyAsync(h->d_flt_ecol, f.excl_col, ennz * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
+  if (a.t_ptr) {
+    CHK(upload_csr(h, h->d_rows_tptr, h->d_rows_tcol, a.t_ptr, a.t_col, R));
+    CHK(h->d_rows_pu.ensure(R, 8));
+    if (!h->d_rows_out) CHK(dev_alloc(&h->d_rows_out, 16));
+    HIPCHK(hipMemsetAsync(h->d_rows_out, 0, 16 * sizeof(double), h->stream));
   }
+  if (f.excl_ptr) CHK(upload_csr(h, h->d_flt_eptr, h->d_flt_ecol, f.excl_ptr, f.excl_col, R));
   const uint64_t n = f.allow ? f.n_allow : h->I;                   // the index space of the sweep
   SweepSrc src{h->hp, h->dec(), h->P(CDAE_P_BP)};
   if (f.allow) {
     const uint32_t na = (uint32_t)f.n_allow;
-    CHK(ensure_cap(&h->d_flt_allow, &h->flt_allow_cap, na));
-    CHK(ensure_cap(&h->d_flt_pos, &h->flt_pos_cap, h->I));
-    CHK(ensure_cap(&h->d_flt_D, &h->flt_D_cap, na, h->Kp));
-    CHK(ensure_cap(&h->d_flt_bp, &h->flt_bp_cap, na));
+    CHK(h->d_flt_allow.ensure(na));
+    CHK(h->d_flt_pos.ensure(h->I));
+    CHK(h->d_flt_D.ensure(na, h->Kp));
+    CHK(h->d_flt_bp.ensure(na));
     HIPCHK(hipMemcpyAsync(h->d_flt_allow, f.allow, na * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
     HIPCHK(hipMemsetAsync(h->d_flt_pos, 0xFF, h->I * sizeof(uint32_t), h->stream));
-    hipLaunchKernelGGL(cdae::allow_pos_kernel, dim3((na + 255) / 256), dim3(256), 0, h->stream, (const uint32_t*)h->d_flt_allow, na, h->d_flt_pos);
+    hipLaunchKernelGGL(cdae::allow_pos_kernel, dim3((na + 255) / 256), dim3(256), 0, h->stream, (const uint32_t*)h->d_flt_allow, na, h->d_flt_pos.p);
     DISPATCH_NI(h->NI, cdae::pack_decoder_kernel, dim3((na + cdae::PACK_WAVES - 1) / cdae::PACK_WAVES), dim3(cdae::PACK_WAVES * cdae::WAVE), 0,
-                h->stream, (const uint32_t*)h->d_flt_allow, na, h->Kp, src.D, src.bp, h->d_flt_D, h->d_flt_bp);
+                h->stream, (const uint32_t*)h->d_flt_allow, na, h->Kp, src.D, src.bp, h->d_flt_D.p, h->d_flt_bp.p);
     HIPCHK(hipGetLastError());
     src.hp.num_items = na; src.D = h->d_flt_D; src.bp = h->d_flt_bp;
   }
   const uint32_t topk = a.topk;
   const bool with_scores = a.out_scores != nullptr;
   const bool mfma = mfma_path(h, topk);
+  const bool csr_mask = f.exclude_rated && !f.excl_ptr && !f.allow;     // the mask is the rated CSR and nothing else
   const uint32_t words = (uint32_t)((n + 31) / 32);
   Scorer sc;
   uint32_t UC = (uint32_t)std::min<uint64_t>(R, EVAL_CHUNK);
   if (mfma) {
-    CHK(ensure_cap(&h->d_rec, &h->rec_cap, (size_t)UC * topk));
-    if (with_scores) CHK(ensure_cap(&h->d_rec_score, &h->rec_score_cap, (size_t)UC * topk));
+    CHK(h->d_rec.ensure((size_t)UC * topk));
+    if (with_scores) CHK(h->d_rec_score.ensure((size_t)UC * topk));
   } else {
-    CHK(sc.prepare(h, (uint32_t)std::min<uint64_t>(R, 4096u), topk, with_scores, n, true));
+    CHK(sc.prepare(h, (uint32_t)std::min<uint64_t>(R, 4096u), topk, with_scores, n, !csr_mask));
     UC = sc.chunk;
   }
-  CHK(ensure_cap(&h->d_bits, &h->bits_cap, (size_t)UC * words));
-  CHK(ensure_cap(&h->d_zeval, &h->eval_cap, UC, h->Kp));
+  if (mfma || !csr_mask) CHK(h->d_bits.ensure((size_t)UC * words));
+  CHK(h->d_zeval.ensure(UC, h->Kp));
   for (uint64_t c0 = 0; c0 < R; c0 += UC) {
     const uint32_t nu = (uint32_t)std::min<uint64_t>(UC, R - c0);
     CHK(rows_encode_chunk(h, a.row_ptr, c0, nu));
-    hipLaunchKernelGGL(cdae::filter_bits_kernel, dim3((nu + 3) / 4), dim3(256), 0, h->stream,
-                       f.exclude_rated ? (const int64_t*)h->d_rows_ptr : (const int64_t*)nullptr, (const uint32_t*)h->d_rows_col,
-                       f.excl_ptr ? (const int64_t*)h->d_flt_eptr : (const int64_t*)nullptr, (const uint32_t*)h->d_flt_ecol,
-                       f.allow ? (const uint32_t*)h->d_flt_pos : (const uint32_t*)nullptr, c0, nu, words, h->d_bits);
-    if (mfma) CHK(launch_recommend_mfma(h, h->d_zeval, nu, words, topk, with_scores ? h->d_rec_score : nullptr, f.allow ? &src : nullptr));
+    if (!csr_mask)
+      hipLaunchKernelGGL(cdae::filter_bits_kernel, dim3((nu + 3) / 4), dim3(256), 0, h->stream,
+                         f.exclude_rated ? (const int64_t*)h->d_rows_ptr : (const int64_t*)nullptr, (const uint32_t*)h->d_rows_col,
+                         f.excl_ptr ? (const int64_t*)h->d_flt_eptr : (const int64_t*)nullptr, (const uint32_t*)h->d_flt_ecol,
+                         f.allow ? (const uint32_t*)h->d_flt_pos : (const uint32_t*)nullptr, c0, nu, words, h->d_bits.p);
+    else if (mfma)
+      hipLaunchKernelGGL(cdae::rated_bits_kernel, dim3((nu + 3) / 4), dim3(256), 0, h->stream, (const int64_t*)h->d_rows_ptr,
+                         (const uint32_t*)h->d_rows_col, c0, nu, words, h->d_bits.p);
+    if (mfma) CHK(launch_recommend_mfma(h, h->d_zeval, nu, words, topk, with_scores ? h->d_rec_score.p : nullptr, f.allow ? &src : nullptr));
+    else if (csr_mask) sc.launch(h, c0, nu, h->d_zeval, nullptr, 0, h->d_rows_ptr, h->d_rows_col);
     else sc.launch_bits(h, src.hp, nu, h->d_zeval, src.D, src.bp, h->d_bits, words);
     if (f.allow)
       hipLaunchKernelGGL(cdae::remap_ids_kernel, dim3((uint32_t)(((size_t)nu * topk + 255) / 256)), dim3(256), 0, h->stream,
-                         (const uint32_t*)h->d_flt_allow, (size_t)nu * topk, h->d_rec);
+                         (const uint32_t*)h->d_flt_allow, (size_t)nu * topk, h->d_rec.p);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(a.out_ids + c0 * topk, h->d_rec, (size_t)nu * topk * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
-    if (with_scores) HIPCHK(hipMemcpyAsync(a.out_scores + c0 * topk, h->d_rec_score, (size_t)nu * topk * sizeof(float), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));                       // one per chunk: d_rec is the next chunk's too
+    if (a.t_ptr) {
+      hipLaunchKernelGGL(cdae::topn_user_kernel, dim3((nu + 255) / 256), dim3(256), 0, h->stream, (const uint32_t*)h->d_rec, topk, c0, nu,
+                         (const int64_t*)h->d_rows_tptr, (const uint32_t*)h->d_rows_tcol, (double)a.with_targets, h->d_rows_pu.p,
+                         reinterpret_cast<unsigned long long*>(h->d_rows_out + 8));
+      HIPCHK(hipGetLastError());
+    }
+    CHK(copy_lists_out(h, (size_t)nu * topk, a.out_ids ? a.out_ids + c0 * topk : nullptr, with_scores ? a.out_scores + c0 * topk : nullptr));
   }
   return 0;
 }
@@ -3049,14 +3054,11 @@ int score_run(cdae_hip* h, uint64_t R, const uint32_t* uids, const int64_t* row_
   std::vector<ScoreChunk> chunks;
   score_plan(R, cp, h->h_cand_tiles, chunks);
   const size_t per_chunk = std::min<size_t>(total, (size_t)SCORE_CAND_CHUNK);
-  CHK(ensure_cap(&h->d_cand_ptr, &h->cand_ptr_cap, R + 1));
-  CHK(ensure_cap(&h->d_cand_col, &h->cand_col_cap, total));
-  CHK(ensure_cap(&h->d_cand_tiles, &h->cand_tiles_cap, h->h_cand_tiles.size()));
-  CHK(ensure_cap(&h->d_cand_score, &h->cand_score_cap, per_chunk));
-  if (out_ranks) CHK(ensure_cap(&h->d_cand_rank, &h->cand_rank_cap, per_chunk));
-  CHK(ensure_cap(&h->d_zeval, &h->eval_cap, (size_t)std::min<uint64_t>(R, EVAL_CHUNK), h->Kp));
-  HIPCHK(hipMemcpyAsync(h->d_cand_ptr, cp, (R + 1) * sizeof(int64_t), hipMemcpyHostToDevice, h->stream));
-  HIPCHK(hipMemcpyAsync(h->d_cand_col, cc, total * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
+  CHK(upload_csr(h, h->d_cand_ptr, h->d_cand_col, cp, cc, R));
+  CHK(h->d_cand_tiles.ensure(h->h_cand_tiles.size()));
+  CHK(h->d_cand_score.ensure(per_chunk));
+  if (out_ranks) CHK(h->d_cand_rank.ensure(per_chunk));
+  CHK(h->d_zeval.ensure((size_t)std::min<uint64_t>(R, EVAL_CHUNK), h->Kp));
   HIPCHK(hipMemcpyAsync(h->d_cand_tiles, h->h_cand_tiles.data(), h->h_cand_tiles.size() * sizeof(uint2), hipMemcpyHostToDevice, h->stream));
   for (const ScoreChunk& c : chunks) {
     if (c.encode) CHK(rows_encode_chunk(h, row_ptr, c.c0, c.nu));
@@ -3130,12 +3132,8 @@ int launch_full_rank_mfma_as(cdae_hip* h, const FrChunk& c, uint32_t words) {
   }
   return 0;
 }
-int launch_full_rank_mfma(cdae_hip* h, const FrChunk& c, uint32_t words) {   // NCH by num_dim as launch_recommend_mfma_nch maps it
-  if (h->K <= 32) return launch_full_rank_mfma_as<4>(h, c, words);
-  if (h->K <= 64) return launch_full_rank_mfma_as<8>(h, c, words);
-  if (h->K <= 128) return launch_full_rank_mfma_as<16>(h, c, words);
-  if (h->K <= 200) return launch_full_rank_mfma_as<25>(h, c, words);
-  return launch_full_rank_mfma_as<32>(h, c, words);
+int launch_full_rank_mfma(cdae_hip* h, const FrChunk& c, uint32_t words) {
+  return dispatch_nch(h->K, [&](auto nch) { return launch_full_rank_mfma_as<decltype(nch)::value>(h, c, words); });
 }
 
 int full_rank_run(cdae_hip* h, uint64_t R, const uint32_t* uids, const int64_t* row_ptr, const uint32_t* col, const int64_t* tp,
@@ -3145,35 +3143,24 @@ int full_rank_run(cdae_hip* h, uint64_t R, const uint32_t* uids, const int64_t* 
   CHK(rows_upload(h, R, uids, row_ptr, col));
   const bool mfma = h->K <= 256;
   const uint32_t words = (uint32_t)((h->I + 31) / 32);
-  // general path: recommend_kernel's placement of a row's scores (Scorer::prepare)
-  const size_t lds_scores = (size_t)h->I * sizeof(float) + 64;
-  const bool in_lds = lds_scores <= 160 * 1024;
-  const size_t shmem = in_lds ? lds_scores : 64;
-  uint32_t rows_max = EVAL_CHUNK;
-  if (!mfma) rows_max = in_lds ? 4096u : (uint32_t)std::max<uint64_t>(1, (256ull << 20) / ((uint64_t)h->I * sizeof(float)));
+  const ScorePlace sp = score_place(h->I, 4096u);                  // general path: recommend_kernel's placement of a row's scores
   std::vector<FrChunk> chunks;
-  full_rank_plan(R, tp, rows_max, mfma, h->h_fr_vrows, chunks);
+  full_rank_plan(R, tp, mfma ? EVAL_CHUNK : sp.rows, mfma, h->h_fr_vrows, chunks);
   size_t rows_cap = 0, targets_cap = 0;
   for (const FrChunk& c : chunks)
     if (c.p1 > c.p0) { rows_cap = std::max<size_t>(rows_cap, c.nu); targets_cap = std::max<size_t>(targets_cap, (size_t)(c.p1 - c.p0)); }
-  const size_t total = (size_t)tp[R];
-  CHK(ensure_cap(&h->d_fr_tptr, &h->fr_tptr_cap, R + 1));
-  CHK(ensure_cap(&h->d_fr_tcol, &h->fr_tcol_cap, total));
-  CHK(ensure_cap(&h->d_fr_tscore, &h->fr_tscore_cap, targets_cap));
-  CHK(ensure_cap(&h->d_fr_rank, &h->fr_rank_cap, targets_cap));
-  CHK(ensure_cap(&h->d_zeval, &h->eval_cap, rows_cap, h->Kp));
-  HIPCHK(hipMemcpyAsync(h->d_fr_tptr, tp, (R + 1) * sizeof(int64_t), hipMemcpyHostToDevice, h->stream));
-  HIPCHK(hipMemcpyAsync(h->d_fr_tcol, tc, total * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
+  CHK(upload_csr(h, h->d_fr_tptr, h->d_fr_tcol, tp, tc, R));
+  CHK(h->d_fr_tscore.ensure(targets_cap));
+  CHK(h->d_fr_rank.ensure(targets_cap));
+  CHK(h->d_zeval.ensure(rows_cap, h->Kp));
   if (mfma) {
-    CHK(ensure_cap(&h->d_bits, &h->bits_cap, rows_cap * words));
-    CHK(ensure_cap(&h->d_fr_tbits, &h->fr_tbits_cap, rows_cap * words));
-    CHK(ensure_cap(&h->d_fr_vrows, &h->fr_vrows_cap, h->h_fr_vrows.size()));
+    CHK(h->d_bits.ensure(rows_cap * words));
+    CHK(h->d_fr_tbits.ensure(rows_cap * words));
+    CHK(h->d_fr_vrows.ensure(h->h_fr_vrows.size()));
     HIPCHK(hipMemcpyAsync(h->d_fr_vrows, h->h_fr_vrows.data(), h->h_fr_vrows.size() * sizeof(uint2), hipMemcpyHostToDevice, h->stream));
   } else {
-    if (!in_lds) CHK(ensure_cap(&h->d_score, &h->score_cap, rows_cap * h->I));
-    const void* kernel = h->NI == 1 ? (const void*)cdae::full_rank_general_kernel<1> : h->NI == 2 ? (const void*)cdae::full_rank_general_kernel<2>
-                       : h->NI == 4 ? (const void*)cdae::full_rank_general_kernel<4> : (const void*)cdae::full_rank_general_kernel<8>;
-    HIPCHK(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
+    if (!sp.in_lds) CHK(h->d_score.ensure(rows_cap * h->I));
+    HIPCHK(hipFuncSetAttribute(KERNEL_OF_NI(h->NI, cdae::full_rank_general_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sp.shmem));
   }
   for (const FrChunk& c : chunks) {
     if (c.p1 == c.p0) continue;                                    // no row of the chunk has targets: nothing to launch, nothing to write
@@ -3186,9 +3173,9 @@ int full_rank_run(cdae_hip* h, uint64_t R, const uint32_t* uids, const int64_t* 
                          (const uint32_t*)h->d_fr_tcol, c.c0, c.nu, words, h->d_fr_tbits);
       CHK(launch_full_rank_mfma(h, c, words));
     } else {
-      DISPATCH_NI(h->NI, cdae::full_rank_general_kernel, dim3(c.nu), dim3(256), shmem, h->stream, h->hp, (const int64_t*)h->d_rows_ptr,
+      DISPATCH_NI(h->NI, cdae::full_rank_general_kernel, dim3(c.nu), dim3(256), sp.shmem, h->stream, h->hp, (const int64_t*)h->d_rows_ptr,
                   (const uint32_t*)h->d_rows_col, (const int64_t*)h->d_fr_tptr, (const uint32_t*)h->d_fr_tcol, c.c0, c.p0, (const float*)h->d_zeval,
-                  (const float*)h->dec(), (const float*)h->P(CDAE_P_BP), in_lds ? (float*)nullptr : h->d_score, h->d_fr_tscore, h->d_fr_rank);
+                  (const float*)h->dec(), (const float*)h->P(CDAE_P_BP), sp.in_lds ? (float*)nullptr : h->d_score.p, h->d_fr_tscore, h->d_fr_rank);
     }
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(out_ranks + c.p0, h->d_fr_rank, nt * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
@@ -3217,12 +3204,12 @@ int guest_table_check(cdae_hip* h, const char* fn, uint64_t n) {
   if (n > GUEST_USERS_MAX) return fail("%s: at most %llu guest nodes, got %llu", fn, (unsigned long long)GUEST_USERS_MAX, (unsigned long long)n);
   return 0;
 }
-int ensure_nodes(cdae_hip* h, float* (&p)[4], size_t (&cap)[4], size_t rows) {
-  for (int k = 0; k < 4; ++k) CHK(ensure_cap(&p[k], &cap[k], rows, h->Kp));
+int ensure_nodes(cdae_hip* h, DevBuf<float> (&b)[4], size_t rows) {
+  for (int k = 0; k < 4; ++k) CHK(b[k].ensure(rows, h->Kp));
   return 0;
 }
 void install_staged(cdae_hip* h, uint64_t n) {       // the staging rows become the table (and the old table the next call's staging rows)
-  for (int k = 0; k < 4; ++k) { std::swap(h->d_guest[k], h->d_fold[k]); std::swap(h->guest_cap[k], h->fold_cap[k]); }
+  std::swap(h->d_guest, h->d_fold);
   h->n_guests = n;
 }
 struct FoldCall {
@@ -3234,7 +3221,7 @@ int fold_run(cdae_hip* h, uint64_t R, const uint32_t* uids, const int64_t* row_p
   CHK(join_aux(h));
   CHK(rows_upload(h, R, uids, row_ptr, col));
   const uint32_t UC = (uint32_t)std::min<uint64_t>(R, EVAL_CHUNK);
-  CHK(ensure_nodes(h, h->d_fold, h->fold_cap, f.install ? (size_t)R : (size_t)UC));
+  CHK(ensure_nodes(h, h->d_fold, f.install ? (size_t)R : (size_t)UC));
   // the long rows of every chunk, as slots inside their chunk: they take the leading workgroups of the chunk's launch
   std::vector<size_t>& long_off = h->h_fold_long_off;
   long_off.clear();
@@ -3245,13 +3232,13 @@ int fold_run(cdae_hip* h, uint64_t R, const uint32_t* uids, const int64_t* row_p
       if (cdae::fold_row_is_long((uint64_t)(row_ptr[r + 1] - row_ptr[r]), h->hp.num_neg)) h->h_fold_long.push_back((uint32_t)(r - c0));
   }
   long_off.push_back(h->h_fold_long.size());
-  CHK(ensure_cap(&h->d_fold_long, &h->fold_long_cap, std::max<size_t>(h->h_fold_long.size(), 1)));
+  CHK(h->d_fold_long.ensure(std::max<size_t>(h->h_fold_long.size(), 1)));
   if (!h->h_fold_long.empty())
     HIPCHK(hipMemcpyAsync(h->d_fold_long, h->h_fold_long.data(), h->h_fold_long.size() * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
   const cdae::FoldArgs a{f.seed, f.stream_id_base, f.epoch_begin, f.n_epochs, h->cfg.num_corruptions};
   const bool g = h->n_guests != 0;
-  const cdae::FoldNodes nd{h->d_Wu, h->d_Wu_ag, h->d_Uu, h->d_Uu_ag, g ? h->d_guest[0] : nullptr, g ? h->d_guest[1] : nullptr,
-                           g ? h->d_guest[2] : nullptr, g ? h->d_guest[3] : nullptr};
+  const cdae::FoldNodes nd{h->d_Wu, h->d_Wu_ag, h->d_Uu, h->d_Uu_ag, g ? h->d_guest[0].p : nullptr, g ? h->d_guest[1].p : nullptr,
+                           g ? h->d_guest[2].p : nullptr, g ? h->d_guest[3].p : nullptr};
   size_t chunk = 0;
   for (uint64_t c0 = 0; c0 < R; c0 += UC, ++chunk) {
     const uint32_t nu = (uint32_t)std::min<uint64_t>(UC, R - c0);
@@ -3303,7 +3290,7 @@ int cdae_hip_set_guest_nodes(cdae_hip_t* h, uint64_t n_guests, const float* wu, 
   if (n_guests == 0) { h->n_guests = 0; return 0; }
   HIPCHK(hipSetDevice(h->device));
   CHK(join_aux(h));
-  CHK(ensure_nodes(h, h->d_fold, h->fold_cap, (size_t)n_guests));
+  CHK(ensure_nodes(h, h->d_fold, (size_t)n_guests));
   const float* host[4] = {wu, wu_ag, uu, uu_ag};
   const size_t count = (size_t)n_guests * h->Kp;
   for (int k = 0; k < 4; ++k) {
@@ -3380,7 +3367,7 @@ int cdae_hip_recommend_rows_filtered(cdae_hip_t* h, uint64_t n_rows, const uint3
   if (n_rows == 0) return 0;
   if (excl_row_ptr) CHK(validate_rows_csr("excl", excl_row_ptr, excl_col, n_rows, h->I));
   if (!out_ids) return fail("%s: null out_ids", fn);
-  return rows_filtered_run(h, a, FilterArgs{excl_row_ptr, excl_col, exclude_rated != 0, allow_items, n_allow});
+  return rows_run(h, a, FilterArgs{excl_row_ptr, excl_col, exclude_rated != 0, allow_items, n_allow});
 }
 
 int cdae_hip_eval_topn_rows(cdae_hip_t* h, uint64_t n_rows, const uint32_t* uids, const int64_t* row_ptr, const uint32_t* col,
@@ -3393,14 +3380,7 @@ int cdae_hip_eval_topn_rows(cdae_hip_t* h, uint64_t n_rows, const uint32_t* uids
   for (uint64_t r = 0; r < n_rows; ++r) a.with_targets += target_row_ptr[r + 1] > target_row_ptr[r];
   if (a.with_targets == 0) return fail("cdae_hip_eval_topn_rows: no row has target items");
   CHK(rows_run(h, a));
-  hipLaunchKernelGGL(cdae::topn_sum_kernel, dim3(1), dim3(64), 0, h->stream, (const double*)h->d_rows_pu, n_rows, h->d_rows_out);
-  HIPCHK(hipGetLastError());
-  double host[16];
-  HIPCHK(hipMemcpyAsync(host, h->d_rows_out, sizeof host, hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipStreamSynchronize(h->stream));
-  for (int c = 0; c < 8; ++c) rets8[c] = host[c];
-  if (hits3) std::memcpy(hits3, host + 8, 3 * sizeof(uint64_t));
-  return 0;
+  return topn_finish(h, h->d_rows_pu, n_rows, h->d_rows_out, rets8, hits3);
 }
 
 int cdae_hip_train_one_user_corruption(cdae_hip_t* h, uint64_t uid, const uint32_t* input_items, size_t n_in,
@@ -3839,7 +3819,7 @@ int ev_phase0(cdae_hip_t* h, uint64_t u0, uint32_t nu, int mode, uint32_t cidx, 
   CHK(join_aux(h));
   const uint32_t n_units = h->h_unit_ptr[u0 + nu] - h->h_unit_ptr[u0];
   CHK(ensure_eval_ws(h, nu, std::max<uint32_t>(n_units, 1u)));
-  CHK(ensure_cap(&h->d_hsum_eval, &h->hsum_eval_cap, nu, (size_t)SHARD_BLOCKS * h->Kp));
+  CHK(h->d_hsum_eval.ensure(nu, (size_t)SHARD_BLOCKS * h->Kp));
   const uint32_t* uptr = h->d_unit_ptr + u0;
   if (n_units)
     DISPATCH_NI(h->NI, cdae::encode_partial_kernel, dim3((n_units + 3) / 4), dim3(256), 0, h->stream, h->hp, h->d_row_ptr, h->d_col,
@@ -3883,9 +3863,7 @@ int ev_recommend(cdae_hip_t* h, uint64_t u0, uint32_t nu, uint32_t topk, uint32_
     const uint32_t nb = std::min(sc.chunk, nu - c0);
     sc.launch(h, u0 + c0, nb, h->d_zeval + (size_t)c0 * h->Kp);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(ids + (size_t)c0 * topk, h->d_rec, (size_t)nb * topk * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipMemcpyAsync(scores + (size_t)c0 * topk, h->d_rec_score, (size_t)nb * topk * sizeof(float), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
+    CHK(copy_lists_out(h, (size_t)nb * topk, ids + (size_t)c0 * topk, scores + (size_t)c0 * topk));
   }
   return 0;
 }
