@@ -32,6 +32,8 @@ IMF_DEFAULT_BATCH_USERS = 16   # CDAE_IMF_DEFAULT_BATCH_USERS / CDAE_BPR_DEFAULT
 BPR_DEFAULT_BATCH_USERS = 8    # with batch_users = 0 trains on a BASELINE-sized data set (cdae_hip_mf_default_batch_users); 1 on smaller ones
 RANK_CANDIDATES_MAX = 4096     # CDAE_RANK_CANDIDATES_MAX (include/cdae_hip.h): candidates per row that score_rows ranks
 NO_USER = 0xFFFFFFFF           # CDAE_NO_USER (include/cdae_hip.h): a row of recommend_rows / eval_topn_rows without a user node
+ITEMS_OUTPUT, ITEMS_INPUT = 0, 1   # CDAE_ITEMS_OUTPUT / CDAE_ITEMS_INPUT (include/cdae_hip.h): the item table similar_items compares rows of
+SIM_DOT, SIM_COSINE = 0, 1         # CDAE_SIM_DOT / CDAE_SIM_COSINE (include/cdae_hip.h): its score
 DEFAULT_BATCH_USERS = 0        # 0 = the library's default (cdae_hip_default_batch_users: num_users / 160, within [32, 256])
 
 
@@ -107,6 +109,8 @@ EXPORTS = {
     "cdae_hip_recommend_rows": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
     "cdae_hip_recommend_rows_filtered": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
                                                    C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "cdae_hip_similar_items": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_uint32, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p]),
     "cdae_hip_score_rows": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "cdae_hip_full_rank_rows": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "cdae_hip_eval_topn_rows": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
@@ -470,6 +474,36 @@ class CDAE:
         _chk(self.lib, self.lib.cdae_hip_recommend_rows_filtered(
             self.h, n, None if ru is None else ru.ctypes.data, rp.ctypes.data, rc.ctypes.data,
             None if ep is None else ep.ctypes.data, None if ep is None else ec.ctypes.data, 1 if exclude_rated else 0,
+            None if al is None else al_buf.ctypes.data, 0 if al is None else al.size, topk, ids.ctypes.data,
+            scores.ctypes.data if with_scores else None))
+        return (ids, scores) if with_scores else ids
+
+    def similar_items(self, items, topk: int = 10, metric: str = "cosine", table: str = "output", exclude_self: bool = True, exclude=None,
+                      allow=None, with_scores: bool = False):
+        """The topk items closest to each of `items` (cdae_hip_similar_items).  metric: "cosine" or "dot"; table: "output" (the rows
+        the scores are made of: V when asymmetric, else W) or "input" (W, the rows the encoder sums; an IMF / BPR model has one item
+        table and both name it); exclude_self=False: a query may list itself; exclude: a (ptr, col) CSR over the queries of items
+        that must not be listed (None: none); allow: ONE ascending unique item list for the whole call, the only items that may be
+        listed (None: the whole catalogue; the queries need not be in it) -> ids [n_queries, topk] uint32 (0xFFFFFFFF beyond a
+        query's candidates), or (ids, scores) with the fp32 scores."""
+        metrics = {"dot": SIM_DOT, "cosine": SIM_COSINE}
+        tables = {"output": ITEMS_OUTPUT, "input": ITEMS_INPUT}
+        if metric not in metrics or table not in tables:
+            raise ValueError('metric is "dot" or "cosine", table is "output" or "input"')
+        q = np.ascontiguousarray(items, dtype=np.uint32).reshape(-1)
+        n = q.size
+        ep = ec = None
+        if exclude is not None:
+            ep, ec, _ = self._rows(exclude[0], exclude[1], None)
+            if ep.size != n + 1:
+                raise ValueError("the exclude CSR covers the queries")
+        al = None if allow is None else np.ascontiguousarray(allow, dtype=np.uint32).reshape(-1)
+        al_buf = al if al is None or al.size else np.zeros(1, dtype=np.uint32)      # an empty list is still a list: the library refuses it
+        ids = np.empty((n, topk), dtype=np.uint32)
+        scores = np.empty((n, topk), dtype=np.float32) if with_scores else None
+        _chk(self.lib, self.lib.cdae_hip_similar_items(
+            self.h, n, q.ctypes.data, tables[table], metrics[metric], 1 if exclude_self else 0,
+            None if ep is None else ep.ctypes.data, None if ep is None else ec.ctypes.data,
             None if al is None else al_buf.ctypes.data, 0 if al is None else al.size, topk, ids.ctypes.data,
             scores.ctypes.data if with_scores else None))
         return (ids, scores) if with_scores else ids

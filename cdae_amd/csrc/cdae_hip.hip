@@ -282,6 +282,12 @@ struct cdae_hip {
   DevBuf<int64_t> d_flt_eptr;
   DevBuf<uint32_t> d_flt_ecol, d_flt_allow, d_flt_pos;
   DevBuf<float> d_flt_D, d_flt_bp;
+  // cdae_hip_similar_items: the queries, the row_ptr that makes them a one-item-per-row CSR (0, 1, 2, ...), the table image of the call
+  // (gathered and / or normalised rows; rebuilt by every call that needs one) and the +0.0 bias (zero-filled where it grows, never
+  // written again); the excl CSR, the allow list and its inverse share d_flt_*.  Grow-only, freed with the handle
+  DevBuf<uint32_t> d_sim_q;
+  DevBuf<int64_t> d_sim_iota;
+  DevBuf<float> d_sim_T, d_sim_zero;
   // Guest table (cdae_hip_set_guest_nodes, cdae_hip_fold_in_rows with install): a second user table, rows wu | wu_ag | uu | uu_ag of
   // [n_guests x Kp] each, that the rows entry points address as CDAE_GUEST_USER(i).  d_fold: the staging rows the fold-in kernel writes
   // (a chunk's, or the whole call's when it installs); installing EXCHANGES the two sets, so a failed call leaves the table as it was.
@@ -548,6 +554,7 @@ int drop_dev_bufs(cdae_hip* h) {
        h->d_cand_ptr, h->d_cand_col, h->d_cand_tiles, h->d_cand_score, h->d_cand_rank,
        h->d_fr_tptr, h->d_fr_tcol, h->d_fr_tbits, h->d_fr_vrows, h->d_fr_tscore, h->d_fr_rank,
        h->d_flt_eptr, h->d_flt_ecol, h->d_flt_allow, h->d_flt_pos, h->d_flt_D, h->d_flt_bp,
+       h->d_sim_q, h->d_sim_iota, h->d_sim_T, h->d_sim_zero,
        h->d_guest[0], h->d_guest[1], h->d_guest[2], h->d_guest[3], h->d_fold[0], h->d_fold[1], h->d_fold[2], h->d_fold[3],
        h->d_fold_long);
   return rc;
@@ -3004,6 +3011,95 @@ int rows_run(cdae_hip* h, const RowsArgs& a, const FilterArgs& f = FilterArgs{})
   return 0;
 }
 
+// ---- top-k item neighbours (cdae_hip_similar_items) -----------------------------------------------------------------------------------
+// rows_run with the encoder replaced by a gather: the hidden row of query q is row q of the item table T (COSINE: divided by its norm),
+// the swept image is T itself (DOT without an allow list: in place), or the allowed and / or normalised rows gathered once per call
+// (rebuilt by every call: the parameters can change behind the library's back through cdae_hip_param_device_ptr), the bias is a buffer
+// of +0.0.  The mask is filter_bits_kernel's: its "rated" CSR is (0, 1, 2, ... ; query_items) when the query itself is excluded, its
+// excl CSR the caller's, its pos the allow list's inverse.  Both sweep kernels run as rows_run runs them with an allow list, and the
+// lists' places are mapped back to ids.  One host synchronisation per chunk.
+struct SimilarArgs {
+  uint64_t n_queries; const uint32_t* query_items; const float* T; bool cosine, exclude_self;
+  uint32_t topk; uint32_t* out_ids; float* out_scores;
+};
+// out[p] = row ids[p] (ids == nullptr: row p) of T for p < n, normalised when `cosine`
+template <int NI>
+void gather_rows_as(cdae_hip* h, bool cosine, const uint32_t* ids, uint32_t n, const float* T, float* out) {
+  const dim3 grid((n + cdae::PACK_WAVES - 1) / cdae::PACK_WAVES), block(cdae::PACK_WAVES * cdae::WAVE);
+  if (cosine) hipLaunchKernelGGL((cdae::gather_rows_kernel<NI, true>), grid, block, 0, h->stream, ids, n, h->Kp, T, out);
+  else hipLaunchKernelGGL((cdae::gather_rows_kernel<NI, false>), grid, block, 0, h->stream, ids, n, h->Kp, T, out);
+}
+void gather_rows(cdae_hip* h, bool cosine, const uint32_t* ids, uint32_t n, const float* T, float* out) {
+  switch (h->NI) {
+    case 1: gather_rows_as<1>(h, cosine, ids, n, T, out); break;
+    case 2: gather_rows_as<2>(h, cosine, ids, n, T, out); break;
+    case 4: gather_rows_as<4>(h, cosine, ids, n, T, out); break;
+    default: gather_rows_as<8>(h, cosine, ids, n, T, out); break;
+  }
+}
+int similar_run(cdae_hip* h, const SimilarArgs& a, const FilterArgs& f) {
+  HIPCHK(hipSetDevice(h->device));
+  CHK(join_aux(h));
+  const uint64_t Q = a.n_queries;
+  CHK(h->d_sim_q.ensure(Q));
+  HIPCHK(hipMemcpyAsync(h->d_sim_q, a.query_items, Q * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
+  if (a.exclude_self) {
+    CHK(h->d_sim_iota.ensure(Q + 1));
+    hipLaunchKernelGGL(cdae::iota_ptr_kernel, dim3((uint32_t)((Q + 1 + 255) / 256)), dim3(256), 0, h->stream, (size_t)(Q + 1), h->d_sim_iota.p);
+  }
+  if (f.excl_ptr) CHK(upload_csr(h, h->d_flt_eptr, h->d_flt_ecol, f.excl_ptr, f.excl_col, Q));
+  const uint32_t n = (uint32_t)(f.allow ? f.n_allow : h->I);           // the index space of the sweep
+  if (f.allow) {
+    CHK(h->d_flt_allow.ensure(n));
+    CHK(h->d_flt_pos.ensure(h->I));
+    HIPCHK(hipMemcpyAsync(h->d_flt_allow, f.allow, (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemsetAsync(h->d_flt_pos, 0xFF, h->I * sizeof(uint32_t), h->stream));
+    hipLaunchKernelGGL(cdae::allow_pos_kernel, dim3((n + 255) / 256), dim3(256), 0, h->stream, (const uint32_t*)h->d_flt_allow, n, h->d_flt_pos.p);
+  }
+  const bool grew = h->d_sim_zero.cap < n;
+  CHK(h->d_sim_zero.ensure(n));
+  if (grew) HIPCHK(hipMemsetAsync(h->d_sim_zero, 0, h->d_sim_zero.cap * sizeof(float), h->stream));
+  SweepSrc src{h->hp, a.T, h->d_sim_zero};
+  src.hp.num_items = n;
+  if (a.cosine || f.allow) {                                           // the table image of this call
+    CHK(h->d_sim_T.ensure(n, h->Kp));
+    gather_rows(h, a.cosine, f.allow ? (const uint32_t*)h->d_flt_allow : (const uint32_t*)nullptr, n, a.T, h->d_sim_T.p);
+    src.D = h->d_sim_T;
+  }
+  HIPCHK(hipGetLastError());
+  const uint32_t topk = a.topk;
+  const bool with_scores = a.out_scores != nullptr;
+  const bool mfma = mfma_path(h, topk);
+  const uint32_t words = (n + 31) / 32;
+  Scorer sc;
+  uint32_t UC = (uint32_t)std::min<uint64_t>(Q, EVAL_CHUNK);
+  if (mfma) {
+    CHK(h->d_rec.ensure((size_t)UC * topk));
+    if (with_scores) CHK(h->d_rec_score.ensure((size_t)UC * topk));
+  } else {
+    CHK(sc.prepare(h, (uint32_t)std::min<uint64_t>(Q, 4096u), topk, with_scores, n, true));
+    UC = sc.chunk;
+  }
+  CHK(h->d_bits.ensure((size_t)UC * words));
+  CHK(h->d_zeval.ensure(UC, h->Kp));
+  for (uint64_t c0 = 0; c0 < Q; c0 += UC) {
+    const uint32_t nu = (uint32_t)std::min<uint64_t>(UC, Q - c0);
+    gather_rows(h, a.cosine, (const uint32_t*)h->d_sim_q + c0, nu, a.T, h->d_zeval.p);
+    hipLaunchKernelGGL(cdae::filter_bits_kernel, dim3((nu + 3) / 4), dim3(256), 0, h->stream,
+                       a.exclude_self ? (const int64_t*)h->d_sim_iota : (const int64_t*)nullptr, (const uint32_t*)h->d_sim_q,
+                       f.excl_ptr ? (const int64_t*)h->d_flt_eptr : (const int64_t*)nullptr, (const uint32_t*)h->d_flt_ecol,
+                       f.allow ? (const uint32_t*)h->d_flt_pos : (const uint32_t*)nullptr, c0, nu, words, h->d_bits.p);
+    if (mfma) CHK(launch_recommend_mfma(h, h->d_zeval, nu, words, topk, with_scores ? h->d_rec_score.p : nullptr, &src));
+    else sc.launch_bits(h, src.hp, nu, h->d_zeval, src.D, src.bp, h->d_bits, words);
+    if (f.allow)
+      hipLaunchKernelGGL(cdae::remap_ids_kernel, dim3((uint32_t)(((size_t)nu * topk + 255) / 256)), dim3(256), 0, h->stream,
+                         (const uint32_t*)h->d_flt_allow, (size_t)nu * topk, h->d_rec.p);
+    HIPCHK(hipGetLastError());
+    CHK(copy_lists_out(h, (size_t)nu * topk, a.out_ids + c0 * topk, with_scores ? a.out_scores + c0 * topk : nullptr));
+  }
+  return 0;
+}
+
 // ---- scores and ranks of caller-supplied candidates (cdae_hip_score_rows) ------------------------------------------------------------
 // Candidates per chunk: a chunk takes whole candidate rows while they fit; a row of more candidates than this (scores only: ranks stop
 // at CDAE_RANK_CANDIDATES_MAX) is cut into chunks of exactly this many, so a row of num_items candidates fits whatever num_items is.
@@ -3368,6 +3464,29 @@ int cdae_hip_recommend_rows_filtered(cdae_hip_t* h, uint64_t n_rows, const uint3
   if (excl_row_ptr) CHK(validate_rows_csr("excl", excl_row_ptr, excl_col, n_rows, h->I));
   if (!out_ids) return fail("%s: null out_ids", fn);
   return rows_run(h, a, FilterArgs{excl_row_ptr, excl_col, exclude_rated != 0, allow_items, n_allow});
+}
+
+int cdae_hip_similar_items(cdae_hip_t* h, uint64_t n_queries, const uint32_t* query_items, uint32_t table, uint32_t metric, int exclude_self,
+                           const int64_t* excl_row_ptr, const uint32_t* excl_col, const uint32_t* allow_items, uint64_t n_allow,
+                           uint32_t topk, uint32_t* out_ids, float* out_scores) {
+  const char* fn = "cdae_hip_similar_items";
+  if (!h) return fail("%s: null handle", fn);
+  if (h->item_shard) return fail("%s applies to a whole model, not to an item shard", fn);
+  if (!h->d_shared) return fail("%s: cdae_hip_set_interactions first", fn);
+  if (table != CDAE_ITEMS_OUTPUT && table != CDAE_ITEMS_INPUT) return fail("%s: unknown table %u", fn, table);
+  if (metric != CDAE_SIM_DOT && metric != CDAE_SIM_COSINE) return fail("%s: unknown metric %u", fn, metric);
+  if (topk == 0 || topk > h->I) return fail("%s: topk must be in [1, num_items]", fn);
+  CHK(validate_allow(fn, allow_items, n_allow, h->I));
+  if (n_queries == 0) return 0;
+  if (!query_items) return fail("%s: null query_items", fn);
+  for (uint64_t q = 0; q < n_queries; ++q)
+    if (query_items[q] >= h->I) return fail("%s: query_items[%llu] = %u is out of range", fn, (unsigned long long)q, query_items[q]);
+  if (excl_row_ptr) CHK(validate_rows_csr("excl", excl_row_ptr, excl_col, n_queries, h->I));
+  if (!out_ids) return fail("%s: null out_ids", fn);
+  // on an IMF / BPR handle the item factors are the one item table (CDAE_P_W); dec() is that table there
+  const float* T = table == CDAE_ITEMS_INPUT ? h->P(CDAE_P_W) : h->dec();
+  const SimilarArgs a{n_queries, query_items, T, metric == CDAE_SIM_COSINE, exclude_self != 0, topk, out_ids, out_scores};
+  return similar_run(h, a, FilterArgs{excl_row_ptr, excl_col, false, allow_items, n_allow});
 }
 
 int cdae_hip_eval_topn_rows(cdae_hip_t* h, uint64_t n_rows, const uint32_t* uids, const int64_t* row_ptr, const uint32_t* col,

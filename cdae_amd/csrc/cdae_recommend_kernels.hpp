@@ -824,6 +824,45 @@ pack_decoder_kernel(const uint32_t* __restrict__ allow, uint32_t n_allow, uint32
   if (lane == 0) bpp[p] = bp[item];
 }
 
+// ---- similar items (cdae_hip_similar_items): top-k item neighbours by dot or cosine ---------------------------------------------------
+// The sweeps above take the table, the hidden rows and the mask as data, so "the items nearest to item q" is a sweep whose hidden row is
+// a row of the item table itself: z := T[q] (DOT) or T[q] / |T[q]| (COSINE) over the rows T[i] or T[i] / |T[i]|, a bias of +0.0.
+// gather_rows_kernel makes both operands and is the only arithmetic the entry point adds:
+//   out[p] = T[ids[p]] (ids == nullptr: T[p]), whole rows of Kp floats, a wavefront per row as in pack_decoder_kernel; under COSINE the
+//   row divided by its norm, in the one order include/cdae_hip.h states: lane l adds the squares of its NI elements in ascending order
+//   in fp64, the 64 partials are added by six __shfl_xor steps of distance 1, 2, 4, 8, 16, 32 (fp64 addition commutes, so every lane
+//   holds the bits of the balanced tree over neighbouring lanes), n = (float)sqrt(ss) and x / n are correctly rounded, and a row with
+//   ss == 0 becomes +0.0 everywhere.  (The square of an fp32 value is exact in fp64, so a contraction of the multiply and the add into
+//   one fma changes no bit.)  A row's image depends on that row alone: a query's row and its place in the table image are the same bits.
+template <int NI, bool COSINE>
+__global__ void __launch_bounds__(PACK_WAVES * WAVE)
+gather_rows_kernel(const uint32_t* __restrict__ ids, uint32_t n, uint32_t Kp, const float* __restrict__ T, float* __restrict__ out) {
+  const uint32_t wid = threadIdx.x / WAVE, lane = threadIdx.x % WAVE;
+  const uint32_t p = blockIdx.x * PACK_WAVES + wid;
+  if (p >= n) return;                                              // (wavefront-uniform, no barrier in this kernel)
+  const uint32_t row = ids ? ids[p] : p;
+  float v[NI];
+  vload<NI>(v, T + (size_t)row * Kp + lane * NI);
+  if constexpr (COSINE) {
+    double ss = 0.0;
+#pragma unroll
+    for (int i = 0; i < NI; ++i) ss = ss + (double)v[i] * (double)v[i];
+#pragma unroll
+    for (int off = 1; off < WAVE; off <<= 1) ss = ss + __shfl_xor(ss, off, WAVE);
+    const float norm = (float)__dsqrt_rn(ss);
+#pragma unroll
+    for (int i = 0; i < NI; ++i) v[i] = ss == 0.0 ? 0.f : __fdiv_rn(v[i], norm);
+  }
+  vstore<NI>(out + (size_t)p * Kp + lane * NI, v);
+}
+
+// ptr[i] = i over [n]: with the queries as its columns, the CSR whose row r holds query r alone (exclude_self through filter_bits_kernel)
+__global__ void __launch_bounds__(256)
+iota_ptr_kernel(size_t n, int64_t* __restrict__ ptr) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) ptr[i] = (int64_t)i;
+}
+
 // ids[i] = allow[ids[i]] over the [n] places of a chunk's lists; the sentinel stays the sentinel
 __global__ void __launch_bounds__(256)
 remap_ids_kernel(const uint32_t* __restrict__ allow, size_t n, uint32_t* __restrict__ ids) {

@@ -34,6 +34,8 @@
  *   CDAE::get_output_values              cdae.hpp:418-426    cdae_hip_score_rows
  *   TOPN_Evaluation::evaluate            evaluation.hpp:113-181, evaluate_rec_list :183-219
  *                                                            cdae_hip_set_test_rows + cdae_hip_eval_topn
+ *   (item neighbours by dot / cosine; no reference counterpart)
+ *                                                            cdae_hip_similar_items
  *   (data-parallel exchange; no reference counterpart)       cdae_hip_delta_*, cdae_hip_comm_*, cdae_hip_exchange_*,
  *                                                            cdae_hip_multi_* (Solver<CDAE>::train on N GPUs)
  *
@@ -83,7 +85,9 @@ extern "C" {
  *     cdae_hip_guest_nodes, CDAE_GUEST_USER — batched fold-in of user nodes for rows outside the training set, and a guest table that serves the fitted nodes
  *     to the rows entry points
  *     also under 12, the version unchanged (a new entry point; nothing existing changed): cdae_hip_recommend_rows_filtered — batched top-k
- *     with an item allow list for the call and per-row exclusions that are not inputs (or inputs that are not exclusions) */
+ *     with an item allow list for the call and per-row exclusions that are not inputs (or inputs that are not exclusions)
+ *     also under 12, the version unchanged (a new entry point; nothing existing changed): cdae_hip_similar_items, CDAE_ITEMS_OUTPUT /
+ *     CDAE_ITEMS_INPUT, CDAE_SIM_DOT / CDAE_SIM_COSINE — batched top-k item neighbours of named items by dot product or cosine */
 #define CDAE_HIP_ABI_VERSION 12
 
 /* numeric values follow libcf::LossType (/root/reference/src/model/loss.hpp:10-18) */
@@ -478,6 +482,53 @@ int cdae_hip_recommend_rows_filtered(cdae_hip_t* h, uint64_t n_rows, const uint3
                                      const int64_t* excl_row_ptr, const uint32_t* excl_col, int exclude_rated,
                                      const uint32_t* allow_items, uint64_t n_allow,
                                      uint32_t topk, uint32_t* out_ids, float* out_scores);
+
+/* The item page: the topk items closest to each of many named items, by dot product or cosine over one of the model's item tables —
+ * the similar_items of a matrix-factorisation library, and the offline build of an item-to-item table.  The reference has no
+ * counterpart; this comment is the definition.
+ *   queries  query_items[n_queries]: any item, any number of times, in any order.  An id >= num_items is an error that names the
+ *            position.  n_queries == 0 succeeds and touches nothing.
+ *   table    T [num_items x num_dim].  CDAE_ITEMS_OUTPUT: D, the rows the scores are made of (V when asymmetric, else W);
+ *            CDAE_ITEMS_INPUT: W, the rows the encoder sums.  On an IMF / BPR handle both name the item factors iv_ (CDAE_P_W).
+ *            Biases take no part.  A full_output handle is served from its fp32 rows like any other.
+ *   score    CDAE_SIM_DOT: s(q, i) = T[i] . T[q].  CDAE_SIM_COSINE: s(q, i) = N[i] . N[q], N being T normalised row by row:
+ *            ss_i is accumulated in fp64 in one fixed order — lane l of 64 owns elements [l NI, (l + 1) NI) of the row stride
+ *            (cdae_hip_row_stride() = 64 NI; pad elements are zero) and adds its squares in ascending order,
+ *            p = p + (double)x * (double)x from p = 0; the 64 partials are added as the balanced tree over neighbouring lanes that
+ *            cdae_hip_score_rows documents — n_i = (float)sqrt(ss_i), and N[i][k] = T[i][k] / n_i, a correctly rounded fp32
+ *            division (the library is built without fast-math).  A row with ss_i == 0 normalises to zeros, so every score with it is
+ *            +0.0, never NaN.  A row's normalised form depends on that row alone.
+ *   which arithmetic (part of the contract)
+ *            the dot product is the arithmetic of the path, chosen as everywhere: num_dim <= 256 and topk <= 16 run
+ *            recommend_all's matrix-core chain with the table row as the A operand, the query row as the B operand and a bias of
+ *            +0.0 added last; anything else runs the general path's fused multiply-add chain over the lane's elements, the
+ *            wavefront sum, + 0.0.  On either path s(q, i) has the bits of s(i, q): the products commute and the chain order is
+ *            the same.
+ *   candidates
+ *            C_q = allow \ excl_q (\ {q} when exclude_self != 0).  allow_items[n_allow]: ONE list for the whole call, ascending and
+ *            unique; NULL with n_allow == 0 is the whole catalogue, a non-NULL list with n_allow == 0 is an error — exactly
+ *            cdae_hip_recommend_rows_filtered's rules and error texts.  excl_row_ptr[n_queries + 1] / excl_col: a host CSR over the
+ *            queries, items ascending and unique inside a row (validated; an error names the row); NULL: none.  The query's own
+ *            vector never depends on allow or excl: a query outside the allow list is served like any other.
+ *   result   the first topk items of C_q in cdae_hip_recommend_all's total order: descending score, equal scores by ascending
+ *            ORIGINAL item id; surplus places hold 0xFFFFFFFF / -INFINITY.  topk in [1, num_items].  out_scores may be NULL.
+ *   position independence
+ *            a query's list and scores do not depend on what else the call holds, on its place in the call, or on the chunking.
+ * Refused (the handle stays usable): item shards, calls before cdae_hip_set_interactions, an unknown table or metric.  Every validation
+ * error is raised before anything is launched.
+ * The table image of a call (the allowed and / or normalised rows; CDAE_SIM_DOT without an allow list sweeps the handle's table in
+ * place) is made once per call and rebuilt by every call.  Everything lives in grow-only device buffers of the handle (freed with it): a
+ * steady-state call allocates nothing.  Queries are taken in chunks of at most 32 768 (the general path's chunk is that of
+ * cdae_hip_recommend_rows' general path, sized by the swept item count) with one host synchronisation per chunk. */
+#define CDAE_ITEMS_OUTPUT 0u   /* D: V when asymmetric, else W — the rows the scores are made of */
+#define CDAE_ITEMS_INPUT  1u   /* W: the rows the encoder sums */
+#define CDAE_SIM_DOT    0u
+#define CDAE_SIM_COSINE 1u
+int cdae_hip_similar_items(cdae_hip_t* h, uint64_t n_queries, const uint32_t* query_items,
+                           uint32_t table, uint32_t metric, int exclude_self,
+                           const int64_t* excl_row_ptr, const uint32_t* excl_col,
+                           const uint32_t* allow_items, uint64_t n_allow,
+                           uint32_t topk, uint32_t* out_ids, float* out_scores);
 
 /* Fold-in: fit the user node of MANY rows that are no train rows, with everything shared frozen — the strong-generalisation protocol
  * (train on some users; for an unseen user fit only their own node on part of their history, rank the rest), and the warm re-fit of a

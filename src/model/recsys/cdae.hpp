@@ -47,6 +47,7 @@
 #include <base/parallel.hpp>
 #include <base/random.hpp>
 #include <model/recsys/recsys_model_base.hpp>
+#include <model/recsys/similar_items.hpp>
 
 #define CDAE_HIP_CHECK(call) CHECK_EQ((call), 0) << "libcdae_hip: " << cdae_hip_last_error() << " "
 
@@ -333,6 +334,22 @@ class CDAE : public RecsysModelBase {
     for (size_t r = 0; r < n; ++r)
       for (size_t i = 0; i < topk && ids[r * topk + i] != 0xFFFFFFFFu; ++i) out[r].push_back(ids[r * topk + i]);
     return out;
+  }
+
+  // The item page, in ONE device call (cdae_hip_similar_items): the topk items closest to each of `items` by cosine
+  // (CDAE_SIM_COSINE) or dot product (CDAE_SIM_DOT) over the output table (CDAE_ITEMS_OUTPUT: V when asymmetric, else W) or the input
+  // table (CDAE_ITEMS_INPUT: W); biases take no part.  exclude_self = false lets an item list itself; excluded_sets[r] must not be
+  // listed for items[r] (empty vector of sets: none anywhere); allow, when not empty, is ONE item list for the whole call ("more like
+  // this within a category"; the queries need not be in it).  Descending score, equal scores by ascending item id; shorter than topk
+  // when fewer candidates are left.  Single-handle models only; serialised on the handle's mutex like recommend().
+  std::vector<std::vector<size_t>> similar_items(const std::vector<size_t>& items, size_t topk, uint32_t metric = CDAE_SIM_COSINE,
+                                                 uint32_t table = CDAE_ITEMS_OUTPUT, bool exclude_self = true,
+                                                 const std::vector<std::vector<size_t>>& excluded_sets = std::vector<std::vector<size_t>>(),
+                                                 const std::vector<size_t>& allow = std::vector<size_t>()) const {
+    CHECK(!multi_) << "similar_items() is provided for a model on one device";
+    std::lock_guard<std::mutex> lk(*mu_);
+    CHECK(ready()) << "reset() must be called first";
+    return similar_items_on(dev_.get(), num_items_, items, topk, metric, table, exclude_self, excluded_sets, allow);
   }
 
   // get_output_values(z, idx) (cdae.hpp:418-426 of the reference) for many rows in ONE device call (cdae_hip_score_rows): row r is

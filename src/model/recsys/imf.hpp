@@ -25,6 +25,7 @@
 #include <base/mat.hpp>
 #include <base/random.hpp>
 #include <model/recsys/recsys_model_base.hpp>
+#include <model/recsys/similar_items.hpp>
 
 #ifndef CDAE_HIP_CHECK
 #define CDAE_HIP_CHECK(call) CHECK_EQ((call), 0) << "libcdae_hip: " << cdae_hip_last_error() << " "
@@ -127,6 +128,17 @@ class IMF : public RecsysModelBase {
     std::vector<size_t> out(topk);
     for (size_t i = 0; i < topk; ++i) out[i] = sorted[i].first;
     return out;
+  }
+  // The item page, in ONE device call (cdae_hip_similar_items): the topk items closest to each of `items` by cosine (CDAE_SIM_COSINE)
+  // or dot product (CDAE_SIM_DOT) of their item factors; the item bias takes no part, and both values of `table` name the one item
+  // table.  exclude_self, excluded_sets and allow as in libcf::CDAE::similar_items.
+  std::vector<std::vector<size_t>> similar_items(const std::vector<size_t>& items, size_t topk, uint32_t metric = CDAE_SIM_COSINE,
+                                                 uint32_t table = CDAE_ITEMS_OUTPUT, bool exclude_self = true,
+                                                 const std::vector<std::vector<size_t>>& excluded_sets = std::vector<std::vector<size_t>>(),
+                                                 const std::vector<size_t>& allow = std::vector<size_t>()) const {
+    std::lock_guard<std::mutex> lk(*mu_);
+    CHECK(dev_ != nullptr) << "reset() must be called first";
+    return similar_items_on(dev_.get(), num_items_, items, topk, metric, table, exclude_self, excluded_sets, allow);
   }
   // TOPN_Evaluation on the device (evaluation.hpp:113-219 -> cdae_hip_eval_topn): the validation rows go over once per data set
   // (`generation` identifies their contents), the eight means come back; nothing else crosses PCIe
