@@ -367,11 +367,15 @@ class CDAE:
     def synchronize(self):
         _chk(self.lib, self.lib.cdae_hip_synchronize(self.h))
 
+    def _batch_examples(self, u_begin: int, n_users: int) -> int:
+        """examples in the item-sorted list of the batch of users [u_begin, u_begin + n_users)"""
+        nnz = int(self._row_ptr[u_begin + n_users] - self._row_ptr[u_begin])
+        return nnz * (1 if self.cfg.full_output else 1 + self.cfg.num_neg)
+
     def debug_sample_batch(self, seed: int, epoch: int, u_begin: int, n_users: int, cidx: int = 0) -> dict:
         """Integer work of one batch (masks, negatives, item sort, segments, duplicate numbering) copied back from the
         device (cdae_hip_debug_sample_batch) — the bit-exact parity tests compare it with the oracle's draws."""
-        nnz = int(self._row_ptr[u_begin + n_users] - self._row_ptr[u_begin])
-        E = nnz * (1 if self.cfg.full_output else 1 + self.cfg.num_neg)
+        E = self._batch_examples(u_begin, n_users)
         out = {"ex_item": np.empty(E, np.uint32), "ex_val": np.empty(E, np.uint64), "sorted_item": np.empty(E, np.uint32),
                "sorted_val": np.empty(E, np.uint64), "seg_begin": np.empty(self.num_items, np.uint32),
                "seg_end": np.empty(self.num_items, np.uint32), "dup_of_pos": np.empty(E, np.uint32),
@@ -713,6 +717,13 @@ class MF(CDAE):
         if which in (P_UB, P_UB_AG):
             return (self.num_users,)
         return CDAE._shape(self, which)
+
+    def _batch_examples(self, u_begin: int, n_users: int) -> int:
+        """debug_sample_batch of an IMF / BPR handle: the window is in TRAINING POSITIONS (user_order), an IMF positive gives
+        1 + num_neg examples (one per instance), a BPR positive 2 * num_neg (two per pair) — cdae_mf_kernels.hpp mf_sample_kernel"""
+        lens = np.diff(self._row_ptr)[self.user_order().astype(np.int64)]
+        nnz = int(lens[u_begin:u_begin + n_users].sum())
+        return nnz * (2 * self.cfg.num_neg if self.cfg.pairwise else 1 + self.cfg.num_neg)
 
 
 def comm_unique_id() -> bytes:

@@ -11,7 +11,12 @@
 //            contributions run in (user, instance) order: grad = +-g * uv_before + 2 lambda * row   (the item-major order comes
 //            from the same sort + segment table as CDAE's decode).
 // A block of ONE user runs phase U with IN_PLACE = true: the item rows are stepped at once — the reference loop itself,
-// duplicate negatives of the user included.  tests/test_gpu_mf.py checks both against oracle/mf_oracle.cpp.
+// duplicate negatives of the user included.  Against oracle/mf_oracle.cpp (DESIGN.md §8b has the table):
+//   tests/test_gpu_mf.py          both schedules at the default hyper-parameters; the in-place loop at K = 24 (NI = 1), every loss
+//   tests/test_gpu_mf_tiers.py    the in-place loop at NI = 1, 2, 4, 8 (both edges of every K tier) on data whose repeats cross the
+//                                 conflict window and the chunk boundary (tests/mf_conflict_ref.py); the block schedule with plain SGD,
+//                                 without bias terms, with num_neg = 1 and 12
+//   tests/test_gpu_mf_integer.py  mf_sample_kernel's two instance layouts and the sort behind it, bit for bit
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -229,6 +234,9 @@ mf_user_kernel(HyperParams hp, uint32_t bias_term, const int64_t* __restrict__ r
         // that group's steps): if one of the instances x - 2 PF .. x - 1 of this chunk stepped one of its rows, what sits in the
         // registers is from before that step — wait for the stores and read again.  (Negatives are rejected against the user's
         // positives, so this is a duplicate negative inside eight instances, or BPR's positive item, which its num_neg pairs share.)
+        // The farthest step a prefetch cannot see is 2 PF - 1 back (slot PF - 1 of a group fetched in front of the PF steps of the
+        // group before it): the window of 2 PF holds one instance more than that.  tests/test_gpu_mf_tiers.py passes with a window
+        // of 2 PF - 1 and fails with 2 PF - 2.
         const uint32_t w0 = x > 2u * (uint32_t)PF ? x - 2u * (uint32_t)PF : 0u;
         const bool in_window = lane >= w0 && lane < x;
         const bool hit = in_window && (ci == it || (PAIR && (cj == it || ci == jt || cj == jt)));

@@ -143,8 +143,9 @@ def test_recommend_and_reported_loss(built, pairwise):
     assert m.current_loss(1, 0) == 0.0                        # ModelBase::data_loss / penalty_loss defaults (model_base.hpp:36-45)
 
 
-def test_user_with_duplicate_negatives_and_many_items(built):
-    """few items: a user draws the same negative several times — in the sequential schedule the second visit must see the first's step"""
+def test_user_with_duplicate_negatives_and_few_items(built):
+    """few items: a user draws the same negative several times — in the sequential schedule the second visit must see the first's step.
+    No user here reaches a second 64-instance chunk (rows of at most 9 items); tests/test_gpu_mf_tiers.py covers that on D40."""
     rng = np.random.default_rng(2)
     rows = [np.sort(rng.choice(12, n, replace=False)).astype(np.uint32) for n in (3, 8, 5, 9, 2, 7)]
     ptr = np.r_[0, np.cumsum([r.size for r in rows])].astype(np.int64)
