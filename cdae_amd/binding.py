@@ -32,6 +32,7 @@ IMF_DEFAULT_BATCH_USERS = 16   # CDAE_IMF_DEFAULT_BATCH_USERS / CDAE_BPR_DEFAULT
 BPR_DEFAULT_BATCH_USERS = 8    # with batch_users = 0 trains on a BASELINE-sized data set (cdae_hip_mf_default_batch_users); 1 on smaller ones
 RANK_CANDIDATES_MAX = 4096     # CDAE_RANK_CANDIDATES_MAX (include/cdae_hip.h): candidates per row that score_rows ranks
 NO_USER = 0xFFFFFFFF           # CDAE_NO_USER (include/cdae_hip.h): a row of recommend_rows / eval_topn_rows without a user node
+ALS_USERS, ALS_ITEMS = 0, 1         # CDAE_ALS_USERS / CDAE_ALS_ITEMS: the side a WRMF half-step solves
 ITEMS_OUTPUT, ITEMS_INPUT = 0, 1   # CDAE_ITEMS_OUTPUT / CDAE_ITEMS_INPUT (include/cdae_hip.h): the item table similar_items compares rows of
 SIM_DOT, SIM_COSINE = 0, 1         # CDAE_SIM_DOT / CDAE_SIM_COSINE (include/cdae_hip.h): its score
 DEFAULT_BATCH_USERS = 0        # 0 = the library's default (cdae_hip_default_batch_users: num_users / 160, within [32, 256])
@@ -58,6 +59,10 @@ class _MfConfig(C.Structure):
                                           "pairwise", "batch_users")] + [(n, C.c_double) for n in ("lambda_", "learn_rate", "beta")]
 
 
+class _AlsConfig(C.Structure):
+    _fields_ = [(n, C.c_uint32) for n in ("struct_size", "num_dim", "cg_steps", "reserved")] + [(n, C.c_double) for n in ("lambda_", "alpha")]
+
+
 class Stats(C.Structure):
     _fields_ = [("wall_seconds", C.c_double), ("users", C.c_uint64), ("examples", C.c_uint64),
                 ("batches", C.c_uint64), ("ms_sample", C.c_double), ("ms_sort", C.c_double),
@@ -74,6 +79,10 @@ EXPORTS = {
     "cdae_hip_abi_version": (C.c_int, []),
     "cdae_hip_create": (C.c_int, [C.POINTER(_Config), C.c_int, C.POINTER(C.c_void_p)]),
     "cdae_hip_create_mf": (C.c_int, [C.POINTER(_MfConfig), C.c_int, C.POINTER(C.c_void_p)]),
+    "cdae_hip_create_als": (C.c_int, [C.POINTER(_AlsConfig), C.c_int, C.POINTER(C.c_void_p)]),
+    "cdae_hip_als_half_step": (C.c_int, [C.c_void_p, C.c_uint32]),
+    "cdae_hip_als_solve_rows": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
+    "cdae_hip_als_gram": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t]),
     "cdae_hip_destroy": (C.c_int, [C.c_void_p]),
     "cdae_hip_set_interactions": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p]),
     "cdae_hip_row_stride": (C.c_uint32, [C.c_void_p]),
@@ -724,6 +733,60 @@ class MF(CDAE):
         lens = np.diff(self._row_ptr)[self.user_order().astype(np.int64)]
         nnz = int(lens[u_begin:u_begin + n_users].sum())
         return nnz * (2 * self.cfg.num_neg if self.cfg.pairwise else 1 + self.cfg.num_neg)
+
+
+@dataclass
+class WRMFConfig:
+    """libcf::WRMFConfig (the reference's src/model/recsys/wrmf.hpp:9-16): lambda, scalar (the confidence weight alpha), num_dim; cg_steps is
+    not in the reference (conjugate-gradient iterations per row and half-step; 0 = the library's 3)."""
+    lambda_: float = 0.01
+    scalar: float = 40.0
+    num_dim: int = 10
+    cg_steps: int = 3
+
+
+class WRMF(MF):
+    """Weighted-regularised matrix factorisation fitted by alternating least squares (cdae_hip_create_als; include/cdae_hip.h has
+    the definition).  The factors are P_WU (users) and P_W (items); recommend_all, eval_topn and similar_items are MF's."""
+
+    def __init__(self, mcfg: WRMFConfig, device: int = 0):
+        self.lib = load_library()
+        self.cfg = mcfg
+        c = _AlsConfig(C.sizeof(_AlsConfig), mcfg.num_dim, mcfg.cg_steps, 0, mcfg.lambda_, mcfg.scalar)
+        self.h = C.c_void_p()
+        _chk(self.lib, self.lib.cdae_hip_create_als(C.byref(c), device, C.byref(self.h)))
+        self.num_users = self.num_items = 0
+        self._rec = None
+
+    def half_step(self, side: int):
+        """One half-step: ALS_USERS solves every user's row against the frozen item table, ALS_ITEMS the reverse."""
+        _chk(self.lib, self.lib.cdae_hip_als_half_step(self.h, side))
+
+    def train_one_iteration(self, seed: int = 0, epoch: int = 0) -> Stats:
+        """The user half-step, then the item half-step (seed and epoch are ignored: nothing is drawn)."""
+        return MF.train_one_iteration(self, seed, epoch)
+
+    def gram(self, side: int) -> np.ndarray:
+        """T^T T of the user (ALS_USERS) or item (ALS_ITEMS) table as the half-steps compute it, [num_dim, num_dim]"""
+        K = self.cfg.num_dim
+        out = np.empty((K, K), dtype=np.float32)
+        _chk(self.lib, self.lib.cdae_hip_als_gram(self.h, side, out.ctypes.data, out.size))
+        return out
+
+    def solve_rows(self, row_ptr, col, x0=None, cg_steps: int = 0) -> np.ndarray:
+        """Factors of caller-supplied rows (users outside the training set) against the frozen item table: CSR rows with ascending
+        unique items, x0 None (zeros) or [n_rows, num_dim] start vectors -> [n_rows, num_dim].  The handle is not written."""
+        rp, rc, _ = self._rows(row_ptr, col, None)
+        n, K = rp.size - 1, self.cfg.num_dim
+        a = None
+        if x0 is not None:
+            a = np.ascontiguousarray(x0, dtype=np.float32)
+            if a.shape != (n, K):
+                raise ValueError("x0 must be [n_rows, num_dim]")
+        out = np.empty((n, K), dtype=np.float32)
+        _chk(self.lib, self.lib.cdae_hip_als_solve_rows(self.h, n, rp.ctypes.data, rc.ctypes.data, None if a is None else a.ctypes.data,
+                                                        cg_steps, out.ctypes.data))
+        return out
 
 
 def comm_unique_id() -> bytes:

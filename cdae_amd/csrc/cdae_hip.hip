@@ -35,6 +35,7 @@
 #include "cdae_foldin_kernels.hpp"
 #include "cdae_sort_kernels.hpp"
 #include "cdae_mf_kernels.hpp"
+#include "cdae_als_kernels.hpp"
 
 #ifdef CDAE_DECODE_TIMING
 #define CDAE_TOUCHED_ARG ((uint32_t*)nullptr)     // the timing build borrows `touched` for its stamps
@@ -288,6 +289,12 @@ struct cdae_hip {
   DevBuf<uint32_t> d_sim_q;
   DevBuf<int64_t> d_sim_iota;
   DevBuf<float> d_sim_T, d_sim_zero;
+  // WRMF handles (cdae_hip_create_als, cdae_als_kernels.hpp): the item-major CSR built once per data set (users ascending inside a
+  // column; dropped with the interaction state), the Gram matrix [Kp x Kp] of the frozen table and its per-slice partials, and the
+  // start vectors / solutions of one chunk of cdae_hip_als_solve_rows (its CSR shares d_rows_ptr / d_rows_col).  Grow-only.
+  int64_t* d_tptr = nullptr; uint32_t* d_tcol = nullptr;
+  DevBuf<float> d_als_G, d_als_part, d_als_x, d_als_out;
+  uint32_t als_steps = 0; float als_alpha = 0.f, als_lambda = 0.f;
   // Guest table (cdae_hip_set_guest_nodes, cdae_hip_fold_in_rows with install): a second user table, rows wu | wu_ag | uu | uu_ag of
   // [n_guests x Kp] each, that the rows entry points address as CDAE_GUEST_USER(i).  d_fold: the staging rows the fold-in kernel writes
   // (a chunk's, or the whole call's when it installs); installing EXCHANGES the two sets, so a failed call leaves the table as it was.
@@ -340,7 +347,8 @@ struct cdae_hip {
   float* d_base = nullptr; float* d_delta = nullptr; float* d_recv = nullptr; float* d_snap = nullptr;   // agreed state, staged delta, all-reduced delta, parameters at the last stage
   void* xchg = nullptr; void (*xchg_free)(void*) = nullptr;   // communicator + schedule of the exchange (cdae_multi.hip)
   uint32_t delta_combine = CDAE_COMBINE_SUM;                  // cdae_hip_delta_set_combine: how staged deltas are folded in (cdae_exchange_algebra.h)
-  // IMF / BPR handles (cdae_hip_create_mf, cdae_mf_kernels.hpp): 0 = CDAE, 1 = IMF, 2 = BPR
+  // IMF / BPR handles (cdae_hip_create_mf, cdae_mf_kernels.hpp): 0 = CDAE, 1 = IMF, 2 = BPR; 3 = WRMF by ALS (cdae_hip_create_als):
+  // IMF's tables and serving, no sampled step — every training path that asks `mf == 2 ? BPR : IMF` is refused before it is reached
   uint32_t mf = 0, mf_bias = 1;
   // IMF / BPR, batch_users = 1 (the library default: the reference's strictly sequential loop): the users are still taken one after the
   // other and every instance still steps the user vector and the item row(s) in place — but LAUNCHES cover MF_SEQ_USERS users: one
@@ -543,7 +551,7 @@ template <class F> int visit_device_ptrs(cdae_hip* h, F f) {
                      h->d_Uu, h->d_Uu_ag, h->d_Ssum, h->d_delta_rows, h->d_Hsum, h->d_iota_eval,
                      h->d_gpos, h->d_ub, h->d_ub_ag, h->d_UVpre, h->d_rank_of, h->d_grow_ptr, h->d_gcol, h->d_gunit_ptr, h->d_gunit_user,
                      h->d_test_ptr, h->d_test_col, h->d_topn_pu, h->d_topn_out, h->d_bucket_cut, h->d_range_of,
-                     h->d_Ghot, h->d_hotdup, h->d_late_bits, h->d_cold_map, h->d_rows_out);
+                     h->d_Ghot, h->d_hotdup, h->d_late_bits, h->d_cold_map, h->d_rows_out, h->d_tptr, h->d_tcol);
 }
 // ... and every grow-only workspace (DevBuf), freed with its capacity.  A new one is added HERE only.  A hipFree error is returned after all have been dropped.
 int drop_dev_bufs(cdae_hip* h) {
@@ -556,7 +564,7 @@ int drop_dev_bufs(cdae_hip* h) {
        h->d_flt_eptr, h->d_flt_ecol, h->d_flt_allow, h->d_flt_pos, h->d_flt_D, h->d_flt_bp,
        h->d_sim_q, h->d_sim_iota, h->d_sim_T, h->d_sim_zero,
        h->d_guest[0], h->d_guest[1], h->d_guest[2], h->d_guest[3], h->d_fold[0], h->d_fold[1], h->d_fold[2], h->d_fold[3],
-       h->d_fold_long);
+       h->d_fold_long, h->d_als_G, h->d_als_part, h->d_als_x, h->d_als_out);
   return rc;
 }
 
@@ -1494,6 +1502,25 @@ int cdae_hip_create_mf(const cdae_mf_config* mc, int device_id, cdae_hip_t** out
   return 0;
 }
 
+int cdae_hip_create_als(const cdae_als_config* ac, int device_id, cdae_hip_t** out) {
+  if (!ac || !out) return fail("null argument");
+  if (ac->struct_size != sizeof(cdae_als_config)) return fail("cdae_als_config size mismatch: got %u, want %zu", ac->struct_size, sizeof(cdae_als_config));
+  if (!(ac->lambda >= 0.0) || !(ac->alpha >= 0.0)) return fail("lambda and alpha must be >= 0");
+  cdae_hip_config c = cdae_hip_config();
+  c.struct_size = sizeof(c);
+  c.num_dim = ac->num_dim; c.num_neg = 1; c.num_corruptions = 1;
+  c.loss_type = CDAE_LOSS_SQUARE; c.user_factor = 1;
+  c.batch_users = 1u;                                       // (no block schedule, no training order: rows are stored by user id)
+  c.lambda = ac->lambda; c.learn_rate = 0.; c.corruption_ratio = 0.; c.beta = 1.;
+  CHK(cdae_hip_create(&c, device_id, out));
+  cdae_hip* h = *out;
+  h->mf = 3u; h->mf_bias = 0u;
+  h->mf_seq = true; h->B = MF_SEQ_USERS;
+  h->als_steps = ac->cg_steps ? ac->cg_steps : CDAE_ALS_DEFAULT_CG_STEPS;
+  h->als_alpha = (float)ac->alpha; h->als_lambda = (float)ac->lambda;
+  return 0;
+}
+
 uint32_t cdae_hip_row_stride(const cdae_hip_t* h) { return h ? h->Kp : 0; }
 uint32_t cdae_hip_mf_default_batch_users(uint64_t U, uint32_t pairwise) {
   if (pairwise) return U >= CDAE_BPR_DEFAULT_MIN_USERS ? CDAE_BPR_DEFAULT_BATCH_USERS : 1u;
@@ -1587,7 +1614,7 @@ int cdae_hip_set_interactions(cdae_hip_t* h, uint64_t U, uint64_t I, const int64
   for (uint64_t u = 0; u < U; ++u) {
     const int64_t a = row_ptr[u], b = row_ptr[u + 1];
     if (b < a) return fail("row_ptr is not monotone at user %llu", (unsigned long long)u);
-    if (!h->item_shard) {      // an item shard sees only its slice of every row: empty and full slices are legal there
+    if (!h->item_shard && h->mf != 3u) {      // an item shard sees only its slice of every row: empty and full slices are legal there (and a WRMF handle samples nothing)
       if (b <= a) return fail("user %llu has no training item (the reference CHECK-fails too, cdae.hpp:139)", (unsigned long long)u);
       if ((uint64_t)(b - a) >= I) return fail("user %llu rated every item: no negative can be sampled", (unsigned long long)u);
     }
@@ -1723,6 +1750,42 @@ int cdae_hip_set_interactions(cdae_hip_t* h, uint64_t U, uint64_t I, const int64
     h->cnt[CDAE_P_UU] = h->cnt[CDAE_P_UU_AG] = WR * h->Kp;
     CHK(dev_alloc(&h->d_Uu, WR * h->Kp));
     CHK(dev_alloc(&h->d_Uu_ag, WR * h->Kp));
+  }
+
+  if (h->mf == 3u) {
+    // WRMF: no example lists, no batch workspace.  What is left: the bias arrays IMF's serving reads, the accumulators' constants, and
+    // the item-major CSR of the item half-step — a counting sort on the host, users ascending inside a column
+    CHK(dev_alloc(&h->d_ub, (size_t)U)); CHK(dev_alloc(&h->d_ub_ag, (size_t)U));
+    h->cnt[CDAE_P_UB] = h->cnt[CDAE_P_UB_AG] = (size_t)U;
+    HIPCHK(hipMemset(h->d_ub, 0, (size_t)U * sizeof(float)));
+    std::vector<int64_t> tptr(I + 1, 0);
+    for (uint64_t i = 0; i < I; ++i) tptr[i + 1] = tptr[i] + (int64_t)pop[i];
+    std::vector<uint32_t> tcol(std::max<size_t>(nnz, 1));
+    {
+      std::vector<int64_t> cursor(tptr.begin(), tptr.end() - 1);
+      for (uint64_t u = 0; u < U; ++u)
+        for (int64_t p = row_ptr[u]; p < row_ptr[u + 1]; ++p) tcol[(size_t)cursor[col[p]]++] = (uint32_t)u;
+    }
+    CHK(dev_alloc(&h->d_tptr, I + 1));
+    CHK(dev_alloc(&h->d_tcol, nnz));
+    HIPCHK(hipMemcpy(h->d_tptr, tptr.data(), (I + 1) * sizeof(int64_t), hipMemcpyHostToDevice));
+    if (nnz) HIPCHK(hipMemcpy(h->d_tcol, tcol.data(), nnz * sizeof(uint32_t), hipMemcpyHostToDevice));
+    CHK(dev_alloc(&h->d_touched, (size_t)I));                 // (nothing touches an item here; the delta entry points read the array)
+    HIPCHK(hipMemset(h->d_touched, 0, (size_t)I * sizeof(uint32_t)));
+    h->Ecap = 0; h->seq = 0; h->pre_n = 0; h->unit_cap = 0;
+    h->h_unit_ptr.assign(U + 1, 0u);
+    h->bucket_sort = false; h->counting_sort = false;
+    auto fillm = [&](float* M, size_t rows, uint32_t K, uint32_t Kp, float v, float pad) {
+      hipLaunchKernelGGL(cdae::fill_matrix_kernel, dim3((uint32_t)((rows * Kp + 255) / 256)), dim3(256), 0, h->stream, M, rows, K, Kp, v, pad);
+    };
+    fillm(h->P(CDAE_P_W_AG), I, h->K, h->Kp, 1e-4f, 1.f);
+    fillm(h->d_Wu_ag, WR, h->K, h->Kp, 1e-4f, 1.f);
+    fillm(h->P(CDAE_P_B_AG), 1, h->K, h->Kp, 1e-4f, 1.f);
+    fillm(h->P(CDAE_P_BP_AG), I, 1, 1, 1e-4f, 1.f);
+    fillm(h->d_ub_ag, U, 1, 1, 1e-4f, 1.f);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return 0;
   }
 
   // batch workspace sized for the largest batch of B consecutive users
@@ -2002,10 +2065,11 @@ int cdae_hip_init_params(cdae_hip_t* h, uint64_t seed) {
   auto fill = [&](float* M, size_t rows, uint32_t K, uint32_t Kp, float v) {     // accumulator pads are 1, others 0
     hipLaunchKernelGGL(fill_matrix_kernel, blocks(rows * Kp), dim3(256), 0, h->stream, M, rows, K, Kp, v, v == 0.f ? 0.f : 1.f);
   };
-  if (h->mf) {                                             // imf.hpp:57-69: Random() * 0.01, accumulators 1e-4, biases 0
+  if (h->mf) {                                             // imf.hpp:57-69: Random() * 0.01, accumulators 1e-4, biases 0; wrmf.hpp:47-48: Random() * 0.001
+    const double mf_scale = h->mf == 3u ? 0.001 : 0.01;
     auto init01 = [&](float* M, size_t rows, uint32_t id, uint64_t row0) {
       hipLaunchKernelGGL(init_matrix_kernel, blocks(rows * h->Kp), dim3(256), 0, h->stream, M, rows, h->K, h->Kp,
-                         cdae_rng_key(seed, 0, id, CDAE_STREAM_INIT), 0.01, row0);
+                         cdae_rng_key(seed, 0, id, CDAE_STREAM_INIT), mf_scale, row0);
     };
     init01(h->d_Wu, h->U, CDAE_P_WU, h->uid_offset); fill(h->d_Wu_ag, h->U, h->K, h->Kp, 1e-4f);
     init01(h->P(CDAE_P_W), h->I, CDAE_P_W, 0); fill(h->P(CDAE_P_W_AG), h->I, h->K, h->Kp, 1e-4f);
@@ -2116,6 +2180,10 @@ int cdae_hip_synchronize(cdae_hip_t* h) {
 }  // extern "C"
 
 namespace {
+
+constexpr const char* ALS_EVERY_ROW = "a WRMF handle trains by whole half-steps, and a half-step needs every row "
+                                      "(cdae_hip_train_epoch, cdae_hip_als_half_step)";
+int als_half_step(cdae_hip* h, uint32_t side);              // (below, beside cdae_hip_als_solve_rows)
 
 int make_plan(cdae_hip* h, uint64_t u_begin, uint64_t u_end, std::vector<Batch>& plan) {
   if (u_begin > u_end || u_end > h->U) return fail("bad user range [%llu, %llu)", (unsigned long long)u_begin, (unsigned long long)u_end);
@@ -2252,6 +2320,7 @@ int drop_prefetched(cdae_hip* h, size_t keep) {
 // event, see below) one pass over users [u_begin, u_end): a software pipeline in which the
 // sampling + sorting of batch t+1 (prep stream) overlaps the training of batch t (main stream).
 int enqueue_users(cdae_hip* h, uint64_t seed, uint32_t epoch, uint64_t u_begin, uint64_t u_end) {
+  if (h->mf == 3u) return fail("%s", ALS_EVERY_ROW);
   if (h->item_shard) return fail("an item shard trains in phases under cdae_hip_multi_train_epoch, not on its own");
   std::vector<Batch> plan;
   CHK(make_plan(h, u_begin, u_end, plan));
@@ -2511,6 +2580,16 @@ int cdae_hip_train_users(cdae_hip_t* h, uint64_t seed, uint32_t epoch, uint64_t 
   if (!h || !h->d_shared) return fail("set_interactions must be called first");
   HIPCHK(hipSetDevice(h->device));
   const auto t0 = std::chrono::steady_clock::now();
+  if (h->mf == 3u) {                                        // WRMF: the user half-step, then the item half-step (wrmf.hpp:102-109)
+    if (u_begin != 0 || u_end != h->U) return fail("%s", ALS_EVERY_ROW);
+    CHK(als_half_step(h, CDAE_ALS_USERS));
+    CHK(als_half_step(h, CDAE_ALS_ITEMS));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    h->acc_users = h->U; h->acc_examples = 0; h->acc_batches = 2;
+    CHK(fill_stats(h, stats));
+    if (stats) stats->wall_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    return 0;
+  }
   CHK(enqueue_users(h, seed, epoch, u_begin, u_end));
   CHK(join_aux(h));
   HIPCHK(hipStreamSynchronize(h->stream));
@@ -2538,6 +2617,7 @@ int cdae_hip_enqueue_users(cdae_hip_t* h, uint64_t seed, uint32_t epoch, uint64_
 
 int cdae_hip_prefetch_users(cdae_hip_t* h, uint64_t seed, uint32_t epoch, uint64_t u_begin, uint64_t u_end) {
   if (!h || !h->d_shared) return fail("set_interactions must be called first");
+  if (h->mf == 3u) return fail("%s", ALS_EVERY_ROW);
   HIPCHK(hipSetDevice(h->device));
   std::vector<Batch> plan;
   CHK(make_plan(h, u_begin, u_end, plan));
@@ -2568,6 +2648,7 @@ int cdae_hip_debug_row_pack(cdae_hip_t* h, uint64_t seed, uint32_t epoch, uint64
                             uint32_t* out_records, uint64_t* n_records) {
   if (!n_records) return fail("null argument");
   if (!h || !h->d_shared) return fail("set_interactions must be called first");
+  if (h->mf == 3u) return fail("%s", ALS_EVERY_ROW);
   const uint32_t hot = decode_hot_rows(h);
   const uint64_t want = packs_rows(h) ? (((uint64_t)h->I - hot + 3) & ~3ull) : 0;
   if (want > *n_records) return fail("the pack has %llu records, the caller's array holds %llu", (unsigned long long)want, (unsigned long long)*n_records);
@@ -2585,6 +2666,7 @@ int cdae_hip_debug_sample_batch(cdae_hip_t* h, uint64_t seed, uint32_t epoch, ui
                                 uint64_t* sorted_val, uint32_t* seg_begin, uint32_t* seg_end, uint32_t* dup_of_pos,
                                 uint32_t* dup_of_ex, uint64_t* n_examples) {
   if (!h || !h->d_shared) return fail("set_interactions must be called first");
+  if (h->mf == 3u) return fail("%s", ALS_EVERY_ROW);
   if (!n_examples) return fail("null argument");
   if (n_users == 0 || u_begin + n_users > h->U) return fail("bad user range [%llu, +%u)", (unsigned long long)u_begin, n_users);
   if (n_users > std::min<uint64_t>(h->B, h->U)) return fail("%u users exceed batch_users %u", n_users, h->B);
@@ -3487,6 +3569,109 @@ int cdae_hip_similar_items(cdae_hip_t* h, uint64_t n_queries, const uint32_t* qu
   const float* T = table == CDAE_ITEMS_INPUT ? h->P(CDAE_P_W) : h->dec();
   const SimilarArgs a{n_queries, query_items, T, metric == CDAE_SIM_COSINE, exclude_self != 0, topk, out_ids, out_scores};
   return similar_run(h, a, FilterArgs{excl_row_ptr, excl_col, false, allow_items, n_allow});
+}
+
+}  // extern "C"
+
+// ---- WRMF by alternating least squares (cdae_als_kernels.hpp) ------------------------------------------------------
+namespace {
+// G = T^T T of `rows` rows into h->d_als_G: per-slice partials, then the fold in slice order
+int als_gram(cdae_hip* h, const float* T, uint64_t rows) {
+  const uint32_t Kp = h->Kp, slices = cdae::als_gram_slices(rows), tiles = Kp / 32u;
+  CHK(h->d_als_G.ensure((size_t)Kp * Kp));
+  CHK(h->d_als_part.ensure((size_t)cdae::ALS_GRAM_SLICES_MAX * Kp * Kp));
+  hipLaunchKernelGGL(cdae::als_gram_kernel, dim3(tiles * tiles, slices), dim3(64), 0, h->stream, T, rows, Kp, (float*)h->d_als_part);
+  hipLaunchKernelGGL(cdae::als_gram_fold_kernel, dim3((Kp * Kp + 255u) / 256u), dim3(256), 0, h->stream, (const float*)h->d_als_part, slices,
+                     Kp * Kp, (float*)h->d_als_G);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+// n rows of the CSR (ptr, col) solved against the table Y and h->d_als_G, 32 rows per workgroup
+template <int NI>
+int als_solve_as(cdae_hip* h, const int64_t* ptr, const uint32_t* col, uint64_t n, const float* Y, const float* x0, float* dst, uint32_t steps) {
+  constexpr size_t lds = cdae::als_solve_lds_bytes<NI>();
+  HIPCHK(hipFuncSetAttribute((const void*)cdae::als_solve_kernel<NI>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  hipLaunchKernelGGL((cdae::als_solve_kernel<NI>), dim3((uint32_t)((n + cdae::ALS_BLOCK_ROWS - 1) / cdae::ALS_BLOCK_ROWS)), dim3(cdae::als_waves<NI>() * 64), lds,
+                     h->stream, ptr, col, n, Y, (const float*)h->d_als_G, x0, dst, h->als_alpha, h->als_lambda, steps);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+int als_solve(cdae_hip* h, const int64_t* ptr, const uint32_t* col, uint64_t n, const float* Y, const float* x0, float* dst, uint32_t steps) {
+  switch (h->NI) {
+    case 1: return als_solve_as<1>(h, ptr, col, n, Y, x0, dst, steps);
+    case 2: return als_solve_as<2>(h, ptr, col, n, Y, x0, dst, steps);
+    case 4: return als_solve_as<4>(h, ptr, col, n, Y, x0, dst, steps);
+    default: return als_solve_as<8>(h, ptr, col, n, Y, x0, dst, steps);
+  }
+}
+int als_check(cdae_hip* h, const char* fn) {
+  if (!h) return fail("%s: null handle", fn);
+  if (h->mf != 3u) return fail("%s applies to a WRMF handle (cdae_hip_create_als)", fn);
+  if (!h->d_shared) return fail("%s: cdae_hip_set_interactions first", fn);
+  return 0;
+}
+// one half-step, enqueued on h->stream: the side's rows in place against the other side's table
+int als_half_step(cdae_hip* h, uint32_t side) {
+  float* X = h->d_Wu; float* Y = h->P(CDAE_P_W);
+  if (side == CDAE_ALS_USERS) {
+    CHK(als_gram(h, Y, h->I));
+    return als_solve(h, h->d_row_ptr, h->d_col, h->U, Y, X, X, h->als_steps);
+  }
+  CHK(als_gram(h, X, h->U));
+  return als_solve(h, h->d_tptr, h->d_tcol, h->I, X, Y, Y, h->als_steps);
+}
+constexpr uint64_t ALS_ROWS_CHUNK = 32768;
+}  // namespace
+
+extern "C" {
+
+int cdae_hip_als_half_step(cdae_hip_t* h, uint32_t side) {
+  CHK(als_check(h, "cdae_hip_als_half_step"));
+  if (side != CDAE_ALS_USERS && side != CDAE_ALS_ITEMS) return fail("cdae_hip_als_half_step: side must be CDAE_ALS_USERS or CDAE_ALS_ITEMS");
+  HIPCHK(hipSetDevice(h->device));
+  CHK(als_half_step(h, side));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  return 0;
+}
+
+int cdae_hip_als_gram(cdae_hip_t* h, uint32_t side, float* out, size_t count) {
+  CHK(als_check(h, "cdae_hip_als_gram"));
+  if (side != CDAE_ALS_USERS && side != CDAE_ALS_ITEMS) return fail("cdae_hip_als_gram: side must be CDAE_ALS_USERS or CDAE_ALS_ITEMS");
+  if (!out || count != (size_t)h->K * h->K) return fail("cdae_hip_als_gram: out must hold num_dim x num_dim = %zu floats, got %zu", (size_t)h->K * h->K, count);
+  HIPCHK(hipSetDevice(h->device));
+  CHK(side == CDAE_ALS_USERS ? als_gram(h, h->d_Wu, h->U) : als_gram(h, h->P(CDAE_P_W), h->I));
+  HIPCHK(hipMemcpy2DAsync(out, h->K * sizeof(float), h->d_als_G, h->Kp * sizeof(float), h->K * sizeof(float), h->K, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  return 0;
+}
+
+int cdae_hip_als_solve_rows(cdae_hip_t* h, uint64_t n_rows, const int64_t* row_ptr, const uint32_t* col, const float* x0,
+                            uint32_t cg_steps, float* out_x) {
+  const char* fn = "cdae_hip_als_solve_rows";
+  CHK(als_check(h, fn));
+  if (n_rows == 0) return 0;
+  CHK(validate_rows_csr("rated", row_ptr, col, n_rows, h->I));
+  if (!out_x) return fail("%s: null out_x", fn);
+  HIPCHK(hipSetDevice(h->device));
+  const uint32_t steps = cg_steps ? cg_steps : h->als_steps;
+  const size_t chunk = (size_t)std::min<uint64_t>(n_rows, ALS_ROWS_CHUNK);
+  CHK(upload_csr(h, h->d_rows_ptr, h->d_rows_col, row_ptr, col, n_rows));
+  CHK(h->d_als_out.ensure(chunk * h->Kp));
+  if (x0) CHK(h->d_als_x.ensure(chunk * h->Kp));
+  const float* Y = h->P(CDAE_P_W);
+  CHK(als_gram(h, Y, h->I));
+  const size_t wK = h->K * sizeof(float), wKp = h->Kp * sizeof(float);
+  for (uint64_t c0 = 0; c0 < n_rows; c0 += ALS_ROWS_CHUNK) {
+    const uint64_t nu = std::min<uint64_t>(ALS_ROWS_CHUNK, n_rows - c0);
+    if (x0) {                                               // (pad lanes zero: the kernel relies on it)
+      HIPCHK(hipMemsetAsync(h->d_als_x, 0, nu * wKp, h->stream));
+      HIPCHK(hipMemcpy2DAsync(h->d_als_x, wKp, x0 + c0 * h->K, wK, wK, nu, hipMemcpyHostToDevice, h->stream));
+    }
+    CHK(als_solve(h, h->d_rows_ptr.p + c0, h->d_rows_col.p, nu, Y, x0 ? (const float*)h->d_als_x.p : nullptr, h->d_als_out.p, steps));
+    HIPCHK(hipMemcpy2DAsync(out_x + c0 * h->K, wK, h->d_als_out, wKp, wK, nu, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));                // the two chunk buffers are the next chunk's too
+  }
+  return 0;
 }
 
 int cdae_hip_eval_topn_rows(cdae_hip_t* h, uint64_t n_rows, const uint32_t* uids, const int64_t* row_ptr, const uint32_t* col,

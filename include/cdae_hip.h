@@ -87,7 +87,10 @@ extern "C" {
  *     also under 12, the version unchanged (a new entry point; nothing existing changed): cdae_hip_recommend_rows_filtered — batched top-k
  *     with an item allow list for the call and per-row exclusions that are not inputs (or inputs that are not exclusions)
  *     also under 12, the version unchanged (a new entry point; nothing existing changed): cdae_hip_similar_items, CDAE_ITEMS_OUTPUT /
- *     CDAE_ITEMS_INPUT, CDAE_SIM_DOT / CDAE_SIM_COSINE — batched top-k item neighbours of named items by dot product or cosine */
+ *     CDAE_ITEMS_INPUT, CDAE_SIM_DOT / CDAE_SIM_COSINE — batched top-k item neighbours of named items by dot product or cosine
+ *     also under 12, the version unchanged (new entry points; nothing existing changed): cdae_als_config, cdae_hip_create_als,
+ *     cdae_hip_als_half_step, cdae_hip_als_solve_rows, cdae_hip_als_gram, CDAE_ALS_USERS / CDAE_ALS_ITEMS — WRMF fitted by alternating
+ *     least squares, conjugate gradients per row on the matrix cores */
 #define CDAE_HIP_ABI_VERSION 12
 
 /* numeric values follow libcf::LossType (/root/reference/src/model/loss.hpp:10-18) */
@@ -683,6 +686,59 @@ typedef struct cdae_mf_config {
 #define CDAE_BPR_DEFAULT_MIN_USERS 65536u
 uint32_t cdae_hip_mf_default_batch_users(uint64_t num_users, uint32_t pairwise);
 int cdae_hip_create_mf(const cdae_mf_config* cfg, int device_id, cdae_hip_t** out);
+
+/* ---- WRMF: weighted-regularised matrix factorisation fitted by alternating least squares (Hu, Koren, Volinsky, "Collaborative
+ * filtering for implicit feedback datasets"; the reference's src/model/recsys/wrmf.hpp, als.hpp), on the same handle type ----
+ * Binary interactions R (the train CSR): preference 1 and confidence 1 + alpha on a stored pair, preference 0 and confidence 1
+ * elsewhere.  The user half-step, with the item table Y frozen and R_u the items of row u, solves for every user with interactions
+ *     G   = Y^T Y                                          (K x K, once per half-step)
+ *     A_u = G + alpha * sum_{i in R_u} y_i y_i^T + lambda * I
+ *     b_u = (1 + alpha) * sum_{i in R_u} y_i
+ *     x_u <- CG(A_u, b_u, start = the current x_u, cg_steps iterations)
+ * and the item half-step is the same over the transposed CSR with G = X^T X of the user table the user half-step has just written.
+ * An epoch is the user half-step followed by the item half-step (wrmf.hpp:102-109); a row without interactions is left as it is
+ * (wrmf.hpp:111-116).  CG is the textbook loop, A_u is never formed (A_u p = G p + alpha sum_i y_i (y_i . p) + lambda p):
+ *     r = b - A x; p = r; rs = r.r; then cg_steps times: Ap; a = rs / (p.Ap); x += a p; r -= a Ap; rs' = r.r; p = r + (rs'/rs) p
+ * and a row whose rs falls below 1e-20 stops with the x it has.  One half-step is exactly parallel: no learning rate, no sampling,
+ * no order between rows; a row's result does not depend on the rows solved beside it, and the same state gives the same bits.
+ *
+ * There is deliberately NO switch for the reference's literal train_one_index (wrmf.hpp:66-100).  It omits the Y^T Y term, so every
+ * unobserved pair is unweighted, and its system lambda * I + scalar * sum y y^T is so ill-conditioned that a truncated fp32 CG on it
+ * differs from fp64 by up to 1e-1 on this repository's test fixtures (measured with numpy): nothing a GPU kernel could be held to.
+ *
+ * alpha is WRMFConfig::scalar; lambda and num_dim are the reference's; cdae_hip_init_params draws Random() * 0.001
+ * (wrmf.hpp:47-48) from the CDAE_STREAM_INIT stream with the keys of the IMF tables.  The factors live where IMF's do — CDAE_P_WU
+ * users x K, CDAE_P_W items x K, biases zero — so cdae_hip_recommend_all, cdae_hip_eval_topn and cdae_hip_similar_items serve the
+ * handle as they serve IMF; the accumulator ids (_AG), CDAE_P_UB and CDAE_P_BP hold the constants init_params writes and nothing
+ * reads them.  Unlike the SGD handles, rows without interactions and rows with every item are legal in set_interactions.
+ *   cdae_hip_train_epoch    both half-steps; seed and epoch are ignored (nothing is drawn); stats.users = num_users, stats.batches = 2
+ *   cdae_hip_train_users    the full range only
+ * A partial range, cdae_hip_enqueue_users, cdae_hip_prefetch_users, cdae_hip_debug_sample_batch and cdae_hip_debug_row_pack are
+ * refused (a half-step needs every row); everything that refuses an IMF / BPR handle refuses this one with the same text;
+ * data_loss / penalty_loss are 0. */
+typedef struct cdae_als_config {
+  uint32_t struct_size;      /* sizeof(cdae_als_config)                                  */
+  uint32_t num_dim;          /* WRMFConfig::num_dim                                      */
+  uint32_t cg_steps;         /* CG iterations per row and half-step; 0 -> 3              */
+  uint32_t reserved;         /* 0                                                        */
+  double lambda;             /* WRMFConfig::lambda                                       */
+  double alpha;              /* WRMFConfig::scalar: confidence 1 + alpha on a stored pair */
+} cdae_als_config;
+#define CDAE_ALS_DEFAULT_CG_STEPS 3u
+#define CDAE_ALS_USERS 0u
+#define CDAE_ALS_ITEMS 1u
+int cdae_hip_create_als(const cdae_als_config* cfg, int device_id, cdae_hip_t** out);
+int cdae_hip_als_half_step(cdae_hip_t* h, uint32_t side);
+/* The user-side solve for rows the caller supplies (users outside the training set, against the frozen item table): a host CSR over
+ * n_rows rows, validated exactly as cdae_hip_recommend_rows validates its rated sets; x0 NULL (zeros) or [n_rows x num_dim];
+ * out_x [n_rows x num_dim]; cg_steps 0 = the handle's.  A row without items returns its start vector.  The handle's parameters are
+ * not written.  Chunks of at most 32 768 rows; n_rows == 0 succeeds and touches nothing; every validation error is raised before
+ * a launch.  The train rows with x0 = the current user factors return the bits cdae_hip_als_half_step(CDAE_ALS_USERS) would write. */
+int cdae_hip_als_solve_rows(cdae_hip_t* h, uint64_t n_rows, const int64_t* row_ptr, const uint32_t* col, const float* x0,
+                            uint32_t cg_steps, float* out_x);
+/* G = T^T T of the current user (CDAE_ALS_USERS) or item (CDAE_ALS_ITEMS) table as the half-steps compute it, [num_dim x num_dim]
+ * row-major: a test hook (the same table gives the same bits on every call). */
+int cdae_hip_als_gram(cdae_hip_t* h, uint32_t side, float* out, size_t count);
 
 /* ---- library-owned RCCL communicator and exchange schedule (one process per GPU: bench.py --gpus N) -----------------
  * The all-reduce of the staged deltas runs inside the library, on its own communicator and HIP stream, overlapped with the
