@@ -21,8 +21,8 @@ FIXTURES = {"F23": ar.F23(), "F300": ar.F300()}
 MEASURED = os.environ.get("CDAE_ALS_MEASURED")          # a file the parity cases append their figures to (tools/als_bench.py reads it)
 
 
-def make(R, K, steps=3, X=None, Y=None, seed=3):
-    m = cdae_amd.WRMF(cdae_amd.WRMFConfig(lambda_=ar.LAMBDA, scalar=ar.ALPHA, num_dim=K, cg_steps=steps))
+def make(R, K, steps=3, X=None, Y=None, seed=3, alpha=ar.ALPHA, lam=ar.LAMBDA):
+    m = cdae_amd.WRMF(cdae_amd.WRMFConfig(lambda_=lam, scalar=alpha, num_dim=K, cg_steps=steps))
     ptr, col = ar.csr(R)
     m.set_interactions(R.shape[0], R.shape[1], ptr, col)
     m.init_params(seed)
