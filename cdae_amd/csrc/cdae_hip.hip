@@ -99,6 +99,12 @@ template <class T> int dev_alloc(T** p, size_t n) {
   HIPCHK(hipMalloc((void**)p, std::max<size_t>(n, 1) * sizeof(T)));
   return 0;
 }
+// dev_alloc, then n elements copied from the host
+template <class T> int dev_upload(T** d, const T* src, size_t n) {
+  CHK(dev_alloc(d, n));
+  HIPCHK(hipMemcpy(*d, src, n * sizeof(T), hipMemcpyHostToDevice));
+  return 0;
+}
 // Grow-only device workspace that owns its capacity: p holds at least cap units of `per` elements (the `per` of the ensure() calls
 // that grew it).  drop() is the only way either member is cleared, so a freed buffer can never keep a capacity that ensure() would
 // believe.  Every DevBuf of a handle is listed once, in drop_dev_bufs().
@@ -1564,6 +1570,14 @@ int cdae_hip_set_user_id_offset(cdae_hip_t* h, uint64_t offset) {
   return 0;
 }
 
+namespace {
+void adopt_plan(cdae_hip* h, const cdae::plan::Args& a, cdae::plan::Plan& p, uint32_t cfg_batch_users);
+int upload_data_set(cdae_hip* h, const cdae::plan::Plan& p, const int64_t* grp, const uint32_t* gcl);
+}  // namespace
+
+// Three steps.  1: the arguments are checked and the data-set plan is built (cdae_dataset_plan.h: host arithmetic alone) — every refusal
+// that the arguments and the handle's configuration decide falls here, and leaves the handle with the data set and parameters it had.
+// 2: the handle is quiesced, its old data set freed, the plan's numbers copied onto it.  3: allocations, uploads, fills, one synchronise.
 int cdae_hip_set_interactions(cdae_hip_t* h, uint64_t U, uint64_t I, const int64_t* row_ptr, const uint32_t* col) {
   if (!h || !row_ptr || (!col && U && row_ptr[U])) return fail("null argument");
   if (h->shard_sampled() && (!h->g_row_ptr_src || !h->g_col_src)) return fail("an item shard of the sampled decode needs the whole rows (set_item_shard_global)");
@@ -1571,173 +1585,112 @@ int cdae_hip_set_interactions(cdae_hip_t* h, uint64_t U, uint64_t I, const int64
   if (U == 0 || I == 0) return fail("empty interaction matrix (%llu users, %llu items)", (unsigned long long)U, (unsigned long long)I);
   if (I >= (1ull << 30) || U >= (1ull << 30)) return fail("at most 2^30 users and items");
   if (row_ptr[0] != 0) return fail("row_ptr[0] must be 0");
+  cdae::plan::Args a;
+  a.U = U; a.I = I; a.row_ptr = row_ptr; a.col = col;
+  a.kind = h->mf; a.full_output = h->cfg.full_output; a.asymmetric = h->cfg.asymmetric; a.item_shard = h->item_shard;
+  a.K = h->K; a.Kp = h->Kp; a.num_neg = h->hp.num_neg;
+  a.I_global = h->I_global; a.own_u0 = h->own_u0; a.own_u1 = h->own_u1;
+  uint32_t cfg_batch_users = h->cfg.batch_users;
+  a.mf_seq = h->mf_seq; a.batch_users = h->B;
+  if (h->mf && h->mf_auto) {
+    cfg_batch_users = cdae_hip_mf_default_batch_users(U, h->mf == 2u ? 1u : 0u);
+    a.mf_seq = cfg_batch_users == 1u;
+    a.batch_users = a.mf_seq ? MF_SEQ_USERS : cfg_batch_users;
+  }
+  // default: ~U/160 users per parameter snapshot, in [32, 256].  256 is the largest size whose Recall@10 shows no systematic
+  // offset against the strictly sequential reference schedule (paired multi-seed study at ML-10M shape, DESIGN.md §2: 384 and
+  // 512 sit 0.001-0.002 low); tests/test_gpu_accuracy.py certifies exactly this value at the BASELINE shapes.
+  if (cfg_batch_users == 0) a.batch_users = cdae_hip_default_batch_users(U);
+  if (const char* ev = DEV_ENV("CDAE_DECODE_HOT_POS")) a.hot_pos = std::atof(ev);
+  if (const char* ev = DEV_ENV("CDAE_DECODE_LATE_POS")) a.late_pos = std::atof(ev);
+  a.no_late_rows = DEV_ENV("CDAE_NO_LATE_ROWS") != nullptr;      // round 5's arithmetic (developer switch)
+  // opt-in (CDAE_SORT_COUNTING=1): measured slower than rocPRIM's onesweep beside the training kernels (DESIGN.md §5, profiles/r02_*)
+  // opt-in (CDAE_SORT_TILE=1).  Measured (profiles/r02_tile_sort.txt): the four launches take 72 us against rocPRIM's ten launches / ~100 us
+  // per batch on the prep stream, yet the training step is the same within 1 % at 256 users and 3 % slower at 512 — the prep
+  // stream runs beside the training kernels, and what counts there is how much it disturbs them, not its own length
+  // (round 4: the tile kernels skip VOID examples, so a sampled item shard can take them too — there the prep chain is NOT hidden
+  // behind a look-ahead lane and the library sort's launches and fills are the larger part of it)
+  a.sort_tile = DEV_ENV("CDAE_SORT_TILE") != nullptr;
+  // the bucket sort is the DEFAULT since round 5.  CDAE_SORT_LIBRARY (developer build): the library sort + segment_kernel everywhere
+  // (the A/B side of the bit-equality tests); CDAE_SORT_SCAN: the bucket sort without its cells
+  a.sort_library = DEV_ENV("CDAE_SORT_LIBRARY") != nullptr;
+  a.sort_scan = DEV_ENV("CDAE_SORT_SCAN") != nullptr;
+  // the whole rows of a sampled item shard were lent for ONE call (set_item_shard_global): the call that hands them to the plan consumes them
+  const int64_t* const grp = h->g_row_ptr_src;
+  const uint32_t* const gcl = h->g_col_src;
+  if (h->shard_sampled()) { a.whole_row_ptr = grp; h->g_row_ptr_src = nullptr; h->g_col_src = nullptr; }
+  cdae::plan::Plan p;
+  const std::string refusal = cdae::plan::build(a, p);
+  if (!refusal.empty()) return fail("%s", refusal.c_str());
+
   HIPCHK(hipSetDevice(h->device));
   CHK(join_aux(h));
-  std::vector<int64_t> perm_ptr;
-  std::vector<uint32_t> perm_col;
-  h->user_perm.clear(); h->user_inv.clear();
-  if (h->mf && h->mf_auto) {
-    const uint32_t b = cdae_hip_mf_default_batch_users(U, h->mf == 2u ? 1u : 0u);
-    h->cfg.batch_users = b;
-    h->mf_seq = b == 1u;
-    h->B = h->mf_seq ? MF_SEQ_USERS : b;
-  }
-  if (h->mf && !h->mf_seq && h->B > 1 && U > h->B) {
-    for (uint64_t u = 0; u < U; ++u)
-      if (row_ptr[u + 1] < row_ptr[u]) return fail("row_ptr is not monotone at user %llu", (unsigned long long)u);
-    // activity-grouped training order (see cdae_hip::user_perm)
-    std::vector<uint32_t> by_len(U);
-    std::iota(by_len.begin(), by_len.end(), 0u);
-    std::stable_sort(by_len.begin(), by_len.end(), [&](uint32_t a, uint32_t b) { return row_ptr[a + 1] - row_ptr[a] > row_ptr[b + 1] - row_ptr[b]; });
-    const uint64_t nblk = (U + h->B - 1) / h->B;
-    std::vector<uint32_t> blk(nblk);
-    std::iota(blk.begin(), blk.end(), 0u);
-    // the short last group (U % B users, the least active) stays LAST: make_plan cuts batches at multiples of B from position 0, so
-    // a short group in the middle made every later batch straddle two unrelated activity groups and last as long as the heavier one
-    const uint64_t shuffled = (U % h->B) ? nblk - 1 : nblk;
-    std::stable_sort(blk.begin(), blk.begin() + shuffled, [](uint32_t a, uint32_t b) { return (uint32_t)(a * 2654435761u) < (uint32_t)(b * 2654435761u); });
-    h->user_perm.reserve(U);
-    for (uint32_t k : blk)
-      for (uint64_t t = (uint64_t)k * h->B; t < std::min<uint64_t>(U, (uint64_t)(k + 1) * h->B); ++t) h->user_perm.push_back(by_len[t]);
-    h->user_inv.resize(U);
-    for (uint64_t pos = 0; pos < U; ++pos) h->user_inv[h->user_perm[pos]] = (uint32_t)pos;
-    perm_ptr.assign(U + 1, 0);
-    perm_col.resize((size_t)row_ptr[U]);
-    for (uint64_t pos = 0; pos < U; ++pos) {
-      const uint32_t u = h->user_perm[pos];
-      std::copy(col + row_ptr[u], col + row_ptr[u + 1], perm_col.begin() + perm_ptr[pos]);
-      perm_ptr[pos + 1] = perm_ptr[pos] + (row_ptr[u + 1] - row_ptr[u]);
-    }
-    row_ptr = perm_ptr.data(); col = perm_col.data();       // from here on: rows by POSITION
-  }
-  std::vector<uint64_t> pop(I, 0);
-  for (uint64_t u = 0; u < U; ++u) {
-    const int64_t a = row_ptr[u], b = row_ptr[u + 1];
-    if (b < a) return fail("row_ptr is not monotone at user %llu", (unsigned long long)u);
-    if (!h->item_shard && h->mf != 3u) {      // an item shard sees only its slice of every row: empty and full slices are legal there (and a WRMF handle samples nothing)
-      if (b <= a) return fail("user %llu has no training item (the reference CHECK-fails too, cdae.hpp:139)", (unsigned long long)u);
-      if ((uint64_t)(b - a) >= I) return fail("user %llu rated every item: no negative can be sampled", (unsigned long long)u);
-    }
-    for (int64_t p = a; p < b; ++p) {
-      if (col[p] >= I) return fail("item id %u out of range at position %lld", col[p], (long long)p);
-      if (p > a && col[p] <= col[p - 1]) return fail("row %llu is not strictly ascending at position %lld", (unsigned long long)u, (long long)p);
-      pop[col[p]]++;
-    }
-  }
   // nothing may still be reading the old data set: a prefetched batch in the prep worker's queue or in the prep streams included
   CHK(quiesce(h));
   CHK(free_interaction_state(h));
-  if (h->cfg.batch_users == 0) {
-    // default: ~U/160 users per parameter snapshot, in [32, 256].  256 is the largest size whose Recall@10 shows no systematic
-    // offset against the strictly sequential reference schedule (paired multi-seed study at ML-10M shape, DESIGN.md §2: 384 and
-    // 512 sit 0.001-0.002 low); tests/test_gpu_accuracy.py certifies exactly this value at the BASELINE shapes.
-    h->B = cdae_hip_default_batch_users(U);
-  }
+  adopt_plan(h, a, p, cfg_batch_users);
+  return upload_data_set(h, p, grp, gcl);
+}
+
+namespace {
+
+// step 2: the plan's numbers onto the handle (the old data set is gone, nothing of the new one is on the device yet)
+void adopt_plan(cdae_hip* h, const cdae::plan::Args& a, cdae::plan::Plan& p, uint32_t cfg_batch_users) {
+  const uint64_t U = a.U, I = a.I;
+  h->cfg.batch_users = cfg_batch_users; h->mf_seq = a.mf_seq; h->B = a.batch_users;
   h->U = U; h->I = I; h->hp.num_items = (uint32_t)I;
-  if (h->item_shard) {
-    if (h->own_u1 == ~0ull) { h->own_u0 = 0; h->own_u1 = U; }
-    if (h->own_u0 > h->own_u1 || h->own_u1 > U) return fail("owned user range [%llu, %llu) outside the %llu users", (unsigned long long)h->own_u0, (unsigned long long)h->own_u1, (unsigned long long)U);
-    h->hp.own_u0 = h->own_u0; h->hp.own_u1 = h->own_u1;
-  }
-  {
-    // Work-unit size of the user-parallel kernels (sample, encode, hidden gather, data_loss: one wavefront per unit).  Those
-    // launches are latency-bound per wavefront — a unit's rows are gathered a few at a time — so a batch should offer the chip
-    // (256 CUs x 4 SIMDs) several thousand wavefronts: small batches take small units.
-    const uint64_t Bu = std::min<uint64_t>(h->B, U);
-    h->hp.unit_pos = Bu <= 1024 ? 64u : cdae::UNIT_POS_MAX;       // measured at ML-10M shape, batch_users 256 / 512: 64 best (profiles/r02_unit_size.txt)
-  }
-  h->h_row_ptr.assign(row_ptr, row_ptr + U + 1);
-  const size_t nnz = (size_t)row_ptr[U];
+  if (h->item_shard) { h->own_u0 = h->hp.own_u0 = p.own_u0; h->own_u1 = h->hp.own_u1 = p.own_u1; }
+  h->hp.unit_pos = p.unit_pos;
+  h->user_perm = std::move(p.act.user_perm); h->user_inv = std::move(p.act.user_inv);
+  h->h_row_ptr.assign(p.row_ptr, p.row_ptr + U + 1);
+  h->hot_rows = p.split.hot_rows; h->late_rows = p.split.late_rows; h->late_words = (uint32_t)((I + 31) / 32);
+  h->h_rank_len = std::move(p.split.rank_len);
+  h->fused_geo_set = false;
+  std::memcpy(h->off, p.params.off, sizeof h->off); std::memcpy(h->cnt, p.params.cnt, sizeof h->cnt);
+  h->n_matrix = p.params.n_matrix; h->n_shared = p.params.n_shared;
+  h->ex_per_pos = p.ex_per_pos; h->Ecap = p.Ecap;
+  if (h->shard_sampled()) h->h_grow_ptr.assign(a.whole_row_ptr, a.whole_row_ptr + U + 1); else h->h_grow_ptr.clear();
+  h->h_gunit_ptr = std::move(p.gunit_ptr);
+  h->seq = 0; h->pre_n = 0;
+  h->counting_sort = p.counting_sort;
+  h->bucket_sort = p.bucket.on; h->bucket_ranges = p.bucket.on ? (uint32_t)p.bucket.cut.size() - 1 : 0u; h->cell_units = 0;
+  h->h_unit_ptr = std::move(p.unit_ptr); h->unit_cap = p.unit_cap;
+  h->sort_bits = p.sort_bits;
+}
+
+// step 3: everything on the device — the rows, the orders, the parameter block, the batch workspace (WRMF: its item-major CSR instead)
+int upload_data_set(cdae_hip* h, const cdae::plan::Plan& p, const int64_t* grp, const uint32_t* gcl) {
+  const uint64_t U = h->U, I = h->I;
+  const uint32_t B = p.B;
+  const size_t nnz = (size_t)p.row_ptr[U], IK = (size_t)I * h->Kp;
   CHK(dev_alloc(&h->d_row_ptr, U + 1));
   CHK(dev_alloc(&h->d_col, nnz));
-  HIPCHK(hipMemcpy(h->d_row_ptr, row_ptr, (U + 1) * sizeof(int64_t), hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(h->d_col, col, nnz * sizeof(uint32_t), hipMemcpyHostToDevice));
-  // decode launch order: most popular rows first (their example chains are the longest)
-  std::vector<uint32_t> order(I);
-  std::iota(order.begin(), order.end(), 0u);
-  std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return pop[a] > pop[b]; });
-  CHK(dev_alloc(&h->d_item_order, (size_t)I));
-  HIPCHK(hipMemcpy(h->d_item_order, order.data(), I * sizeof(uint32_t), hipMemcpyHostToDevice));
-  {
-    std::vector<uint32_t> rank_of(I);
-    for (uint32_t r = 0; r < I; ++r) rank_of[order[r]] = r;
-    CHK(dev_alloc(&h->d_rank_of, (size_t)I));
-    HIPCHK(hipMemcpy(h->d_rank_of, rank_of.data(), I * sizeof(uint32_t), hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(h->d_row_ptr, p.row_ptr, (U + 1) * sizeof(int64_t), hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(h->d_col, p.col, nnz * sizeof(uint32_t), hipMemcpyHostToDevice));
+  CHK(dev_upload(&h->d_item_order, p.order.data(), (size_t)I));
+  CHK(dev_upload(&h->d_rank_of, p.rank_of.data(), (size_t)I));
+  if (h->late_rows) {
+    CHK(dev_upload(&h->d_late_bits, p.split.late_bits.data(), (size_t)h->late_words));
+    const size_t nB = (size_t)std::max<uint64_t>(std::min<uint64_t>(h->B, U), 1) * cdae::LATE_MAX;
+    CHK(dev_alloc(&h->d_Ghot, nB)); CHK(dev_alloc(&h->d_hotdup, nB));
+    HIPCHK(hipMemset(h->d_Ghot, 0, nB * sizeof(float)));
+    HIPCHK(hipMemset(h->d_hotdup, 0xFF, nB * sizeof(uint32_t)));
   }
-  {
-    // hot rows: expected positives per batch (popularity x batch share) of at least CDAE_DECODE_HOT_POS (default 48);
-    // every row also receives ~ B * mean(n_u) * num_neg / I uniformly spread negatives
-    const char* ev = DEV_ENV("CDAE_DECODE_HOT_POS");
-    const double hot_pos = ev ? std::atof(ev) : 48.0;
-    const double share = (double)std::min<uint64_t>(h->B, U) / (double)U;
-    uint32_t hot = 0;
-    while (hot < I && (double)pop[order[hot]] * share >= hot_pos) ++hot;
-    h->hot_rows = std::min<uint32_t>((hot + 3u) & ~3u, (uint32_t)I);
-  }
-  {
-    // Late rows: the most popular of the hot rows (at most one lane of hidden_finish_kernel each).  Their terms of the hidden gradient are
-    // added by hidden_finish_kernel / hg_raw_kernel from Ghot, not gathered — in EVERY launch order (so that the fused launch, the
-    // separate launches and an item shard of one agree bit for bit); the gather tells them by a bitmap it stages in LDS (item spaces up
-    // to 65 536).  CDAE_NO_LATE_ROWS: round 5's arithmetic (developer switch).
-    const bool hybrid = h->K <= 256 && !h->mf && !h->cfg.full_output;
-    h->late_rows = 0;
-    if (hybrid && I <= 32u * cdae::LATE_BITS_WORDS && !DEV_ENV("CDAE_NO_LATE_ROWS")) {
-      // late: at least CDAE_DECODE_LATE_POS (default 48, i.e. the hot rows: measured 16 / 24 / 32 / 48 -> 0.0915 / 0.0918 / 0.0907 / 0.0898 ms per step) expected positives per batch, at most LATE_MAX rows; all of them take a
-      // wavefront of their own (a late row in the four-rows-per-wavefront format would need its own Ghot bookkeeping there)
-      const char* ev = DEV_ENV("CDAE_DECODE_LATE_POS");
-      const double late_pos = ev ? std::atof(ev) : 48.0;
-      const double share = (double)std::min<uint64_t>(h->B, U) / (double)U;
-      uint32_t late = 0;
-      while (late < I && late < cdae::LATE_MAX && (double)pop[order[late]] * share >= late_pos) ++late;
-      // (a batch must have examples enough to make the split worth its bookkeeping: none for tiny batches)
-      h->late_rows = h->hot_rows ? std::min<uint32_t>(std::min<uint32_t>((late + 3u) & ~3u, cdae::LATE_MAX), (uint32_t)I) : 0u;
-      h->hot_rows = std::max(h->hot_rows, h->late_rows);
-    }
-    h->late_words = (uint32_t)((I + 31) / 32);
-    {
-      // expected examples per batch of every row, by popularity rank: positives (popularity x batch share) + the uniformly drawn negatives
-      const double share = (double)std::min<uint64_t>(h->B, U) / (double)U;
-      const double neg_per_item = share * (double)row_ptr[U] * (double)h->hp.num_neg / (double)std::max<uint64_t>(I, 1);
-      h->h_rank_len.resize(I);
-      for (uint32_t r = 0; r < I; ++r) h->h_rank_len[r] = (float)((double)pop[order[r]] * share + neg_per_item);
-    }
-    if (h->late_rows) {
-      std::vector<uint32_t> bits(h->late_words, 0u);
-      for (uint32_t r = 0; r < h->late_rows; ++r) bits[order[r] >> 5] |= 1u << (order[r] & 31u);
-      CHK(dev_alloc(&h->d_late_bits, (size_t)h->late_words));
-      HIPCHK(hipMemcpy(h->d_late_bits, bits.data(), h->late_words * sizeof(uint32_t), hipMemcpyHostToDevice));
-      const size_t nB = (size_t)std::max<uint64_t>(std::min<uint64_t>(h->B, U), 1) * cdae::LATE_MAX;
-      CHK(dev_alloc(&h->d_Ghot, nB)); CHK(dev_alloc(&h->d_hotdup, nB));
-      HIPCHK(hipMemset(h->d_Ghot, 0, nB * sizeof(float)));
-      HIPCHK(hipMemset(h->d_hotdup, 0xFF, nB * sizeof(uint32_t)));
-    }
-    if (!h->h_err) CHK(err_slot_acquire(h->device, &h->h_err, &h->d_fused_err, &h->err_slot));
-    *(volatile uint32_t*)h->h_err = 0u;
-    h->fused_geo_set = false;
-    // The fused launch: needs late rows (else the gather would wait for the longest chains); hot rows take a CU per four of them, so
-    // at most half the chip's; the row matrices are addressed through 32-bit buffer offsets.
-    hipDeviceProp_t prop;
-    HIPCHK(hipGetDeviceProperties(&prop, h->device));
-    h->num_cus = (uint32_t)std::max(prop.multiProcessorCount, 16);
-    h->fused_possible = h->late_rows && h->hot_rows <= 2u * h->num_cus && !h->item_shard && (uint64_t)I * h->Kp * 4u < (1ull << 31) &&
-                        !DEV_ENV("CDAE_DECODE_UNFUSED");
+  if (!h->h_err) CHK(err_slot_acquire(h->device, &h->h_err, &h->d_fused_err, &h->err_slot));
+  *(volatile uint32_t*)h->h_err = 0u;
+  // The fused launch: needs late rows (else the gather would wait for the longest chains); hot rows take a CU per four of them, so
+  // at most half the chip's; the row matrices are addressed through 32-bit buffer offsets.
+  hipDeviceProp_t prop;
+  HIPCHK(hipGetDeviceProperties(&prop, h->device));
+  h->num_cus = (uint32_t)std::max(prop.multiProcessorCount, 16);
+  h->fused_possible = h->late_rows && h->hot_rows <= 2u * h->num_cus && !h->item_shard && (uint64_t)I * h->Kp * 4u < (1ull << 31) &&
+                      !DEV_ENV("CDAE_DECODE_UNFUSED");
 #ifdef CDAE_DECODE_TIMING
-    h->fused_possible = false;
+  h->fused_possible = false;
 #endif
-    h->fused_decode = h->fused_possible && h->allow_fused;
-  }
+  h->fused_decode = h->fused_possible && h->allow_fused;
 
   // parameters
-  const size_t IK = (size_t)I * h->Kp;
-  size_t o = 0;
-  std::memset(h->off, 0, sizeof h->off); std::memset(h->cnt, 0, sizeof h->cnt);
-  auto place = [&](uint32_t id, size_t n) { h->off[id] = o; h->cnt[id] = n; o += n; };
-  place(CDAE_P_W, IK); place(CDAE_P_W_AG, IK);
-  if (h->cfg.asymmetric) { place(CDAE_P_V, IK); place(CDAE_P_V_AG, IK); }
-  h->n_matrix = o;
-  place(CDAE_P_BP, I); place(CDAE_P_BP_AG, I);
-  place(CDAE_P_B, h->Kp); place(CDAE_P_B_AG, h->Kp);
-  h->n_shared = o;
   CHK(dev_alloc(&h->d_shared, h->n_shared));
   HIPCHK(hipMemset(h->d_shared, 0, h->n_shared * sizeof(float)));
   const size_t WR = (size_t)h->wu_rows();                   // private rows held here: every user, or an item shard's own user range
@@ -1752,285 +1705,147 @@ int cdae_hip_set_interactions(cdae_hip_t* h, uint64_t U, uint64_t I, const int64
     CHK(dev_alloc(&h->d_Uu_ag, WR * h->Kp));
   }
 
-  if (h->mf == 3u) {
-    // WRMF: no example lists, no batch workspace.  What is left: the bias arrays IMF's serving reads, the accumulators' constants, and
-    // the item-major CSR of the item half-step — a counting sort on the host, users ascending inside a column
-    CHK(dev_alloc(&h->d_ub, (size_t)U)); CHK(dev_alloc(&h->d_ub_ag, (size_t)U));
-    h->cnt[CDAE_P_UB] = h->cnt[CDAE_P_UB_AG] = (size_t)U;
-    HIPCHK(hipMemset(h->d_ub, 0, (size_t)U * sizeof(float)));
-    std::vector<int64_t> tptr(I + 1, 0);
-    for (uint64_t i = 0; i < I; ++i) tptr[i + 1] = tptr[i] + (int64_t)pop[i];
-    std::vector<uint32_t> tcol(std::max<size_t>(nnz, 1));
-    {
-      std::vector<int64_t> cursor(tptr.begin(), tptr.end() - 1);
-      for (uint64_t u = 0; u < U; ++u)
-        for (int64_t p = row_ptr[u]; p < row_ptr[u + 1]; ++p) tcol[(size_t)cursor[col[p]]++] = (uint32_t)u;
+  const bool als = h->mf == 3u;      // WRMF: no example lists, no batch workspace — the item-major CSR of its item half-step instead
+  if (!als) {
+    if (h->shard_sampled()) {
+      const size_t gnnz = (size_t)grp[U];
+      CHK(dev_alloc(&h->d_grow_ptr, U + 1)); CHK(dev_alloc(&h->d_gcol, gnnz));
+      HIPCHK(hipMemcpy(h->d_grow_ptr, grp, (U + 1) * sizeof(int64_t), hipMemcpyHostToDevice));
+      HIPCHK(hipMemcpy(h->d_gcol, gcl, gnnz * sizeof(uint32_t), hipMemcpyHostToDevice));
+      CHK(dev_upload(&h->d_gunit_ptr, h->h_gunit_ptr.data(), (size_t)U + 1));
+      CHK(dev_upload(&h->d_gunit_user, p.gunit_user.data(), p.gunit_user.size()));
     }
-    CHK(dev_alloc(&h->d_tptr, I + 1));
-    CHK(dev_alloc(&h->d_tcol, nnz));
-    HIPCHK(hipMemcpy(h->d_tptr, tptr.data(), (I + 1) * sizeof(int64_t), hipMemcpyHostToDevice));
-    if (nnz) HIPCHK(hipMemcpy(h->d_tcol, tcol.data(), nnz * sizeof(uint32_t), hipMemcpyHostToDevice));
-    CHK(dev_alloc(&h->d_touched, (size_t)I));                 // (nothing touches an item here; the delta entry points read the array)
-    HIPCHK(hipMemset(h->d_touched, 0, (size_t)I * sizeof(uint32_t)));
-    h->Ecap = 0; h->seq = 0; h->pre_n = 0; h->unit_cap = 0;
-    h->h_unit_ptr.assign(U + 1, 0u);
-    h->bucket_sort = false; h->counting_sort = false;
-    auto fillm = [&](float* M, size_t rows, uint32_t K, uint32_t Kp, float v, float pad) {
-      hipLaunchKernelGGL(cdae::fill_matrix_kernel, dim3((uint32_t)((rows * Kp + 255) / 256)), dim3(256), 0, h->stream, M, rows, K, Kp, v, pad);
-    };
-    fillm(h->P(CDAE_P_W_AG), I, h->K, h->Kp, 1e-4f, 1.f);
-    fillm(h->d_Wu_ag, WR, h->K, h->Kp, 1e-4f, 1.f);
-    fillm(h->P(CDAE_P_B_AG), 1, h->K, h->Kp, 1e-4f, 1.f);
-    fillm(h->P(CDAE_P_BP_AG), I, 1, 1, 1e-4f, 1.f);
-    fillm(h->d_ub_ag, U, 1, 1, 1e-4f, 1.f);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(h->stream));
-    return 0;
-  }
-
-  // batch workspace sized for the largest batch of B consecutive users
-  const uint32_t B = (uint32_t)std::min<uint64_t>(h->B, U);
-  uint64_t emax = 0;
-  for (uint64_t s0 = 0; s0 < U; ++s0) {   // any window [s0, s0+B) may be requested by train_users
-    const uint64_t s1 = std::min<uint64_t>(U, s0 + B);
-    emax = std::max<uint64_t>(emax, (uint64_t)(row_ptr[s1] - row_ptr[s0]));
-  }
-  h->ex_per_pos = h->mf == 2 ? 2u * h->hp.num_neg : 1u + h->hp.num_neg;
-  h->Ecap = emax * h->ex_per_pos;
-  h->h_grow_ptr.clear(); h->h_gunit_ptr.clear();
-  if (h->shard_sampled()) {
-    // the example list of a batch is the single-GPU one (every position of the WHOLE rows, every negative draw), entries of other
-    // shards' rows VOID: capacity, units and offsets come from the whole rows
-    const int64_t* grp = h->g_row_ptr_src;
-    const uint32_t* gcl = h->g_col_src;
-    h->g_row_ptr_src = nullptr; h->g_col_src = nullptr;
-    if (grp[0] != 0) return fail("whole-row row_ptr[0] must be 0");
-    h->h_grow_ptr.assign(grp, grp + U + 1);
-    uint64_t gmax = 0;
-    for (uint64_t s0 = 0; s0 < U; ++s0) gmax = std::max<uint64_t>(gmax, (uint64_t)(grp[std::min<uint64_t>(U, s0 + B)] - grp[s0]));
-    h->Ecap = gmax * h->ex_per_pos;
-    const size_t gnnz = (size_t)grp[U];
-    CHK(dev_alloc(&h->d_grow_ptr, U + 1)); CHK(dev_alloc(&h->d_gcol, gnnz));
-    HIPCHK(hipMemcpy(h->d_grow_ptr, grp, (U + 1) * sizeof(int64_t), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(h->d_gcol, gcl, gnnz * sizeof(uint32_t), hipMemcpyHostToDevice));
-    h->h_gunit_ptr.assign(U + 1, 0u);
-    for (uint64_t u = 0; u < U; ++u)
-      h->h_gunit_ptr[u + 1] = h->h_gunit_ptr[u] + (uint32_t)((grp[u + 1] - grp[u] + h->hp.unit_pos - 1) / h->hp.unit_pos);
-    CHK(dev_alloc(&h->d_gunit_ptr, U + 1));
-    HIPCHK(hipMemcpy(h->d_gunit_ptr, h->h_gunit_ptr.data(), (U + 1) * sizeof(uint32_t), hipMemcpyHostToDevice));
-    std::vector<uint32_t> guser(h->h_gunit_ptr[U]);
-    for (uint64_t u = 0; u < U; ++u)
-      for (uint32_t g = h->h_gunit_ptr[u]; g < h->h_gunit_ptr[u + 1]; ++g) guser[g] = (uint32_t)u;
-    CHK(dev_alloc(&h->d_gunit_user, std::max<size_t>(guser.size(), 1)));
-    HIPCHK(hipMemcpy(h->d_gunit_user, guser.data(), guser.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-  }
-  h->seq = 0; h->pre_n = 0;
-  // opt-in (CDAE_SORT_COUNTING=1): measured slower than rocPRIM's onesweep beside the training kernels (DESIGN.md §5, profiles/r02_*)
-  // opt-in (CDAE_SORT_TILE=1).  Measured (profiles/r02_tile_sort.txt): the four launches take 72 us against rocPRIM's ten launches / ~100 us
-  // per batch on the prep stream, yet the training step is the same within 1 % at 256 users and 3 % slower at 512 — the prep
-  // stream runs beside the training kernels, and what counts there is how much it disturbs them, not its own length
-  // (round 4: the tile kernels skip VOID examples, so a sampled item shard can take them too — there the prep chain is NOT hidden
-  // behind a look-ahead lane and the library sort's launches and fills are the larger part of it)
-  h->counting_sort = I <= cdae::TILE_SORT_MAX_ITEMS && DEV_ENV("CDAE_SORT_TILE") != nullptr;
-  // DEFAULT since round 5: bucket_sort_kernel — one narrow launch, every workgroup owns a range of item ids cut HERE so that the
-  // ranges expect equal numbers of examples per batch: B * pop[i] / U positives + the uniformly drawn negatives.  It scans the batch's
-  // whole 16-bit key list once per range and pass, so it is for batches up to BUCKET_MAX_EXAMPLES examples (256-512 users at the
-  // BASELINE shapes) over at most 65536 items; beyond that the library sort below stays.  CDAE_SORT_LIBRARY (developer build): the
-  // library sort + segment_kernel everywhere (the A/B side of the bit-equality tests).
-  h->bucket_sort = false; h->bucket_ranges = 0; h->cell_units = 0;
-  {
-    // full-output blocks list their positives only and are long (thousands of users).  There the one narrow launch is the wrong shape: its
-    // workgroups (1024 threads, 90 KB of LDS: a CU each) run ~130 us beside a fused decode whose grid wants every CU (ML-10M shape, 2048
-    // users per block: full_decode_fused_kernel 57 -> 93 us, step 0.203 -> 0.24 ms), and from ~300 K examples on it is longer than the
-    // block it prepares (4096 users: 0.43 ms against a 0.33 ms step).  Blocks above 100 K examples keep the library sort's short launches.
-    const uint64_t BUCKET_MAX_EXAMPLES = h->cfg.full_output ? 100000 : 600000;
-    const uint64_t keys = I + (h->shard_sampled() ? 1u : 0u);
-    if (keys <= 65536 && !h->counting_sort && !h->mf_seq && h->Ecap <= BUCKET_MAX_EXAMPLES && h->Ecap > 0 && !DEV_ENV("CDAE_SORT_LIBRARY")) {
-      const double b_share = (double)B / (double)U;
-      const double draw_items = (double)(h->shard_sampled() ? h->I_global : I);
-      const double whole_nnz = h->shard_sampled() ? (double)h->h_grow_ptr[U] : (double)nnz;
-      const uint32_t negs = h->mf == 2 ? 2u * h->hp.num_neg - 0u : h->hp.num_neg;      // (BPR lists the positive once per pair too: weights only balance, any estimate is legal)
-      const double neg_per_item = b_share * whole_nnz * (double)negs / draw_items;
-      std::vector<double> wgt(I);
-      double total = 0.0;
-      for (uint64_t i = 0; i < I; ++i) { wgt[i] = b_share * (double)pop[i] + neg_per_item; total += wgt[i]; }
-      const double per_range = std::max(total / 256.0, std::min(2730.0, total / 8.0));   // ~2.7 K examples per range: half the LDS window
-      std::vector<uint32_t> cut{0u};
-      double acc = 0.0;
-      for (uint64_t i = 0; i < I; ++i) {
-        acc += wgt[i];
-        if (i + 1 < I && (acc >= per_range || (i + 1) - cut.back() == cdae::BK_ITEMS)) { cut.push_back((uint32_t)(i + 1)); acc = 0.0; }
-      }
-      cut.push_back((uint32_t)I);
-      if (cut.size() - 1 <= cdae::BK_MAX_RANGES) {
-        h->bucket_sort = true;
-        h->bucket_ranges = (uint32_t)cut.size() - 1;
-        CHK(dev_alloc(&h->d_bucket_cut, cut.size()));
-        HIPCHK(hipMemcpy(h->d_bucket_cut, cut.data(), cut.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-        // cells: sample_kernel routes every example into the cell of (its item's range, its unit), so that the sort reads its range's cells
-        // instead of scanning the batch's key list.  The CDAE sampler only; <= 256 ranges (LDS counters per wavefront); example indices must
-        // fit the entry's 20 bits (Ecap <= 600 000 does)
-        if (!h->mf && h->bucket_ranges <= cdae::BKC_MAX_RANGES && h->Ecap < (1ull << (32 - cdae::BKC_ITEM_BITS)) && !DEV_ENV("CDAE_SORT_SCAN")) {
-          std::vector<uint16_t> rof(I);
-          for (uint32_t r = 0; r + 1 < cut.size(); ++r)
-            for (uint32_t i = cut[r]; i < cut[r + 1]; ++i) rof[i] = (uint16_t)r;
-          CHK(dev_alloc(&h->d_range_of, (size_t)I));
-          HIPCHK(hipMemcpy(h->d_range_of, rof.data(), I * sizeof(uint16_t), hipMemcpyHostToDevice));
+    if (h->bucket_sort) {
+      CHK(dev_upload(&h->d_bucket_cut, p.bucket.cut.data(), p.bucket.cut.size()));
+      if (!p.bucket.range_of.empty()) CHK(dev_upload(&h->d_range_of, p.bucket.range_of.data(), (size_t)I));
+    }
+    CHK(dev_upload(&h->d_unit_ptr, h->h_unit_ptr.data(), (size_t)U + 1));
+    CHK(dev_upload(&h->d_unit_user, p.unit_user.data(), p.unit_user.size()));
+    CHK(dev_alloc(&h->d_Hpart, (size_t)h->unit_cap * h->Kp));
+    CHK(dev_alloc(&h->d_uptr_tmp, (size_t)B + 1));
+    {
+      const uint32_t one_unit[2] = {0u, 1u};          // explicit-input step: one user, one unit
+      HIPCHK(hipMemcpy(h->d_uptr_tmp, one_unit, sizeof one_unit, hipMemcpyHostToDevice));
+    }
+    for (auto& b : h->ex) {
+      CHK(dev_alloc(&b.item, h->Ecap)); CHK(dev_alloc(&b.val, h->Ecap));
+      CHK(dev_alloc(&b.sorted_item, h->Ecap)); CHK(dev_alloc(&b.sorted_val, h->Ecap));
+      CHK(dev_alloc(&b.seg, 4 * (size_t)I));                   // first | one-past-last position by item, then the same by popularity rank
+      CHK(dev_alloc(&b.dup_of_pos, h->Ecap)); CHK(dev_alloc(&b.dup_of_ex, h->Ecap)); CHK(dev_alloc(&b.dup_count, cdae::DUP_STRIPES));
+      if (packs_rows(h)) CHK(dev_alloc(&b.pack, ((size_t)I + 3) & ~(size_t)3));   // whole wavefronts of the rows [hot_rows, I)
+      if (h->counting_sort) {
+        CHK(dev_alloc(&b.item_count, (size_t)I)); CHK(dev_alloc(&b.prefix, (size_t)I + 1));
+        CHK(dev_alloc(&b.rank, (size_t)I)); CHK(dev_alloc(&b.bucketed, h->Ecap));
+        CHK(dev_alloc(&b.tile_hist, (size_t)((h->Ecap + cdae::TILE_EX - 1) / cdae::TILE_EX + 1) * I));
+        CHK(dev_alloc(&b.block_total, 128));
+      } else if (I + (h->shard_sampled() ? 1u : 0u) <= 65536) { CHK(dev_alloc(&b.key16, h->Ecap + 8)); CHK(dev_alloc(&b.sorted_key16, h->Ecap)); }   // (a sampled item shard sorts one more key: VOID = I)
+      if (h->bucket_sort) { CHK(dev_alloc(&b.bucketed, h->Ecap)); }
+      b.cell_tag = 0;
+      if (h->bucket_sort && h->d_range_of) {
+        // [ranges][units of the largest batch][BKC_SLOTS] words; beyond 256 MiB per set (or 16 384 units) the sort scans instead
+        const size_t words = (size_t)h->bucket_ranges * h->unit_cap * cdae::BKC_SLOTS;
+        if (h->unit_cap <= cdae::BK_CELL_UNITS_MAX && words * sizeof(uint32_t) <= (256ull << 20)) {
+          CHK(dev_alloc(&b.cells, words));
+          CHK(dev_alloc(&b.cell_flag, 1));
+          HIPCHK(hipMemset(b.cell_flag, 0, sizeof(uint32_t)));
+          h->cell_units = h->unit_cap;
         }
       }
+      CHK(dev_alloc(&b.wg_state, cdae::BK_MAX_RANGES));
+      HIPCHK(hipMemset(b.wg_state, 0, cdae::BK_MAX_RANGES * sizeof(uint32_t)));
+      if (!b.ready) { HIPCHK(hipEventCreateWithFlags(&b.ready, sync_event_flags())); HIPCHK(hipEventCreateWithFlags(&b.released, sync_event_flags())); }
+      HIPCHK(hipEventRecord(b.released, h->stream));
     }
-  }
-  h->h_unit_ptr.assign(U + 1, 0u);
-  for (uint64_t u = 0; u < U; ++u)
-    h->h_unit_ptr[u + 1] = h->h_unit_ptr[u] + (uint32_t)((row_ptr[u + 1] - row_ptr[u] + h->hp.unit_pos - 1) / h->hp.unit_pos);
-  h->unit_cap = 0;
-  for (uint64_t s0 = 0; s0 < U; ++s0) {
-    const uint64_t s1 = std::min<uint64_t>(U, s0 + B);
-    h->unit_cap = std::max(h->unit_cap, h->h_unit_ptr[s1] - h->h_unit_ptr[s0]);
-  }
-  // cdae_hip_encode takes arbitrary user lists of up to B users: the heaviest B users bound its unit count
-  {
-    std::vector<uint32_t> per(U);
-    for (uint64_t u = 0; u < U; ++u) per[u] = h->h_unit_ptr[u + 1] - h->h_unit_ptr[u];
-    std::partial_sort(per.begin(), per.begin() + B, per.end(), std::greater<uint32_t>());
-    uint64_t top = 0;
-    for (uint32_t i = 0; i < B; ++i) top += per[i];
-    h->unit_cap = (uint32_t)std::max<uint64_t>(h->unit_cap, top);
-  }
-  if (h->shard_sampled())                                   // hidden_gather's partial rows are per unit of the WHOLE rows
-    for (uint64_t s0 = 0; s0 < U; ++s0)
-      h->unit_cap = std::max(h->unit_cap, h->h_gunit_ptr[std::min<uint64_t>(U, s0 + B)] - h->h_gunit_ptr[s0]);
-  CHK(dev_alloc(&h->d_unit_ptr, U + 1));
-  HIPCHK(hipMemcpy(h->d_unit_ptr, h->h_unit_ptr.data(), (U + 1) * sizeof(uint32_t), hipMemcpyHostToDevice));
-  {
-    std::vector<uint32_t> unit_user(h->h_unit_ptr[U]);
-    for (uint64_t u = 0; u < U; ++u)
-      for (uint32_t g = h->h_unit_ptr[u]; g < h->h_unit_ptr[u + 1]; ++g) unit_user[g] = (uint32_t)u;
-    CHK(dev_alloc(&h->d_unit_user, std::max<size_t>(unit_user.size(), 1)));
-    HIPCHK(hipMemcpy(h->d_unit_user, unit_user.data(), unit_user.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-  }
-  CHK(dev_alloc(&h->d_Hpart, (size_t)h->unit_cap * h->Kp));
-  CHK(dev_alloc(&h->d_uptr_tmp, (size_t)B + 1));
-  {
-    const uint32_t one_unit[2] = {0u, 1u};          // explicit-input step: one user, one unit
-    HIPCHK(hipMemcpy(h->d_uptr_tmp, one_unit, sizeof one_unit, hipMemcpyHostToDevice));
-  }
-  if ((uint64_t)B * h->Kp * sizeof(float) > 0x7FFFFFFFull)      // decode addresses z rows with 31-bit byte offsets (buffer loads, cdae_kernels.hpp)
-    return fail("batch_users %u x row stride %u floats exceeds the 2 GiB the batch's Z may occupy; lower batch_users", B, h->Kp);
-  if (h->Ecap > 0xFFFFFFF0ull) return fail("batch of %u users holds %llu examples (> 2^32); lower batch_users", B, (unsigned long long)h->Ecap);
-  for (auto& b : h->ex) {
-    CHK(dev_alloc(&b.item, h->Ecap)); CHK(dev_alloc(&b.val, h->Ecap));
-    CHK(dev_alloc(&b.sorted_item, h->Ecap)); CHK(dev_alloc(&b.sorted_val, h->Ecap));
-    CHK(dev_alloc(&b.seg, 4 * (size_t)I));                   // first | one-past-last position by item, then the same by popularity rank
-    CHK(dev_alloc(&b.dup_of_pos, h->Ecap)); CHK(dev_alloc(&b.dup_of_ex, h->Ecap)); CHK(dev_alloc(&b.dup_count, cdae::DUP_STRIPES));
-    if (packs_rows(h)) CHK(dev_alloc(&b.pack, ((size_t)I + 3) & ~(size_t)3));   // whole wavefronts of the rows [hot_rows, I)
-    if (h->counting_sort) {
-      CHK(dev_alloc(&b.item_count, (size_t)I)); CHK(dev_alloc(&b.prefix, (size_t)I + 1));
-      CHK(dev_alloc(&b.rank, (size_t)I)); CHK(dev_alloc(&b.bucketed, h->Ecap));
-      CHK(dev_alloc(&b.tile_hist, (size_t)((h->Ecap + cdae::TILE_EX - 1) / cdae::TILE_EX + 1) * I));
-      CHK(dev_alloc(&b.block_total, 128));
-    } else if (I + (h->shard_sampled() ? 1u : 0u) <= 65536) { CHK(dev_alloc(&b.key16, h->Ecap + 8)); CHK(dev_alloc(&b.sorted_key16, h->Ecap)); }   // (a sampled item shard sorts one more key: VOID = I)
-    if (h->bucket_sort) { CHK(dev_alloc(&b.bucketed, h->Ecap)); }
-    b.cell_tag = 0;
-    if (h->bucket_sort && h->d_range_of) {
-      // [ranges][units of the largest batch][BKC_SLOTS] words; beyond 256 MiB per set (or 16 384 units) the sort scans instead
-      const size_t words = (size_t)h->bucket_ranges * h->unit_cap * cdae::BKC_SLOTS;
-      if (h->unit_cap <= cdae::BK_CELL_UNITS_MAX && words * sizeof(uint32_t) <= (256ull << 20)) {
-        CHK(dev_alloc(&b.cells, words));
-        CHK(dev_alloc(&b.cell_flag, 1));
-        HIPCHK(hipMemset(b.cell_flag, 0, sizeof(uint32_t)));
-        h->cell_units = h->unit_cap;
-      }
+    CHK(dev_alloc(&h->d_D0, IK));
+    {
+      // one correction row per duplicate negative of a batch (~2 % of the examples at ML-10M shape); beyond the
+      // capacity decode falls back to atomics.  Zero-filled once: decode's 16-lane path leaves elements >= 64 NV + 16 NT
+      // of a row untouched and the gather reads whole rows.
+      const char* ev = DEV_ENV("CDAE_DUP_CAP");
+      const uint64_t want = h->mf ? 1 : (ev ? std::strtoull(ev, nullptr, 10) : std::max<uint64_t>(65536, h->Ecap / 4));   // small problems: every example (IMF / BPR have no correction rows)
+      h->dup_cap = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(want, 1), std::max<uint64_t>(h->Ecap, 1));
+      h->dup_stripes = std::max<uint32_t>(1u, std::min<uint32_t>(cdae::DUP_STRIPES, h->dup_cap / 4096u));
+      if ((uint64_t)h->dup_cap * h->Kp * 4u >= (1ull << 31)) h->fused_possible = h->fused_decode = false;     // (32-bit buffer offsets in the fused launch)
+      CHK(dev_alloc(&h->d_dup_corr, (size_t)h->dup_cap * h->Kp));
+      HIPCHK(hipMemset(h->d_dup_corr, 0, (size_t)h->dup_cap * h->Kp * sizeof(float)));
     }
-    CHK(dev_alloc(&b.wg_state, cdae::BK_MAX_RANGES));
-    HIPCHK(hipMemset(b.wg_state, 0, cdae::BK_MAX_RANGES * sizeof(uint32_t)));
-    if (!b.ready) { HIPCHK(hipEventCreateWithFlags(&b.ready, sync_event_flags())); HIPCHK(hipEventCreateWithFlags(&b.released, sync_event_flags())); }
-    HIPCHK(hipEventRecord(b.released, h->stream));
+    CHK(dev_alloc(&h->d_G, h->Ecap));
   }
-  CHK(dev_alloc(&h->d_D0, IK));
-  {
-    // one correction row per duplicate negative of a batch (~2 % of the examples at ML-10M shape); beyond the
-    // capacity decode falls back to atomics.  Zero-filled once: decode's 16-lane path leaves elements >= 64 NV + 16 NT
-    // of a row untouched and the gather reads whole rows.
-    const char* ev = DEV_ENV("CDAE_DUP_CAP");
-    const uint64_t want = h->mf ? 1 : (ev ? std::strtoull(ev, nullptr, 10) : std::max<uint64_t>(65536, h->Ecap / 4));   // small problems: every example (IMF / BPR have no correction rows)
-    h->dup_cap = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(want, 1), std::max<uint64_t>(h->Ecap, 1));
-    h->dup_stripes = std::max<uint32_t>(1u, std::min<uint32_t>(cdae::DUP_STRIPES, h->dup_cap / 4096u));
-    if ((uint64_t)h->dup_cap * h->Kp * 4u >= (1ull << 31)) h->fused_possible = h->fused_decode = false;     // (32-bit buffer offsets in the fused launch)
-    CHK(dev_alloc(&h->d_dup_corr, (size_t)h->dup_cap * h->Kp));
-    HIPCHK(hipMemset(h->d_dup_corr, 0, (size_t)h->dup_cap * h->Kp * sizeof(float)));
-  }
-  CHK(dev_alloc(&h->d_G, h->Ecap));
-  if (h->mf) {
-    const uint64_t inst_cap = emax * (h->mf == 2 ? h->hp.num_neg : 1u + h->hp.num_neg);
-    CHK(dev_alloc(&h->d_UVpre, (size_t)inst_cap * h->Kp));
+  if (h->mf) {                                              // IMF / BPR / WRMF: the bias arrays (WRMF: the ones IMF's serving reads)
+    const uint64_t inst_cap = p.emax * (h->mf == 2 ? h->hp.num_neg : 1u + h->hp.num_neg);
+    if (!als) CHK(dev_alloc(&h->d_UVpre, (size_t)inst_cap * h->Kp));
     CHK(dev_alloc(&h->d_ub, (size_t)U)); CHK(dev_alloc(&h->d_ub_ag, (size_t)U));
     h->cnt[CDAE_P_UB] = h->cnt[CDAE_P_UB_AG] = (size_t)U;
     HIPCHK(hipMemset(h->d_ub, 0, (size_t)U * sizeof(float)));
   }
-  h->sort_bits = 1;
-  while ((1ull << h->sort_bits) < I + (h->shard_sampled() ? 1u : 0u)) h->sort_bits++;
-  h->sort_tmp_bytes = 0;
-  HIPCHK(rocprim::radix_sort_pairs(nullptr, h->sort_tmp_bytes, h->ex[0].item, h->ex[0].sorted_item, h->ex[0].val,
-                                   h->ex[0].sorted_val, (size_t)std::max<uint64_t>(h->Ecap, 1), 0u, (unsigned)h->sort_bits, h->stream));
-  if (h->ex[0].key16) {
-    size_t bytes16 = 0;
-    HIPCHK(rocprim::radix_sort_pairs(nullptr, bytes16, h->ex[0].key16, h->ex[0].sorted_key16, h->ex[0].val, h->ex[0].sorted_val,
-                                     (size_t)std::max<uint64_t>(h->Ecap, 1), 0u, (unsigned)h->sort_bits, h->stream));
-    h->sort_tmp_bytes = std::max(h->sort_tmp_bytes, bytes16);
-  }
-  h->sort_tmp_stride = (h->sort_tmp_bytes + 255) & ~(size_t)255;
-  CHK(dev_alloc((char**)&h->d_sort_tmp, 2 * h->sort_tmp_stride));
-  const size_t BK = (size_t)B * h->Kp;
-  CHK(dev_alloc(&h->d_Z, BK)); CHK(dev_alloc(&h->d_Dz, BK)); CHK(dev_alloc(&h->d_HG, BK));
-  if (h->cfg.linear_function) { CHK(dev_alloc(&h->d_Ssum, BK)); CHK(dev_alloc(&h->d_delta_rows, BK)); }
-  if (h->cfg.full_output) {
-    h->Bp = (B + 127u) & ~127u;
-    // big item spaces and K > 256: 256-row GEMM tiles (the K > 256 launches — gemm1_loss_duo_kernel, gemm_tn_bf16_kernel — want them)
-    h->Ip = (I >= 32768 || h->Kp > 256) ? (((uint32_t)I + 255u) & ~255u) : (((uint32_t)I + 127u) & ~127u);
-    CHK(dev_alloc(&h->d_Zb, (size_t)h->Bp * h->Kp)); CHK(dev_alloc(&h->d_ZTb, (size_t)h->Kp * h->Bp));
-    CHK(dev_alloc(&h->d_Db, (size_t)h->Ip * h->Kp)); CHK(dev_alloc(&h->d_DTb, (size_t)h->Kp * h->Ip));
-    // G [Bp x Ip] only where a launch reads it: the NT form of GEMM 2 (K > 256 without gemm_tn_bf16_kernel, or CDAE_FULL_UNFUSED);
-    // the fused K <= 256 kernel and the TN form read G^T alone (2 GB less per handle at 1 M items x 1024 users)
-    if ((h->Kp > 256 || h->full_unfused) && !gemm2_tn_path(h)) CHK(dev_alloc(&h->d_Gb, (size_t)h->Bp * h->Ip));
-    CHK(dev_alloc(&h->d_GTb, (size_t)h->Ip * h->Bp));
-    CHK(dev_alloc(&h->d_dD, (size_t)h->Ip * h->Kp));
-    CHK(dev_alloc(&h->d_has_in, (size_t)h->Ip));
-    HIPCHK(hipMemsetAsync(h->d_has_in, 0, (size_t)h->Ip, h->stream));
-    {
-      // the rated-items bitmap is read by the fused K <= 256 decode only (the K = 512 launches patch their positives in place:
-      // full_positive_fixup_kernel) — round 5: no longer built where nothing reads it (128 MB and ~1 ms of prep stream per
-      // 1024-user block at 1 M items)
-      if (h->Kp <= 256 && !h->full_unfused) {
-        h->bits_stride = (size_t)B * ((I + 31) / 32);
-        CHK(dev_alloc(&h->d_bits_train, cdae_hip::NSETS * h->bits_stride));     // one per example-buffer set
-      }
-      // item slices of the fused decode: slices x Bp/128 workgroups ~ one per CU (measured best at B = 2048: 16 slices; every
-      // slice adds a [B x Kp] partial of hg)
-      const uint32_t tiles = h->Ip / (32 * cdae::FUSED_SUB), ublocks = h->Bp / 128;
-      h->full_slices = std::max<uint32_t>(1, std::min<uint32_t>({32u, tiles, (256u + ublocks - 1) / ublocks}));
+  if (als) {
+    CHK(dev_alloc(&h->d_tptr, I + 1));
+    CHK(dev_alloc(&h->d_tcol, nnz));
+    HIPCHK(hipMemcpy(h->d_tptr, p.item_major.ptr.data(), (I + 1) * sizeof(int64_t), hipMemcpyHostToDevice));
+    if (nnz) HIPCHK(hipMemcpy(h->d_tcol, p.item_major.col.data(), nnz * sizeof(uint32_t), hipMemcpyHostToDevice));
+  } else {
+    h->sort_tmp_bytes = 0;
+    HIPCHK(rocprim::radix_sort_pairs(nullptr, h->sort_tmp_bytes, h->ex[0].item, h->ex[0].sorted_item, h->ex[0].val,
+                                     h->ex[0].sorted_val, (size_t)std::max<uint64_t>(h->Ecap, 1), 0u, (unsigned)h->sort_bits, h->stream));
+    if (h->ex[0].key16) {
+      size_t bytes16 = 0;
+      HIPCHK(rocprim::radix_sort_pairs(nullptr, bytes16, h->ex[0].key16, h->ex[0].sorted_key16, h->ex[0].val, h->ex[0].sorted_val,
+                                       (size_t)std::max<uint64_t>(h->Ecap, 1), 0u, (unsigned)h->sort_bits, h->stream));
+      h->sort_tmp_bytes = std::max(h->sort_tmp_bytes, bytes16);
     }
-  }
-  if (h->cfg.full_output || h->item_shard) {
-    std::vector<uint32_t> iota((size_t)std::max<uint32_t>(B, h->item_shard ? EVAL_CHUNK : 0u) + 1);
-    std::iota(iota.begin(), iota.end(), 0u);
-    CHK(dev_alloc(&h->d_iota, iota.size()));
-    HIPCHK(hipMemcpy(h->d_iota, iota.data(), iota.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-    // item shard: [input sums | gathered Wu rows | gathered Uu rows] of a batch, one all-reduce buffer
-    if (h->item_shard) CHK(dev_alloc(&h->d_Hsum, (size_t)SHARD_BLOCKS * B * h->Kp));
-  }
-  {
-    size_t rows = 8 * (size_t)h->unit_cap;
+    h->sort_tmp_stride = (h->sort_tmp_bytes + 255) & ~(size_t)255;
+    CHK(dev_alloc((char**)&h->d_sort_tmp, 2 * h->sort_tmp_stride));
+    const size_t BK = (size_t)B * h->Kp;
+    CHK(dev_alloc(&h->d_Z, BK)); CHK(dev_alloc(&h->d_Dz, BK)); CHK(dev_alloc(&h->d_HG, BK));
+    if (h->cfg.linear_function) { CHK(dev_alloc(&h->d_Ssum, BK)); CHK(dev_alloc(&h->d_delta_rows, BK)); }
     if (h->cfg.full_output) {
-      rows = std::max(rows, (size_t)h->full_slices * B);
-      const uint32_t kps = gemm2_k_per_split(h);                                 // unfused path: one [Bp x Kp] slab per contraction split
-      rows = std::max(rows, (size_t)((h->Ip + kps - 1) / kps) * h->Bp);
+      h->Bp = (B + 127u) & ~127u;
+      // big item spaces and K > 256: 256-row GEMM tiles (the K > 256 launches — gemm1_loss_duo_kernel, gemm_tn_bf16_kernel — want them)
+      h->Ip = (I >= 32768 || h->Kp > 256) ? (((uint32_t)I + 255u) & ~255u) : (((uint32_t)I + 127u) & ~127u);
+      CHK(dev_alloc(&h->d_Zb, (size_t)h->Bp * h->Kp)); CHK(dev_alloc(&h->d_ZTb, (size_t)h->Kp * h->Bp));
+      CHK(dev_alloc(&h->d_Db, (size_t)h->Ip * h->Kp)); CHK(dev_alloc(&h->d_DTb, (size_t)h->Kp * h->Ip));
+      // G [Bp x Ip] only where a launch reads it: the NT form of GEMM 2 (K > 256 without gemm_tn_bf16_kernel, or CDAE_FULL_UNFUSED);
+      // the fused K <= 256 kernel and the TN form read G^T alone (2 GB less per handle at 1 M items x 1024 users)
+      if ((h->Kp > 256 || h->full_unfused) && !gemm2_tn_path(h)) CHK(dev_alloc(&h->d_Gb, (size_t)h->Bp * h->Ip));
+      CHK(dev_alloc(&h->d_GTb, (size_t)h->Ip * h->Bp));
+      CHK(dev_alloc(&h->d_dD, (size_t)h->Ip * h->Kp));
+      CHK(dev_alloc(&h->d_has_in, (size_t)h->Ip));
+      HIPCHK(hipMemsetAsync(h->d_has_in, 0, (size_t)h->Ip, h->stream));
+      {
+        // the rated-items bitmap is read by the fused K <= 256 decode only (the K = 512 launches patch their positives in place:
+        // full_positive_fixup_kernel) — round 5: no longer built where nothing reads it (128 MB and ~1 ms of prep stream per
+        // 1024-user block at 1 M items)
+        if (h->Kp <= 256 && !h->full_unfused) {
+          h->bits_stride = (size_t)B * ((I + 31) / 32);
+          CHK(dev_alloc(&h->d_bits_train, cdae_hip::NSETS * h->bits_stride));     // one per example-buffer set
+        }
+        // item slices of the fused decode: slices x Bp/128 workgroups ~ one per CU (measured best at B = 2048: 16 slices; every
+        // slice adds a [B x Kp] partial of hg)
+        const uint32_t tiles = h->Ip / (32 * cdae::FUSED_SUB), ublocks = h->Bp / 128;
+        h->full_slices = std::max<uint32_t>(1, std::min<uint32_t>({32u, tiles, (256u + ublocks - 1) / ublocks}));
+      }
     }
-    CHK(dev_alloc(&h->d_HGpart, rows * h->Kp));
+    if (h->cfg.full_output || h->item_shard) {
+      std::vector<uint32_t> iota((size_t)std::max<uint32_t>(B, h->item_shard ? EVAL_CHUNK : 0u) + 1);
+      std::iota(iota.begin(), iota.end(), 0u);
+      CHK(dev_alloc(&h->d_iota, iota.size()));
+      HIPCHK(hipMemcpy(h->d_iota, iota.data(), iota.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+      // item shard: [input sums | gathered Wu rows | gathered Uu rows] of a batch, one all-reduce buffer
+      if (h->item_shard) CHK(dev_alloc(&h->d_Hsum, (size_t)SHARD_BLOCKS * B * h->Kp));
+    }
+    {
+      size_t rows = 8 * (size_t)h->unit_cap;
+      if (h->cfg.full_output) {
+        rows = std::max(rows, (size_t)h->full_slices * B);
+        const uint32_t kps = gemm2_k_per_split(h);                                 // unfused path: one [Bp x Kp] slab per contraction split
+        rows = std::max(rows, (size_t)((h->Ip + kps - 1) / kps) * h->Bp);
+      }
+      CHK(dev_alloc(&h->d_HGpart, rows * h->Kp));
+    }
   }
-  CHK(dev_alloc(&h->d_touched, (size_t)I));
+  CHK(dev_alloc(&h->d_touched, (size_t)I));                 // (nothing touches an item of a WRMF handle; the delta entry points read the array)
   HIPCHK(hipMemset(h->d_touched, 0, (size_t)I * sizeof(uint32_t)));
-  CHK(dev_alloc(&h->d_uids, (size_t)B));
+  if (!als) CHK(dev_alloc(&h->d_uids, (size_t)B));
   // weights 0, accumulators 1e-4 (cdae.hpp:114,...), accumulator pad lanes 1: a well-defined state even
   // before init_params / set_param (a zero accumulator pad would make beta == 0 divide 0 by 0)
   auto fillm = [&](float* M, size_t rows, uint32_t K, uint32_t Kp, float v, float pad) {
@@ -2049,6 +1864,8 @@ int cdae_hip_set_interactions(cdae_hip_t* h, uint64_t U, uint64_t I, const int64
   HIPCHK(hipStreamSynchronize(h->stream));
   return 0;
 }
+
+}  // namespace
 
 int cdae_hip_init_params(cdae_hip_t* h, uint64_t seed) {
   if (h) h->db_valid = h->db_rows_valid = false;      // the bf16 images of the decoder no longer match it (full-output path, compute_batch_full)

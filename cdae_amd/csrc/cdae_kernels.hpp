@@ -23,6 +23,7 @@
 
 #include "../../include/cdae_rng.h"
 #include "cdae_exchange_algebra.h"
+#include "cdae_dataset_plan.h"      // the limits the host's data-set plan reads: DUP_STRIPES, LATE_MAX, LATE_BITS_WORDS, BKC_*, UNIT_POS_MAX
 
 namespace cdae {
 
@@ -31,12 +32,6 @@ constexpr uint32_t SLOT_MASK = 0x0FFFFFFFu;   // example word: slot | dup_prev <
 constexpr uint32_t DUP_PREV_BIT = 1u << 28;   // (set by segment_kernel) the row's previous example is the same user's
 constexpr uint32_t DUP_NEXT_BIT = 1u << 29;   // the row's next example is the same user's
 constexpr uint32_t DUP_NONE = 0xFFFFFFFFu;    // "no correction row" (dup_of_pos / dup_of_ex)
-// Correction rows are numbered by bumping a counter once per workgroup of segment_kernel / segment_sort_kernel.  ONE counter for
-// hundreds of workgroups is a chain of same-address returning atomics (~55 ns each: 37 us of a 660-workgroup launch); the index
-// space is cut into up to DUP_STRIPES stripes of at least 4096 rows with a counter each (workgroup b draws from stripe b mod
-// stripes; a stripe that runs out hands out DUP_NONE and decode falls back to its atomics path for those examples — small
-// problems use one stripe: they must not run out where one counter would not).
-constexpr uint32_t DUP_STRIPES = 64;
 constexpr uint32_t TARGET_BIT = 1u << 30;
 constexpr uint32_t INPUT_BIT = 1u << 31;
 
@@ -47,7 +42,6 @@ constexpr uint32_t INPUT_BIT = 1u << 31;
 // and hidden_finish_kernel adds  sum_r Ghot[slot][r] D0[item_order[r]]  (+ the runs' correction rows) itself, in rank order, behind
 // the gathered partial rows.  That is what lets the gather of everything else run INSIDE the decode launch, beside the late rows'
 // chains (decode_gather_kernel): a gather wavefront only ever waits for rows that finish early.
-constexpr uint32_t LATE_MAX = 64;               // one lane of hidden_finish_kernel per late row
 struct DecodeLate {
   float* Ghot;                                  // [batch users][LATE_MAX], zeroed by the batch's encode
   uint32_t* hotdup;                             // [batch users][LATE_MAX]: correction row of (user, late row)'s duplicate run (DUP_NONE: none)
@@ -284,9 +278,7 @@ __device__ __forceinline__ float wave_sum(float v) {
 // base): user slot s owns units uptr[s] .. uptr[s+1]-1.
 // bucket_sort_kernel's cells (cdae_sort_kernels.hpp): sample_kernel's wavefront (one work unit) drops every example into the cell of
 // (its item's range, the unit): BKC_SLOTS words, word 0 = how many the unit put there, then (example index << BKC_ITEM_BITS | item - range start)
-constexpr uint32_t BKC_SLOTS = 32, BKC_ITEM_BITS = 12, BKC_ITEM_MASK = (1u << BKC_ITEM_BITS) - 1u;
-constexpr uint32_t BKC_MAX_RANGES = 256;      // LDS counters per wavefront in sample_kernel
-constexpr uint32_t UNIT_POS_MAX = 128;     // HyperParams::unit_pos (set per data set / batch size by the host) never exceeds it
+constexpr uint32_t BKC_SLOTS = 32, BKC_ITEM_MASK = (1u << BKC_ITEM_BITS) - 1u;
 
 struct UnitRef { uint32_t slot, p0, p1; };   // user slot and the positive range [p0, p1) of the unit
 
@@ -1582,7 +1574,6 @@ struct GatherArgs {
 };
 constexpr uint32_t GATHER_CAP = 448;             // list entries per wavefront; a 128-example step adds at most 256 (flushed when fewer are free).  448,
                                                  // not 512: three workgroups of the fused launch and one of bucket_sort_kernel (88 KiB) then share a CU's LDS
-constexpr uint32_t LATE_BITS_WORDS = 2048;       // LDS copy of the late-row bitmap: item spaces up to 65 536
 
 // every thread of the workgroup: the late-row bitmap into LDS (before any wavefront leaves)
 __device__ __forceinline__ void stage_late_bits(uint32_t* lbits, const uint32_t* __restrict__ late_bits, uint32_t late_words) {

@@ -54,7 +54,6 @@ constexpr uint32_t SEGSORT_ITEMS = CDAE_SEGSORT_ITEMS;    // consecutive items p
 #endif
 constexpr uint32_t SEGSORT_WINDOW = CDAE_SEGSORT_WINDOW;   // examples held in LDS at a time (2 arrays of 8-byte values)
 
-constexpr uint32_t TILE_SORT_MAX_ITEMS = 32768;         // tile_scatter_kernel's cursors: 4 bytes per item of LDS (128 KiB at the limit)
 #ifndef CDAE_TILE_EX
 #define CDAE_TILE_EX 4096
 #endif
@@ -297,11 +296,8 @@ segment_sort_kernel(uint32_t num_items, const uint32_t* __restrict__ prefix, con
 // the window is ranked in global memory (correct, slow; never at the batch sizes in use).
 constexpr uint32_t BK_THREADS = 512;
 constexpr uint32_t BK_WINDOW = 4096;      // example words of one group held in LDS (x 2: arrival order, sorted)
-constexpr uint32_t BK_ITEMS = 2048;       // most items of one range (LDS counters: 4 per thread in bk_block_scan)
 constexpr uint32_t BK_WAVE_LIST = BK_WINDOW / (BK_THREADS / 64);   // scan fallback: records per wavefront list (they live in the sorted-words array until it is needed)
 constexpr uint32_t BK_SPIN_CAP = 1u << 21;  // polls (~0.5 us each) of a range's total before bucket_sort_kernel gives up (error bit 1)
-constexpr uint32_t BK_MAX_RANGES = 1024;  // wg_state words (sample_kernel clears them with the other per-batch counters)
-constexpr uint32_t BK_CELL_UNITS_MAX = 16384;   // most units of a batch the cell path takes (their counts, 2 bytes each, fit the `raw` array)
 constexpr size_t BK_LDS_BYTES = (size_t)BK_WINDOW * 8 * 2 + (size_t)BK_WINDOW * 2 + (size_t)(BK_ITEMS + 1) * 4 * 2 + 64 * 4;
 static_assert(BK_ITEMS <= 4 * BK_THREADS && BK_ITEMS <= (1u << BKC_ITEM_BITS), "bk_block_scan takes 4 counters per thread; a cell entry holds the item in BKC_ITEM_BITS bits");
 

@@ -161,7 +161,9 @@ int cdae_hip_destroy(cdae_hip_t* h);
 
 /* CSR of the training interactions: row_ptr[num_users+1], col_idx[nnz] sorted ascending and unique
  * inside each row (the reference's uid -> {iid -> label} hashtable, data-inl.hpp:414-429, with the
- * always-1 labels of yelp.cpp:60-66 dropped).  Copied; the caller keeps its arrays. */
+ * always-1 labels of yelp.cpp:60-66 dropped).  Copied; the caller keeps its arrays.  A call refused for its arguments (a
+ * malformed row, an owned-user range outside the users, a batch whose Z would exceed 2 GiB or whose list 2^32 examples) leaves the
+ * handle with the data set and parameters it had; a call that fails later (a device allocation) leaves it without a data set. */
 int cdae_hip_set_interactions(cdae_hip_t* h, uint64_t num_users, uint64_t num_items,
                               const int64_t* row_ptr, const uint32_t* col_idx);
 
