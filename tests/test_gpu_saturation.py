@@ -447,3 +447,118 @@ def test_mf_from_grid_scores(built, pairwise, loss, B):
     record_measured(f"saturation_mf_pair{int(pairwise)}_loss{loss}_B{B}", **{f"p{w}": e for w, e in errs.items()})
     worst = max(errs, key=errs.get)
     assert errs[worst] < MF_BOUND, (worst, errs)
+
+
+# ---- (g) fold-in of user nodes (fold_in_rows_kernel: its own uses of activate, act_deriv and loss_grad) ----------------------------
+FOLD_K, FOLD_LAMBDA = 128, 2.0 ** -6
+FOLD_LENS = (1, 3, 42, 43, 64, 129, 200)            # both roles at num_neg = 5 (a wavefront up to 42 items, a workgroup beyond)
+FOLD_UIDS = (1, cdae_amd.NO_USER, 1, 0, 1, cdae_amd.NO_USER, 1)
+
+
+FOLD_NAMES = ("wu", "wu_ag", "uu", "uu_ag")
+
+
+def _fold_errs(got, want):
+    return {n: float((np.abs(g - w) / (FLOOR + np.abs(w))).max()) for n, g, w in zip(FOLD_NAMES, got, want)}
+
+
+def _fold_model(I, tables, Wu, **kw):
+    """a handle over len(Wu) users that holds the given tables (no training), CROSS_ENTROPY, lr = 1/8, lambda = 2^-6"""
+    from test_gpu_rows import csr
+    U = Wu.shape[0]
+    model = cdae_amd.CDAE(cdae_amd.CDAEConfig(num_dim=FOLD_K, lt=cdae_amd.CROSS_ENTROPY, beta=1.0, batch_users=U, learn_rate=LR,
+                                              lambda_=FOLD_LAMBDA, **kw))
+    model.set_interactions(U, I, *csr([np.arange(3 * u, 3 * u + 3, dtype=np.uint32) for u in range(U)]))
+    model.init_params(0)
+    for which, arr in tables.items():
+        model.set(which, arr)
+    model.set(cdae_amd.P_WU, Wu)
+    return model
+
+
+def _fold_rows(I, seed):
+    from test_gpu_rows import csr
+    rng = np.random.default_rng(seed)
+    return csr([np.sort(rng.choice(I, n, replace=False)).astype(np.uint32) for n in FOLD_LENS]) + (np.array(FOLD_UIDS, np.uint32),)
+
+
+def _fold_yardstick(model, ptr, col, uids, n_epochs, frozen_delta=False):
+    """tests/fold_in_ref.py from the handle's fp32 parameters -> (want, z of every row's first step)"""
+    import fold_in_ref as ref
+    from test_gpu_fold_in import SEED, oracle_config, start_nodes
+    import oracle as orc
+    cfg = model.cfg
+    o = orc.Oracle(oracle_config(cfg), ptr.size - 1, model.num_items, ptr, col)
+    P = dict(W=model.get(cdae_amd.P_W).astype(np.float64), b=model.get(cdae_amd.P_B).astype(np.float64),
+             bp=model.get(cdae_amd.P_BP).astype(np.float64), V=model.get(cdae_amd.P_V).astype(np.float64) if cfg.asymmetric else None)
+    start = [a.astype(np.float64) for a in start_nodes(model, uids)]
+    z0 = np.stack([ref.step(o.cfg, P, col[ptr[r]:ptr[r + 1]], o.draw_inputs(SEED, 0, r, 0), o.draw_negatives(SEED, 0, r, 0),
+                            tuple(a[r] for a in start))[1] for r in range(ptr.size - 1)])
+    return ref.fold_in(o, P, start, SEED, 0, n_epochs), start, z0, o, P
+
+
+@pytest.mark.parametrize("adagrad", [True, False], ids=["ada", "sgd"])
+@pytest.mark.parametrize("act", ["sigmoid", "tanh"])
+def test_fold_in_from_saturated_hidden_units(built, act, adagrad):
+    """b carries the grid in units 0 .. 63 and user 1's Wu row carries it in units 64 .. 127; W = 0 (asymmetric: the decoder V is
+    not), so S = 0 and h = b + wu is the grid point itself, exactly, on the device and in the yardstick.  Two epochs against the fp64
+    yardstick under the bound test_sampled_training_from_saturated_parameters holds this activation and optimiser to.  Then ONE step:
+    where z is exactly 0, 1 or -1 (|h| > 18, or > 9 for tanh: act'(z) = 0, delta = 0) the node moves by the lambda wu term alone —
+    an equality: a unit whose wu is 0 keeps wu = 0 and wu_ag = 1e-4 bit for bit, and under plain SGD with power-of-two lr and lambda
+    every saturated unit is wu - lr lambda wu, which fp64 forms exactly and fmaf rounds once."""
+    from test_gpu_fold_in import SEED, fold_all
+    I = 977
+    rng = np.random.default_rng(41)
+    half = np.resize(GRID, 64)
+    b = np.r_[half, np.zeros(64)]
+    Wu = np.stack([np.zeros(FOLD_K), np.r_[np.zeros(64), half], rng.normal(0, 0.1, FOLD_K)])
+    tables = {cdae_amd.P_W: np.zeros((I, FOLD_K)), cdae_amd.P_V: rng.normal(0, 0.05, (I, FOLD_K)), cdae_amd.P_B: b,
+              cdae_amd.P_BP: rng.uniform(-1, 1, I)}
+    model = _fold_model(I, tables, Wu, asymmetric=True, using_adagrad=adagrad, tanh=(act == "tanh"))
+    ptr, col, uids = _fold_rows(I, 43)
+    thr = 9.0 if act == "tanh" else 18.0
+    bound = SAMPLED["tanh"][4] if act == "tanh" else SAMPLED["ce_ada_fused" if adagrad else "sq_sgd"][4]
+    want, start, z0, o, P = _fold_yardstick(model, ptr, col, uids, 2)
+    h0 = b[None, :] + start[0]
+    sat = np.abs(h0) > thr
+    np.testing.assert_array_equal(np.isin(z0, (0.0, 1.0, -1.0)) & (h0 != 0), sat)          # the premise: exactly saturated there
+    assert share_beyond(h0[uids == 1], thr) > 0.4 and share_beyond(h0, 88.5) > 0.05 and (np.abs(h0) == 1000).any()
+    got = fold_all(model, ptr, col, uids, n_epochs=2)
+    record_measured(f"saturation_fold_in_hidden_{act}_{'ada' if adagrad else 'sgd'}", **_fold_errs(got, want))
+    for name, g, w in zip(FOLD_NAMES, got, want):
+        assert_close(g, w, f"fold-in {act} {name}", atol=bound * FLOOR, rtol=bound)
+    assert np.abs(want[0] - start[0])[~sat].max() > 1e-3             # (the unsaturated units took real steps)
+    # one step: delta = 0 where z is saturated
+    one = fold_all(model, ptr, col, uids, n_epochs=1)
+    still = sat & (start[0] == 0)
+    assert still.any() and (one[0][still] == 0).all() and (one[1][still] == np.float32(1e-4)).all()
+    if not adagrad:
+        lam_only = (start[0] - LR * (FOLD_LAMBDA * start[0])).astype(np.float32)
+        assert (start[0][sat] != 0).any()
+        np.testing.assert_array_equal(one[0][sat], lam_only[sat])
+    model.close()
+
+
+def test_fold_in_from_saturated_scores(built):
+    """b' carries the grid (977 items: the 53 points again and again) and W ~ N(0, 0.02^2), so every example's y = W[j].z + b'[j] sits
+    within a fraction of its grid point: the kernel's branch-free CROSS_ENTROPY gradient beyond |y| > 18 and past the fp32 overflow of
+    e^-y, against the yardstick's clamped branches.  Two epochs of AdaGrad, both roles, under the sigmoid / AdaGrad bound of
+    test_sampled_training_from_saturated_parameters."""
+    from test_gpu_fold_in import SEED, fold_all
+    I = 977
+    rng = np.random.default_rng(47)
+    tables = {cdae_amd.P_W: rng.normal(0, 0.02, (I, FOLD_K)), cdae_amd.P_B: rng.normal(0, 0.3, FOLD_K), cdae_amd.P_BP: np.resize(GRID, I)}
+    Wu = rng.normal(0, 0.3, (3, FOLD_K))
+    model = _fold_model(I, tables, Wu)
+    ptr, col, uids = _fold_rows(I, 49)
+    bound = SAMPLED["ce_ada_fused"][4]
+    want, start, z0, o, P = _fold_yardstick(model, ptr, col, uids, 2)
+    examples = [np.r_[col[ptr[r]:ptr[r + 1]], o.draw_negatives(SEED, 0, r, 0)] for r in range(ptr.size - 1)]
+    y0 = np.concatenate([P["W"][E] @ z0[r] + P["bp"][E] for r, E in enumerate(examples)])        # the scores of every row's first step
+    assert share_beyond(y0, 18.0) > 0.4 and share_beyond(y0, 88.5) > 0.1 and share_beyond(y0, 500) > 0.02
+    got = fold_all(model, ptr, col, uids, n_epochs=2)
+    record_measured("saturation_fold_in_scores", **_fold_errs(got, want))
+    for name, g, w in zip(FOLD_NAMES, got, want):
+        assert_close(g, w, f"fold-in scores {name}", atol=bound * FLOOR, rtol=bound)
+    assert np.abs(want[0] - start[0]).max() > 1e-3
+    model.close()
