@@ -1765,6 +1765,10 @@ int upload_data_set(cdae_hip* h, const cdae::plan::Plan& p, const int64_t* grp, 
       const uint64_t want = h->mf ? 1 : (ev ? std::strtoull(ev, nullptr, 10) : std::max<uint64_t>(65536, h->Ecap / 4));   // small problems: every example (IMF / BPR have no correction rows)
       h->dup_cap = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(want, 1), std::max<uint64_t>(h->Ecap, 1));
       h->dup_stripes = std::max<uint32_t>(1u, std::min<uint32_t>(cdae::DUP_STRIPES, h->dup_cap / 4096u));
+      // Few workgroups draw (bucket_sort_kernel: one per range): one counter's chain is under 2 us, and stripes only strand capacity —
+      // a dense small problem (400 users x 200 items, num_neg = 12: 56 000 duplicates among a batch's 86 000 examples) overflowed its
+      // 16 stripes of 4096 rows with 65 536 rows allocated, and the atomics fallback made training differ from run to run.
+      if (h->bucket_sort && h->bucket_ranges <= 32u) h->dup_stripes = 1u;
       if ((uint64_t)h->dup_cap * h->Kp * 4u >= (1ull << 31)) h->fused_possible = h->fused_decode = false;     // (32-bit buffer offsets in the fused launch)
       CHK(dev_alloc(&h->d_dup_corr, (size_t)h->dup_cap * h->Kp));
       HIPCHK(hipMemset(h->d_dup_corr, 0, (size_t)h->dup_cap * h->Kp * sizeof(float)));

@@ -35,7 +35,7 @@ def test_init_params_match_counter_stream(tiny):
     assert np.all(model.get(1) == np.float32(1e-4)) and np.all(model.get(8) == 0)
 
 
-@pytest.mark.parametrize("K", [1, 10, 50, 64, 65, 200])
+@pytest.mark.parametrize("K", [1, 10, 50, 64, 65, 128, 129, 200, 256, 257, 512])
 @pytest.mark.parametrize("mode", [0, 1])
 def test_encode_matches_oracle(tiny, K, mode):
     model, o = make_pair(tiny, K=K)
@@ -505,18 +505,23 @@ def test_ragged_rows_multi_unit_users_and_long_rows(ragged, B, K):
     np.testing.assert_array_equal(rec_g[clear], rec_o[clear])
 
 
-@pytest.mark.parametrize("K,B", [(40, 2000), (200, 1500), (64, 700)])
-def test_item_rows_with_thousands_of_examples_per_batch(built, K, B):
-    """Few items, many users per batch: every item row holds hundreds to thousands of examples of ONE batch — the four-rows-per-
-    wavefront decode walks many 64-example chunks through its LDS ring (staging, wrap at 128, g write-out per chunk), the popular
-    rows exceed the LDS room their g is parked in (1280 examples) and fall back to per-chunk stores, input rows scan many chunks."""
+def few_items_many_users():
+    """60 items, 2000 users of 4 .. 13 items each (tests/test_gpu_step_tiers.py trains on it too)"""
     rng = np.random.default_rng(11)
     I, U = 60, 2000
     p = 1.0 / np.arange(1, I + 1) ** 0.8
     p /= p.sum()
     rows = [np.sort(rng.choice(I, size=int(rng.integers(4, 14)), replace=False, p=p)).astype(np.uint32) for _ in range(U)]
     ptr = np.r_[0, np.cumsum([r.size for r in rows])].astype(np.int64)
-    d = synth.Interactions(U, I, ptr, np.concatenate(rows), np.zeros(U + 1, np.int64), np.empty(0, np.uint32))
+    return synth.Interactions(U, I, ptr, np.concatenate(rows), np.zeros(U + 1, np.int64), np.empty(0, np.uint32))
+
+
+@pytest.mark.parametrize("K,B", [(40, 2000), (200, 1500), (64, 700)])
+def test_item_rows_with_thousands_of_examples_per_batch(built, K, B):
+    """Few items, many users per batch: every item row holds hundreds to thousands of examples of ONE batch — the four-rows-per-
+    wavefront decode walks many 64-example chunks through its LDS ring (staging, wrap at 128, g write-out per chunk), the popular
+    rows exceed the LDS room their g is parked in (1280 examples) and fall back to per-chunk stores, input rows scan many chunks."""
+    d = few_items_many_users()
     model, o = make_pair(d, K=K, B=B, num_neg=3)
     for ep in range(2):
         model.train_one_iteration(seed=4, epoch=ep)
