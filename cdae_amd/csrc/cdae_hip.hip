@@ -29,6 +29,7 @@
 
 #include "../../include/cdae_hip.h"
 #include "cdae_internal.hpp"
+#include "cdae_dev_buf.h"
 #include "cdae_kernels.hpp"
 #include "cdae_full_kernels.hpp"
 #include "cdae_recommend_kernels.hpp"
@@ -70,6 +71,20 @@ int fail(const char* fmt, ...) {
     if (rc__) return rc__;   \
   } while (0)
 
+}  // namespace
+
+// DevBuf's memory (cdae_dev_buf.h): the only hipMalloc / hipFree of a handle's device memory
+int cdae::mem::acquire(void** p, size_t bytes) {
+  HIPCHK(hipMalloc(p, bytes));
+  return 0;
+}
+int cdae::mem::release(void* p) {
+  HIPCHK(hipFree(p));
+  return 0;
+}
+
+namespace {
+
 // launch `KERNEL<NI>` for the handle's NI (elements of a K-vector per lane)
 #define DISPATCH_NI(ni, KERNEL, grid, block, shmem, stream, ...)                                  \
   do {                                                                                            \
@@ -95,37 +110,12 @@ template <class F> int dispatch_nch(uint32_t K, F&& f) {
   return f(std::integral_constant<int, 32>{});
 }
 
-template <class T> int dev_alloc(T** p, size_t n) {
-  HIPCHK(hipMalloc((void**)p, std::max<size_t>(n, 1) * sizeof(T)));
+// b.alloc(n), then n elements copied from the host
+template <class T> int dev_upload(DevBuf<T>& b, const T* src, size_t n) {
+  CHK(b.alloc(n));
+  HIPCHK(hipMemcpy(b.p, src, n * sizeof(T), hipMemcpyHostToDevice));
   return 0;
 }
-// dev_alloc, then n elements copied from the host
-template <class T> int dev_upload(T** d, const T* src, size_t n) {
-  CHK(dev_alloc(d, n));
-  HIPCHK(hipMemcpy(*d, src, n * sizeof(T), hipMemcpyHostToDevice));
-  return 0;
-}
-// Grow-only device workspace that owns its capacity: p holds at least cap units of `per` elements (the `per` of the ensure() calls
-// that grew it).  drop() is the only way either member is cleared, so a freed buffer can never keep a capacity that ensure() would
-// believe.  Every DevBuf of a handle is listed once, in drop_dev_bufs().
-template <class T> struct DevBuf {
-  T* p = nullptr;
-  size_t cap = 0;
-  int ensure(size_t n, size_t per = 1) {
-    if (cap >= n) return 0;
-    CHK(drop());
-    CHK(dev_alloc(&p, n * per));
-    cap = n;
-    return 0;
-  }
-  int drop() {                  // both members are cleared whatever hipFree answers
-    T* const old = p;
-    p = nullptr; cap = 0;
-    if (old) HIPCHK(hipFree(old));
-    return 0;
-  }
-  operator T*() const { return p; }
-};
 
 constexpr uint32_t MF_SEQ_USERS = 256;     // IMF / BPR sequential default: users per launch window (cdae_hip::mf_seq)
 // batches above this many users take the two-launch encode (a workgroup of 16 wavefronts per user is mostly idle wavefronts;
@@ -147,15 +137,15 @@ struct cdae_hip {
   cdae::HyperParams hp{};
 
   std::vector<int64_t> h_row_ptr;
-  int64_t* d_row_ptr = nullptr;
-  uint32_t* d_col = nullptr;
-  uint32_t* d_item_order = nullptr;
+  DevBuf<int64_t> d_row_ptr;
+  DevBuf<uint32_t> d_col;
+  DevBuf<uint32_t> d_item_order;
   uint32_t hot_rows = 0;            // decode: rows [0, hot_rows) of item_order get a wavefront of their own
   // late rows (cdae_kernels.hpp DecodeLate): the first late_rows of them leave their hidden-gradient terms to hidden_finish_kernel
   uint32_t late_rows = 0;
-  float* d_Ghot = nullptr;          // [B][LATE_MAX]
-  uint32_t* d_hotdup = nullptr;     // [B][LATE_MAX]
-  uint32_t* d_late_bits = nullptr;  // [(I + 31) / 32] bitmap of the late rows' items
+  DevBuf<float> d_Ghot;             // [B][LATE_MAX]
+  DevBuf<uint32_t> d_hotdup;        // [B][LATE_MAX]
+  DevBuf<uint32_t> d_late_bits;     // [(I + 31) / 32] bitmap of the late rows' items
   uint32_t late_words = 0;
   bool fused_decode = false;        // decode + gather as ONE launch (decode_gather_kernel); CDAE_DECODE_UNFUSED turns it off (developer switch)
   bool fused_possible = false;      // ... what set_interactions found possible; fused_decode = fused_possible && allow_fused
@@ -171,67 +161,65 @@ struct cdae_hip {
   bool row_pack = true;             // the four-row role takes its rows from ExBuf::pack (CDAE_ROW_PACK=0, developer switch: popularity order as before)
   std::vector<float> h_pack_len;    // [I - hot_rows] expected lengths of the packed rows, longest first: one synthetic draw from h_rank_len (fused launch: balancing packed groups)
   std::vector<float> h_rank_len;    // [I] expected examples per batch of the row of popularity rank r (fused launch: balancing the four-row groups over the SIMDs)
-  uint32_t* d_cold_map = nullptr;   // [decode workgroups x 4] four-row group of every wavefront of the fused launch's row workgroups (0xFFFFFFFF: none)
+  DevBuf<uint32_t> d_cold_map;      // [decode workgroups x 4] four-row group of every wavefront of the fused launch's row workgroups (0xFFFFFFFF: none)
   uint32_t num_cus = 256;
   cdae::DecodeLate decode_late() const { return cdae::DecodeLate{d_Ghot, d_hotdup, late_rows}; }
   cdae::LateFinish late_finish() { return cdae::LateFinish{d_Ghot, d_hotdup, d_item_order, d_D0, d_dup_corr, late_rows}; }
   // developer switches, read once in cdae_hip_create (DESIGN.md lists them)
   bool full_unfused = false;        // CDAE_FULL_UNFUSED: full-output decode as three separate GEMMs
   std::vector<uint32_t> h_unit_ptr;     // prefix of work units (<= hp.unit_pos positives each) per user
-  uint32_t* d_rank_of = nullptr;        // [I] inverse of d_item_order
-  uint32_t* d_unit_user = nullptr;      // [total units] user of every unit (kernels' unit -> user look-up)
-  uint32_t* d_unit_ptr = nullptr;
+  DevBuf<uint32_t> d_rank_of;           // [I] inverse of d_item_order
+  DevBuf<uint32_t> d_unit_user;         // [total units] user of every unit (kernels' unit -> user look-up)
+  DevBuf<uint32_t> d_unit_ptr;
   uint32_t unit_cap = 0;                // most units in any window of batch_users users
-  float* d_Hpart = nullptr;             // [unit_cap][Kp] encode partial sums
-  uint32_t* d_uptr_tmp = nullptr;       // per-call prefix for cdae_hip_encode's arbitrary user lists
+  DevBuf<float> d_Hpart;                // [unit_cap][Kp] encode partial sums
+  DevBuf<uint32_t> d_uptr_tmp;          // per-call prefix for cdae_hip_encode's arbitrary user lists
 
   // shared (item-side) parameters, one allocation: [W | W_ag | (V | V_ag) | bp | bp_ag | b | b_ag]
-  float* d_shared = nullptr;
+  DevBuf<float> d_shared;
   size_t n_shared = 0, n_matrix = 0;
   size_t off[CDAE_P_COUNT] = {0};
   size_t cnt[CDAE_P_COUNT] = {0};   // padded element counts
-  float* d_Wu = nullptr;
-  float* d_Wu_ag = nullptr;
-  float* d_Uu = nullptr;                // linear_function only: [U][Kp] per-user gate (cdae.hpp:437-438)
-  float* d_Uu_ag = nullptr;
-  float* d_Ssum = nullptr;              // linear_function only: [B][Kp] unscaled input sums of the batch (Uu step)
-  float* d_delta_rows = nullptr;        // linear_function only: [B][Kp] Uu[u] (.) delta_u (what the input rows receive)
+  DevBuf<float> d_Wu, d_Wu_ag;
+  DevBuf<float> d_Uu, d_Uu_ag;          // linear_function only: [U][Kp] per-user gate (cdae.hpp:437-438)
+  DevBuf<float> d_Ssum;                 // linear_function only: [B][Kp] unscaled input sums of the batch (Uu step)
+  DevBuf<float> d_delta_rows;           // linear_function only: [B][Kp] Uu[u] (.) delta_u (what the input rows receive)
 
   // batch workspace
   uint64_t Ecap = 0;
   // example lists are kept in NSETS sets: batch q uses set q % NSETS.  Batch t+1 (and, with the second prep lane, t+2) is
   // sampled and sorted on a prep stream while batch t trains
   struct ExBuf {
-    uint32_t* item = nullptr; uint64_t* val = nullptr;            // user-major example list
-    uint32_t* sorted_item = nullptr; uint64_t* sorted_val = nullptr;   // the same, stably sorted by item
-    uint32_t* seg = nullptr;                                      // [2*I]: first | one-past-last sorted position per item
-    uint16_t* key16 = nullptr; uint16_t* sorted_key16 = nullptr;      // 16-bit sort keys when I <= 65536 (rocPRIM then runs onesweep)
-    uint32_t* dup_of_pos = nullptr; uint32_t* dup_of_ex = nullptr;   // duplicate-negative correction rows (segment_kernel)
-    uint32_t* dup_count = nullptr;
+    DevBuf<uint32_t> item; DevBuf<uint64_t> val;                  // user-major example list
+    DevBuf<uint32_t> sorted_item; DevBuf<uint64_t> sorted_val;         // the same, stably sorted by item
+    DevBuf<uint32_t> seg;                                         // [2*I]: first | one-past-last sorted position per item
+    DevBuf<uint16_t> key16, sorted_key16;                             // 16-bit sort keys when I <= 65536 (rocPRIM then runs onesweep)
+    DevBuf<uint32_t> dup_of_pos, dup_of_ex;                          // duplicate-negative correction rows (segment_kernel)
+    DevBuf<uint32_t> dup_count;
     // counting sort (cdae_sort_kernels.hpp): per-item counts / prefix / (unused cursor), item-bucketed values, per-tile counts
-    uint32_t* item_count = nullptr; uint32_t* prefix = nullptr; uint32_t* rank = nullptr; uint64_t* bucketed = nullptr;
-    uint32_t* tile_hist = nullptr; uint32_t* block_total = nullptr;      // (`rank` holds the in-block item prefix)
-    uint32_t* wg_state = nullptr;                                    // bucket_sort_kernel: one word per item range (cleared by the sample kernel)
-    uint32_t* cells = nullptr; uint32_t* cell_flag = nullptr;        // ... and its cells [ranges][units][BKC_SLOTS], filled by sample_kernel; overflow word
+    DevBuf<uint32_t> item_count, prefix, rank; DevBuf<uint64_t> bucketed;
+    DevBuf<uint32_t> tile_hist, block_total;                             // (`rank` holds the in-block item prefix)
+    DevBuf<uint32_t> wg_state;                                       // bucket_sort_kernel: one word per item range (cleared by the sample kernel)
+    DevBuf<uint32_t> cells, cell_flag;                               // ... and its cells [ranges][units][BKC_SLOTS], filled by sample_kernel; overflow word
     uint32_t cell_tag = 0;                                           // (host) the tag of the batch last prepared into this set
-    cdae::RowRecord* pack = nullptr;                                 // row_pack_kernel: the batch's rows of the four-row decode role by this batch's length (nullptr: handle without the role)
+    DevBuf<cdae::RowRecord> pack;                                    // row_pack_kernel: the batch's rows of the four-row decode role by this batch's length (empty: handle without the role)
     hipEvent_t ready = nullptr, released = nullptr;
   } ex[3];
   static constexpr int NSETS = 3;
   hipStream_t prep2 = nullptr;          // second prep lane (batches with odd sequence number), or nullptr: one lane, look-ahead 1
   bool prep2_own = false;               // prep2 is a stream of its own (else it aliases `aux`)
   bool prep2_auto = false;              // use the second lane only for batches of at most PREP2_AUTO_MAX_USERS users
-  float* d_D0 = nullptr;                // decoder matrix at batch start (hidden-gradient gather)
+  DevBuf<float> d_D0;                   // decoder matrix at batch start (hidden-gradient gather)
   uint32_t dup_stripes = 1;             // counters the correction rows are numbered from (cdae_kernels.hpp DUP_STRIPES)
-  float* d_dup_corr = nullptr; uint32_t dup_cap = 0;   // [dup_cap][Kp] hidden-gradient corrections of duplicate negatives
-  float* d_HGpart = nullptr;            // [8][B][Kp] per-XCD partial hidden gradients
+  DevBuf<float> d_dup_corr; uint32_t dup_cap = 0;      // [dup_cap][Kp] hidden-gradient corrections of duplicate negatives
+  DevBuf<float> d_HGpart;               // [8][B][Kp] per-XCD partial hidden gradients
   // full-output decode (MFMA path): bf16 operand copies and the dense gradient, padded to 128-multiples
   uint32_t Bp = 0, Ip = 0;
-  __bf16 *d_Zb = nullptr, *d_ZTb = nullptr, *d_Db = nullptr, *d_DTb = nullptr, *d_Gb = nullptr, *d_GTb = nullptr;
-  float* d_dD = nullptr;
-  uint8_t* d_has_in = nullptr;          // [I]: item has a kept input in the block being stepped (set by full_positive_fixup_kernel, cleared by full_rows_inputs_kernel)
-  uint32_t* d_iota = nullptr;           // 0..B: identity unit prefix (fused full-output path: one hg partial row per user)
-  uint32_t* d_bits_train = nullptr;     // [NSETS][B x ceil(I/32)] rated-item bitmap of the batch (targets of the fused full-output decode), per example-buffer set
+  DevBuf<__bf16> d_Zb, d_ZTb, d_Db, d_DTb, d_Gb, d_GTb;
+  DevBuf<float> d_dD;
+  DevBuf<uint8_t> d_has_in;             // [I]: item has a kept input in the block being stepped (set by full_positive_fixup_kernel, cleared by full_rows_inputs_kernel)
+  DevBuf<uint32_t> d_iota;              // 0..B: identity unit prefix (fused full-output path: one hg partial row per user)
+  DevBuf<uint32_t> d_bits_train;        // [NSETS][B x ceil(I/32)] rated-item bitmap of the batch (targets of the fused full-output decode), per example-buffer set
   size_t bits_stride = 0;
   uint32_t full_slices = 1;
   // Full-output path, item spaces below 32768 (full_rows_kernel): the row step writes the bf16 images of every decoder row it
@@ -251,18 +239,19 @@ struct cdae_hip {
   hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_delta = nullptr;
   bool join_pending = false;            // full-output path: the aux stream's b recurrence of the last batch has not been joined yet
   hipStream_t prep = nullptr;           // sampling + sorting of the next batch
-  void* d_sort_tmp = nullptr; size_t sort_tmp_bytes = 0, sort_tmp_stride = 0;   // two workspaces, one per prep lane
-  float* d_Z = nullptr; float* d_Dz = nullptr; float* d_HG = nullptr; float* d_G = nullptr;
-  uint32_t* d_touched = nullptr;
-  double* d_scalar = nullptr;
-  uint32_t* d_uids = nullptr;
-  // Grow-only workspaces of the evaluation and serving entry points (DevBuf, listed in drop_dev_bufs): a steady-state call allocates nothing
+  DevBuf<char> d_sort_tmp; size_t sort_tmp_bytes = 0, sort_tmp_stride = 0;   // two workspaces, one per prep lane
+  DevBuf<float> d_Z, d_Dz, d_HG, d_G;
+  DevBuf<uint32_t> d_touched;
+  DevBuf<double> d_scalar;              // [8] reduction results; lives as long as the handle (cdae_hip_create)
+  DevBuf<unsigned long long> d_trace;   // CDAE_WAVE_TRACE (developer aid): owns hp.trace; lives as long as the handle
+  DevBuf<uint32_t> d_uids;
+  // Grow-only workspaces of the evaluation and serving entry points (grow-only: ensure()): a steady-state call allocates nothing
   DevBuf<uint32_t> d_rec;               // the lists of one chunk
   DevBuf<float> d_score;                // recommend, general path: score rows when num_items * 4 B exceed the LDS
   DevBuf<float> d_zeval, d_hpart_eval;  // evaluation workspace: [users][Kp] hidden rows, [units][Kp] encode partial sums
   DevBuf<uint32_t> d_bits;              // recommend: rated-item bitmap
   // TOPN metrics on the device (cdae_hip_set_test_rows / cdae_hip_eval_topn): the validation rows as CSR, per-user metric terms
-  int64_t* d_test_ptr = nullptr; uint32_t* d_test_col = nullptr; double* d_topn_pu = nullptr; double* d_topn_out = nullptr;
+  DevBuf<int64_t> d_test_ptr; DevBuf<uint32_t> d_test_col; DevBuf<double> d_topn_pu, d_topn_out;
   uint64_t test_users_with_rows = 0;
   bool topn_active = false;             // recommend paths: score every chunk's lists with topn_user_kernel (cdae_hip_eval_topn)
   // cdae_hip_recommend_rows / cdae_hip_eval_topn_rows: the caller's rated sets (CSR + user of every row), target sets and per-row metric
@@ -270,7 +259,7 @@ struct cdae_hip {
   DevBuf<int64_t> d_rows_ptr, d_rows_tptr;
   DevBuf<uint32_t> d_rows_uid, d_rows_col, d_rows_tcol;
   DevBuf<double> d_rows_pu;
-  double* d_rows_out = nullptr;         // [16]: the eight means, then the three hit counts
+  DevBuf<double> d_rows_out;            // [16]: the eight means, then the three hit counts
   // cdae_hip_score_rows: the candidate CSR, the tile table of the call, the scores and ranks of one chunk (grow-only, freed with the handle)
   DevBuf<int64_t> d_cand_ptr;
   DevBuf<uint32_t> d_cand_col, d_cand_rank;
@@ -298,7 +287,7 @@ struct cdae_hip {
   // WRMF handles (cdae_hip_create_als, cdae_als_kernels.hpp): the item-major CSR built once per data set (users ascending inside a
   // column; dropped with the interaction state), the Gram matrix [Kp x Kp] of the frozen table and its per-slice partials, and the
   // start vectors / solutions of one chunk of cdae_hip_als_solve_rows (its CSR shares d_rows_ptr / d_rows_col).  Grow-only.
-  int64_t* d_tptr = nullptr; uint32_t* d_tcol = nullptr;
+  DevBuf<int64_t> d_tptr; DevBuf<uint32_t> d_tcol;
   DevBuf<float> d_als_G, d_als_part, d_als_x, d_als_out;
   uint32_t als_steps = 0; float als_alpha = 0.f, als_lambda = 0.f;
   // Guest table (cdae_hip_set_guest_nodes, cdae_hip_fold_in_rows with install): a second user table, rows wu | wu_ag | uu | uu_ag of
@@ -331,9 +320,9 @@ struct cdae_hip {
   // bucket_sort_kernel (cdae_sort_kernels.hpp): the default item-major ordering — one narrow launch; item ranges cut at set_interactions
   bool bucket_sort = false;
   uint32_t bucket_ranges = 0;
-  uint32_t* d_bucket_cut = nullptr;     // [bucket_ranges + 1] item ids
+  DevBuf<uint32_t> d_bucket_cut;        // [bucket_ranges + 1] item ids
   bool bucket_attr_set = false;         // dynamic-LDS attribute set on this handle's device
-  uint16_t* d_range_of = nullptr;       // [I] item -> range (sample_kernel routes every example into its range's cell); nullptr: the sort scans the key list
+  DevBuf<uint16_t> d_range_of;          // [I] item -> range (sample_kernel routes every example into its range's cell); empty: the sort scans the key list
   uint32_t cell_units = 0;              // units the cells are allocated for (the most of any batch)
   bool counting_sort = false;           // tile counting sort on the prep stream (cdae_sort_kernels.hpp) instead of rocPRIM: num_items <= TILE_SORT_MAX_ITEMS
   bool tile_attr_set = false;           // dynamic LDS above 64 KiB allowed for the two tile kernels (per handle: the attribute is per device)
@@ -350,7 +339,7 @@ struct cdae_hip {
   int rows_fused_kh = 2;                // CDAE_FULL_ROWS_KH: workgroups per item tile of the fused row step (1 | 2)
 
   // data-parallel exchange
-  float* d_base = nullptr; float* d_delta = nullptr; float* d_recv = nullptr; float* d_snap = nullptr;   // agreed state, staged delta, all-reduced delta, parameters at the last stage
+  DevBuf<float> d_base, d_delta, d_recv, d_snap;   // agreed state, staged delta, all-reduced delta, parameters at the last stage
   void* xchg = nullptr; void (*xchg_free)(void*) = nullptr;   // communicator + schedule of the exchange (cdae_multi.hip)
   uint32_t delta_combine = CDAE_COMBINE_SUM;                  // cdae_hip_delta_set_combine: how staged deltas are folded in (cdae_exchange_algebra.h)
   // IMF / BPR handles (cdae_hip_create_mf, cdae_mf_kernels.hpp): 0 = CDAE, 1 = IMF, 2 = BPR; 3 = WRMF by ALS (cdae_hip_create_als):
@@ -372,13 +361,13 @@ struct cdae_hip {
   // id (get / set_param, recommend_all map through them).  Empty: identity (CDAE; IMF / BPR with one user per block = the reference order).
   std::vector<uint32_t> user_perm, user_inv;
   uint32_t ex_per_pos = 1;              // examples of the batch's item-sorted list per train interaction (CDAE: 1 + num_neg)
-  float* d_ub = nullptr; float* d_ub_ag = nullptr;   // [U] user bias and its accumulator
-  float* d_UVpre = nullptr;             // [instances of a batch][Kp]: user vector before each instance's step (phase I input)
+  DevBuf<float> d_ub, d_ub_ag;   // [U] user bias and its accumulator
+  DevBuf<float> d_UVpre;                // [instances of a batch][Kp]: user vector before each instance's step (phase I input)
   // item-sharded layout (cdae_multi.hip): this handle holds item rows [item0, item0 + I) of I_global; every user,
   // possibly with no local item.  The two per-user sums that cross shards live in d_Hsum (input sums) and d_HG (hidden gradient).
   bool item_shard = false; uint64_t item0 = 0, I_global = 0;
-  uint32_t* d_gpos = nullptr;           // item shard: per user (length of the whole row, position of the first local item): the dropout stream's index space
-  float* d_Hsum = nullptr; uint32_t* d_iota_eval = nullptr;
+  DevBuf<uint32_t> d_gpos;              // item shard: per user (length of the whole row, position of the first local item): the dropout stream's index space
+  DevBuf<float> d_Hsum;
   DevBuf<float> d_hsum_eval;            // item shard, evaluation: [users][SHARD_BLOCKS x Kp] input-sum all-reduce buffer of a chunk
   DevBuf<float> d_rec_score;            // the scores of d_rec's lists (item-sharded top-k merge, the rows entry points' out_scores)
   uint64_t fs_prepped = 0;              // item-sharded training: batches whose example lists have been prepared (buffer set = parity)
@@ -391,7 +380,7 @@ struct cdae_hip {
   const int64_t* g_row_ptr_src = nullptr; const uint32_t* g_col_src = nullptr;   // (set_item_shard_global -> the next set_interactions)
   std::vector<int64_t> h_grow_ptr;
   std::vector<uint32_t> h_gunit_ptr;
-  int64_t* d_grow_ptr = nullptr; uint32_t* d_gcol = nullptr; uint32_t* d_gunit_ptr = nullptr; uint32_t* d_gunit_user = nullptr;
+  DevBuf<int64_t> d_grow_ptr; DevBuf<uint32_t> d_gcol, d_gunit_ptr, d_gunit_user;
   bool shard_sampled() const { return item_shard && !cfg.full_output; }
 
   bool skip_ready_wait = false;         // compute_batch: enqueue_users has seen the set's `ready` event complete on the host (no wait packet on the main stream)
@@ -538,46 +527,40 @@ int collect_profile(cdae_hip* h, cdae_hip_stats* st) {
   return 0;
 }
 
-// Every device allocation of a handle that set_interactions (or a later entry point) makes, visited as void**: f(slot) != 0 stops the
-// visit and is returned.  A new buffer is added HERE only.  (d_scalar is not in the list: cdae_hip_create allocates it and it lives
-// as long as the handle.)
-template <class F, class... P> int visit_slots(F& f, P*&... p) {
-  int rc = 0;
-  ((rc = rc ? rc : f((void**)&p)), ...);
-  return rc;
-}
-template <class F> int visit_device_ptrs(cdae_hip* h, F f) {
+// Every device buffer that a data set owns, listed ONCE: f(buffers...) is called for the three example-buffer sets and then for the
+// handle's own.  A new buffer is added HERE only.  Not in the list: d_scalar and d_trace, which cdae_hip_create allocates and which
+// live as long as the handle — their destructors free them.
+template <class F> void visit_data_set_bufs(cdae_hip* h, F&& f) {
   for (auto& b : h->ex)
-    CHK(visit_slots(f, b.item, b.val, b.sorted_item, b.sorted_val, b.seg, b.dup_of_pos, b.dup_of_ex, b.dup_count, b.key16, b.sorted_key16,
-                    b.item_count, b.prefix, b.rank, b.bucketed, b.tile_hist, b.block_total, b.wg_state, b.cells, b.cell_flag, b.pack));
-  return visit_slots(f, h->d_row_ptr, h->d_col, h->d_item_order, h->d_shared, h->d_Wu, h->d_Wu_ag, h->d_D0, h->d_HGpart, h->d_sort_tmp,
-                     h->d_unit_ptr, h->d_Hpart, h->d_uptr_tmp, h->d_Zb, h->d_ZTb, h->d_Db, h->d_DTb, h->d_Gb, h->d_GTb, h->d_dD, h->d_has_in,
-                     h->d_Z, h->d_Dz, h->d_HG, h->d_G, h->d_touched, h->d_uids, h->d_base, h->d_delta, h->d_recv, h->d_snap,
-                     h->d_dup_corr, h->d_unit_user, h->d_iota, h->d_bits_train,
-                     h->d_Uu, h->d_Uu_ag, h->d_Ssum, h->d_delta_rows, h->d_Hsum, h->d_iota_eval,
-                     h->d_gpos, h->d_ub, h->d_ub_ag, h->d_UVpre, h->d_rank_of, h->d_grow_ptr, h->d_gcol, h->d_gunit_ptr, h->d_gunit_user,
-                     h->d_test_ptr, h->d_test_col, h->d_topn_pu, h->d_topn_out, h->d_bucket_cut, h->d_range_of,
-                     h->d_Ghot, h->d_hotdup, h->d_late_bits, h->d_cold_map, h->d_rows_out, h->d_tptr, h->d_tcol);
+    f(b.item, b.val, b.sorted_item, b.sorted_val, b.seg, b.dup_of_pos, b.dup_of_ex, b.dup_count, b.key16, b.sorted_key16,
+      b.item_count, b.prefix, b.rank, b.bucketed, b.tile_hist, b.block_total, b.wg_state, b.cells, b.cell_flag, b.pack);
+  f(h->d_row_ptr, h->d_col, h->d_item_order, h->d_shared, h->d_Wu, h->d_Wu_ag, h->d_D0, h->d_HGpart, h->d_sort_tmp,
+    h->d_unit_ptr, h->d_Hpart, h->d_uptr_tmp, h->d_Zb, h->d_ZTb, h->d_Db, h->d_DTb, h->d_Gb, h->d_GTb, h->d_dD, h->d_has_in,
+    h->d_Z, h->d_Dz, h->d_HG, h->d_G, h->d_touched, h->d_uids, h->d_base, h->d_delta, h->d_recv, h->d_snap,
+    h->d_dup_corr, h->d_unit_user, h->d_iota, h->d_bits_train,
+    h->d_Uu, h->d_Uu_ag, h->d_Ssum, h->d_delta_rows, h->d_Hsum,
+    h->d_gpos, h->d_ub, h->d_ub_ag, h->d_UVpre, h->d_rank_of, h->d_grow_ptr, h->d_gcol, h->d_gunit_ptr, h->d_gunit_user,
+    h->d_test_ptr, h->d_test_col, h->d_topn_pu, h->d_topn_out, h->d_bucket_cut, h->d_range_of,
+    h->d_Ghot, h->d_hotdup, h->d_late_bits, h->d_cold_map, h->d_rows_out, h->d_tptr, h->d_tcol,
+    // the grow-only workspaces of the evaluation and serving entry points
+    h->d_rec, h->d_rec_score, h->d_score, h->d_bits, h->d_zeval, h->d_hpart_eval, h->d_hsum_eval,
+    h->d_rows_ptr, h->d_rows_uid, h->d_rows_col, h->d_rows_tptr, h->d_rows_pu, h->d_rows_tcol,
+    h->d_cand_ptr, h->d_cand_col, h->d_cand_tiles, h->d_cand_score, h->d_cand_rank,
+    h->d_fr_tptr, h->d_fr_tcol, h->d_fr_tbits, h->d_fr_vrows, h->d_fr_tscore, h->d_fr_rank,
+    h->d_flt_eptr, h->d_flt_ecol, h->d_flt_allow, h->d_flt_pos, h->d_flt_D, h->d_flt_bp,
+    h->d_sim_q, h->d_sim_iota, h->d_sim_T, h->d_sim_zero,
+    h->d_guest[0], h->d_guest[1], h->d_guest[2], h->d_guest[3], h->d_fold[0], h->d_fold[1], h->d_fold[2], h->d_fold[3],
+    h->d_fold_long, h->d_als_G, h->d_als_part, h->d_als_x, h->d_als_out);
 }
-// ... and every grow-only workspace (DevBuf), freed with its capacity.  A new one is added HERE only.  A hipFree error is returned after all have been dropped.
-int drop_dev_bufs(cdae_hip* h) {
+// Drops every one of them; the first release error is returned after all have been dropped.
+int drop_data_set_bufs(cdae_hip* h) {
   int rc = 0;
-  auto drop = [&](auto&... b) { ((rc = b.drop() || rc), ...); };
-  drop(h->d_rec, h->d_rec_score, h->d_score, h->d_bits, h->d_zeval, h->d_hpart_eval, h->d_hsum_eval,
-       h->d_rows_ptr, h->d_rows_uid, h->d_rows_col, h->d_rows_tptr, h->d_rows_pu, h->d_rows_tcol,
-       h->d_cand_ptr, h->d_cand_col, h->d_cand_tiles, h->d_cand_score, h->d_cand_rank,
-       h->d_fr_tptr, h->d_fr_tcol, h->d_fr_tbits, h->d_fr_vrows, h->d_fr_tscore, h->d_fr_rank,
-       h->d_flt_eptr, h->d_flt_ecol, h->d_flt_allow, h->d_flt_pos, h->d_flt_D, h->d_flt_bp,
-       h->d_sim_q, h->d_sim_iota, h->d_sim_T, h->d_sim_zero,
-       h->d_guest[0], h->d_guest[1], h->d_guest[2], h->d_guest[3], h->d_fold[0], h->d_fold[1], h->d_fold[2], h->d_fold[3],
-       h->d_fold_long, h->d_als_G, h->d_als_part, h->d_als_x, h->d_als_out);
+  visit_data_set_bufs(h, [&](auto&... b) { ((rc = b.drop() || rc), ...); });
   return rc;
 }
 
 void free_all(cdae_hip* h) {
-  (void)visit_device_ptrs(h, [](void** p) { if (*p) (void)hipFree(*p); *p = nullptr; return 0; });   // (errors ignored: the handle goes away)
-  (void)drop_dev_bufs(h);
-  if (h->d_scalar) (void)hipFree(h->d_scalar);
+  (void)drop_data_set_bufs(h);        // (errors ignored: the handle goes away; before the streams and events do)
   for (auto& b : h->ex) {
     if (b.ready) (void)hipEventDestroy(b.ready);
     if (b.released) (void)hipEventDestroy(b.released);
@@ -606,11 +589,7 @@ int quiesce(cdae_hip* h) {
 }
 
 int free_interaction_state(cdae_hip* h) {
-  CHK(visit_device_ptrs(h, [](void** p) {
-    if (*p) { HIPCHK(hipFree(*p)); *p = nullptr; }
-    return 0;
-  }));
-  CHK(drop_dev_bufs(h));
+  CHK(drop_data_set_bufs(h));
   h->db_valid = false; h->db_rows_valid = false; h->zb_rows = 0xFFFFFFFFu;
   h->n_guests = 0;
   return 0;
@@ -629,7 +608,7 @@ inline uint32_t decode_hot_rows(const cdae_hip* h) { return std::min<uint32_t>(h
 // its rows in popularity order (pack == nullptr): its step is paced by the exchange, not by this launch.
 inline bool packs_rows(const cdae_hip* h) { return h->row_pack && h->K <= 256 && !h->mf && !h->cfg.full_output && !h->item_shard; }
 // ... and the batches of such a handle that have one: every batch prep_batch ordered (an explicit input set is ordered by its caller)
-inline cdae::RowRecord* pack_of(const cdae_hip* h, const cdae_hip::ExBuf& x, uint64_t E) { return packs_rows(h) && E > 0 ? x.pack : nullptr; }
+inline cdae::RowRecord* pack_of(const cdae_hip* h, const cdae_hip::ExBuf& x, uint64_t E) { return packs_rows(h) && E > 0 ? x.pack.p : nullptr; }
 
 // K1 + sort on the prep stream into example-buffer set `b`
 // lane 1: the second prep stream with the second half of the sort workspace (two batches are prepared side by side)
@@ -660,14 +639,14 @@ int prep_batch(cdae_hip* h, int b, const Batch& bt, uint64_t seed, uint32_t epoc
                        h->d_gunit_ptr + bt.s0, n_units, bt.s0, bt.nb, bt.cidx, seed, epoch, x.item, x.val, x.key16,
                        x.seg, h->counting_sort || bucket ? 0u : 4u * I, x.dup_count, x.dup_of_ex, h->d_gunit_user,
                        x.wg_state, (const uint32_t*)nullptr, (uint32_t)h->item0, I, (uint32_t)h->I_global,
-                       (const uint16_t*)(use_cells ? h->d_range_of : nullptr), (const uint32_t*)h->d_bucket_cut, h->bucket_ranges,
+                       (const uint16_t*)(use_cells ? h->d_range_of.p : nullptr), (const uint32_t*)h->d_bucket_cut, h->bucket_ranges,
                        use_cells ? x.cells : (uint32_t*)nullptr, x.cell_flag, x.cell_tag);
   } else
   hipLaunchKernelGGL(sample_kernel, dim3((n_units + 3) / 4), dim3(256), 0, st, h->hp, h->d_row_ptr, h->d_col,
                      h->d_unit_ptr + bt.s0, n_units, bt.s0, bt.nb, bt.cidx, seed, epoch, x.item, x.val, x.key16,
                      x.seg, h->counting_sort || bucket ? 0u : 4u * I, x.dup_count, x.dup_of_ex, h->d_unit_user,
                      x.wg_state, (const uint32_t*)h->d_gpos, 0u, 0u, 0u,
-                     (const uint16_t*)(use_cells ? h->d_range_of : nullptr), (const uint32_t*)h->d_bucket_cut, h->bucket_ranges,
+                     (const uint16_t*)(use_cells ? h->d_range_of.p : nullptr), (const uint32_t*)h->d_bucket_cut, h->bucket_ranges,
                      use_cells ? x.cells : (uint32_t*)nullptr, x.cell_flag, x.cell_tag);
   CHK(pr.end());
   CHK(pr.begin(h, F_SORT, st, prof_q));
@@ -683,7 +662,7 @@ int prep_batch(cdae_hip* h, int b, const Batch& bt, uint64_t seed, uint32_t epoc
       h->bucket_attr_set = true;
     }
     hipLaunchKernelGGL(bucket_sort_kernel, dim3(h->bucket_ranges), dim3(BK_THREADS), BK_LDS_BYTES, st, (const uint16_t*)x.key16, (const uint64_t*)x.val,
-                       (uint32_t)bt.E, (const uint32_t*)h->d_bucket_cut, x.wg_state, (const uint32_t*)(use_cells ? x.cells : nullptr), n_units,
+                       (uint32_t)bt.E, (const uint32_t*)h->d_bucket_cut, x.wg_state, (const uint32_t*)(use_cells ? x.cells.p : nullptr), n_units,
                        (const uint32_t*)x.cell_flag, x.cell_tag, x.seg, x.seg + I, (const uint32_t*)h->d_rank_of,
                        x.seg + 2 * (size_t)I, x.seg + 3 * (size_t)I, x.sorted_val, x.bucketed, x.dup_count, h->dup_cap, x.dup_of_pos, x.dup_of_ex,
                        h->dup_stripes, h->d_fused_err);
@@ -705,13 +684,13 @@ int prep_batch(cdae_hip* h, int b, const Batch& bt, uint64_t seed, uint32_t epoc
                        x.sorted_val, x.item_count, x.dup_count, h->dup_cap, x.dup_of_pos, x.dup_of_ex, h->dup_stripes);
   } else if (x.key16) {
     // 16-bit keys: rocPRIM picks onesweep (2 digit passes) instead of block sort + log2(tiles) merge passes
-    HIPCHK(rocprim::radix_sort_pairs(sort_tmp, h->sort_tmp_bytes, x.key16, x.sorted_key16, x.val, x.sorted_val,
+    HIPCHK(rocprim::radix_sort_pairs(sort_tmp, h->sort_tmp_bytes, x.key16.p, x.sorted_key16.p, x.val.p, x.sorted_val.p,
                                      (size_t)bt.E, 0u, (unsigned)h->sort_bits, st));
     hipLaunchKernelGGL(segment_kernel<uint16_t>, seg_grid, dim3(256), 0, st, x.sorted_key16, x.sorted_val, (uint32_t)bt.E,
                        x.seg, x.seg + I, x.dup_count, h->dup_cap, x.dup_of_pos, x.dup_of_ex, h->dup_stripes,
                        (const uint32_t*)h->d_rank_of, x.seg + 2 * (size_t)I, x.seg + 3 * (size_t)I, shs ? I : 0xFFFFFFFFu);
   } else {
-    HIPCHK(rocprim::radix_sort_pairs(sort_tmp, h->sort_tmp_bytes, x.item, x.sorted_item, x.val, x.sorted_val,
+    HIPCHK(rocprim::radix_sort_pairs(sort_tmp, h->sort_tmp_bytes, x.item.p, x.sorted_item.p, x.val.p, x.sorted_val.p,
                                      (size_t)bt.E, 0u, (unsigned)h->sort_bits, st));
     hipLaunchKernelGGL(segment_kernel<uint32_t>, seg_grid, dim3(256), 0, st, x.sorted_item, x.sorted_val, (uint32_t)bt.E,
                        x.seg, x.seg + I, x.dup_count, h->dup_cap, x.dup_of_pos, x.dup_of_ex, h->dup_stripes,
@@ -793,8 +772,7 @@ int fused_geometry(cdae_hip* h, uint32_t hot, uint32_t I, bool packed) {
     const uint32_t cu = cu0 + i / 4, w = i % 4;
     for (size_t k = 0; k < bin[i].size(); ++k) map[((size_t)k * S + cu) * 4 + w] = bin[i][k];
   }
-  if (h->d_cold_map) { HIPCHK(hipFree(h->d_cold_map)); h->d_cold_map = nullptr; }
-  CHK(dev_alloc(&h->d_cold_map, map.size()));
+  CHK(h->d_cold_map.alloc(map.size()));
   HIPCHK(hipMemcpy(h->d_cold_map, map.data(), map.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
   g.cold_map = h->d_cold_map;
   h->fused_geo = g;
@@ -924,8 +902,8 @@ int compute_batch(cdae_hip* h, int b, const Batch& bt, uint64_t seed, uint32_t e
   // The fused launch (decode + gather, decode_gather_kernel): plain batches of a handle that has late rows.  The batch's encode then
   // fills G with G_PENDING (the gather wavefronts wait on it), whichever encode form runs.
   const bool fused = h->fused_decode && !explicit_in && n_units > 0u && bt.E > 0u && bt.E < (1ull << 32);
-  float* const ghot = h->late_rows ? h->d_Ghot : nullptr;
-  uint32_t* const gfill = fused ? reinterpret_cast<uint32_t*>(h->d_G) : nullptr;
+  float* const ghot = h->late_rows ? h->d_Ghot.p : nullptr;
+  uint32_t* const gfill = fused ? reinterpret_cast<uint32_t*>(h->d_G.p) : nullptr;
   const uint32_t n_fill = fused ? (uint32_t)bt.E : 0u;
   if (!explicit_in && !h->encode_two_launches && nb <= ENCODE_USERS_MAX) {
     // one launch: a workgroup per user (encode_users_kernel)
@@ -1145,7 +1123,7 @@ int full_tail(cdae_hip* h, cdae_hip::ExBuf& x, uint64_t s0, uint32_t nb, const F
   const uint32_t I = (uint32_t)h->I, Kp = h->Kp, Bp = h->Bp, Ip = h->Ip;
   const dim3 blk(256);
   const bool rows_fused = rows_fused_path(h);                             // GEMM 3 + row step in one launch (Kp = 512, >= 32768 items)
-  __bf16* const img = a.write_images ? h->d_Db : nullptr;
+  __bf16* const img = a.write_images ? h->d_Db.p : nullptr;
   Prof pr;
   HIPCHK(hipEventRecord(h->ev_fork, st));
   HIPCHK(hipStreamWaitEvent(h->aux, h->ev_fork, 0));
@@ -1223,8 +1201,8 @@ int compute_batch_full(cdae_hip* h, int b, const Batch& bt, uint64_t seed, uint3
   const bool pair_copy = Ip <= 65536 && need_d && !z_in_encode;
   if (need_d && !pair_copy) hipLaunchKernelGGL(to_bf16_transpose_kernel, dim3(Kp / 64, Ip / 64), blk, 0, st, h->dec(), I, Kp, Kp, Ip, h->d_Db, h->d_DTb);
   CHK(join_aux(h));
-  __bf16* zb = z_in_encode ? h->d_Zb : nullptr;
-  __bf16* ztb = z_in_encode ? h->d_ZTb : nullptr;
+  __bf16* zb = z_in_encode ? h->d_Zb.p : nullptr;
+  __bf16* ztb = z_in_encode ? h->d_ZTb.p : nullptr;
   if (two_launches) {
     DISPATCH_NI(h->NI, encode_finish_kernel, grid_users, blk, 0, st, h->hp, h->d_Hpart, uptr, h->d_Wu, h->P(CDAE_P_B),
                 (const uint32_t*)nullptr, s0, nb, 1, h->d_Z, h->d_Dz, h->d_HG, h->d_Uu, h->d_Ssum, zb, ztb, Bp);
@@ -1440,8 +1418,7 @@ int cdae_hip_create(const cdae_hip_config* cfg, int device_id, cdae_hip_t** out)
   if (e == hipSuccess) e = hipEventCreateWithFlags(&h->ev_join, sync_event_flags());
   if (e == hipSuccess) e = hipEventCreateWithFlags(&h->ev_delta, sync_event_flags());
   if (e != hipSuccess) { free_all(h); delete h; return fail("stream/event setup failed: %s", hipGetErrorString(e)); }
-  e = hipMalloc((void**)&h->d_scalar, 8 * sizeof(double));
-  if (e != hipSuccess) { free_all(h); delete h; return fail("hipMalloc failed: %s", hipGetErrorString(e)); }
+  if (int rc = h->d_scalar.alloc(8)) { free_all(h); delete h; return rc; }
   cdae::HyperParams& hp = h->hp;
   hp.lambda = (float)cfg->lambda; hp.lr = (float)cfg->learn_rate; hp.beta = (float)cfg->beta;
   hp.scale = cfg->scaled ? (float)(1.0 / (1.0 - cfg->corruption_ratio)) : 1.f;     // cdae.hpp:202-205
@@ -1453,7 +1430,8 @@ int cdae_hip_create(const cdae_hip_config* cfg, int device_id, cdae_hip_t** out)
   hp.uid_offset = 0; hp.num_items = 0; hp.K = h->K; hp.Kp = h->Kp;
   hp.own_u0 = 0; hp.own_u1 = ~0ull;
   if (DEV_ENV("CDAE_WAVE_TRACE")) {      // developer aid (tools/wave_trace.py): the last training batch's wavefront timeline
-    if (hipMalloc((void**)&hp.trace, 4 * cdae::TRACE_CAP * sizeof(unsigned long long)) != hipSuccess) hp.trace = nullptr;
+    (void)h->d_trace.alloc(4 * cdae::TRACE_CAP);      // (no trace where this fails)
+    hp.trace = h->d_trace;
     if (hp.trace) (void)hipMemset(hp.trace, 0, 4 * cdae::TRACE_CAP * sizeof(unsigned long long));
   }
   hp.debug_skip = DEV_ENV("CDAE_DEBUG_SKIP_ROLES") ? (uint32_t)std::strtoul(DEV_ENV("CDAE_DEBUG_SKIP_ROLES"), nullptr, 10) : 0u;
@@ -1471,8 +1449,6 @@ int cdae_hip_destroy(cdae_hip_t* h) {
     std::vector<unsigned long long> rec(4 * cdae::TRACE_CAP);
     (void)hipMemcpy(rec.data(), h->hp.trace, rec.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost);
     if (FILE* f = std::fopen(DEV_ENV("CDAE_WAVE_TRACE"), "wb")) { std::fwrite(rec.data(), sizeof(unsigned long long), rec.size(), f); std::fclose(f); }
-    (void)hipFree(h->hp.trace);
-    h->hp.trace = nullptr;
   }
   if (h->xchg && h->xchg_free) { h->xchg_free(h->xchg); h->xchg = nullptr; }
   free_all(h);
@@ -1663,16 +1639,16 @@ int upload_data_set(cdae_hip* h, const cdae::plan::Plan& p, const int64_t* grp, 
   const uint64_t U = h->U, I = h->I;
   const uint32_t B = p.B;
   const size_t nnz = (size_t)p.row_ptr[U], IK = (size_t)I * h->Kp;
-  CHK(dev_alloc(&h->d_row_ptr, U + 1));
-  CHK(dev_alloc(&h->d_col, nnz));
+  CHK(h->d_row_ptr.alloc(U + 1));
+  CHK(h->d_col.alloc(nnz));
   HIPCHK(hipMemcpy(h->d_row_ptr, p.row_ptr, (U + 1) * sizeof(int64_t), hipMemcpyHostToDevice));
   HIPCHK(hipMemcpy(h->d_col, p.col, nnz * sizeof(uint32_t), hipMemcpyHostToDevice));
-  CHK(dev_upload(&h->d_item_order, p.order.data(), (size_t)I));
-  CHK(dev_upload(&h->d_rank_of, p.rank_of.data(), (size_t)I));
+  CHK(dev_upload(h->d_item_order, p.order.data(), (size_t)I));
+  CHK(dev_upload(h->d_rank_of, p.rank_of.data(), (size_t)I));
   if (h->late_rows) {
-    CHK(dev_upload(&h->d_late_bits, p.split.late_bits.data(), (size_t)h->late_words));
+    CHK(dev_upload(h->d_late_bits, p.split.late_bits.data(), (size_t)h->late_words));
     const size_t nB = (size_t)std::max<uint64_t>(std::min<uint64_t>(h->B, U), 1) * cdae::LATE_MAX;
-    CHK(dev_alloc(&h->d_Ghot, nB)); CHK(dev_alloc(&h->d_hotdup, nB));
+    CHK(h->d_Ghot.alloc(nB)); CHK(h->d_hotdup.alloc(nB));
     HIPCHK(hipMemset(h->d_Ghot, 0, nB * sizeof(float)));
     HIPCHK(hipMemset(h->d_hotdup, 0xFF, nB * sizeof(uint32_t)));
   }
@@ -1691,72 +1667,72 @@ int upload_data_set(cdae_hip* h, const cdae::plan::Plan& p, const int64_t* grp, 
   h->fused_decode = h->fused_possible && h->allow_fused;
 
   // parameters
-  CHK(dev_alloc(&h->d_shared, h->n_shared));
+  CHK(h->d_shared.alloc(h->n_shared));
   HIPCHK(hipMemset(h->d_shared, 0, h->n_shared * sizeof(float)));
   const size_t WR = (size_t)h->wu_rows();                   // private rows held here: every user, or an item shard's own user range
   h->cnt[CDAE_P_WU] = h->cnt[CDAE_P_WU_AG] = WR * h->Kp;
-  CHK(dev_alloc(&h->d_Wu, WR * h->Kp));
-  CHK(dev_alloc(&h->d_Wu_ag, WR * h->Kp));
+  CHK(h->d_Wu.alloc(WR * h->Kp));
+  CHK(h->d_Wu_ag.alloc(WR * h->Kp));
   HIPCHK(hipMemset(h->d_Wu, 0, std::max<size_t>(WR * h->Kp, 1) * sizeof(float)));
   HIPCHK(hipMemset(h->d_Wu_ag, 0, std::max<size_t>(WR * h->Kp, 1) * sizeof(float)));
   if (h->cfg.linear_function) {
     h->cnt[CDAE_P_UU] = h->cnt[CDAE_P_UU_AG] = WR * h->Kp;
-    CHK(dev_alloc(&h->d_Uu, WR * h->Kp));
-    CHK(dev_alloc(&h->d_Uu_ag, WR * h->Kp));
+    CHK(h->d_Uu.alloc(WR * h->Kp));
+    CHK(h->d_Uu_ag.alloc(WR * h->Kp));
   }
 
   const bool als = h->mf == 3u;      // WRMF: no example lists, no batch workspace — the item-major CSR of its item half-step instead
   if (!als) {
     if (h->shard_sampled()) {
       const size_t gnnz = (size_t)grp[U];
-      CHK(dev_alloc(&h->d_grow_ptr, U + 1)); CHK(dev_alloc(&h->d_gcol, gnnz));
+      CHK(h->d_grow_ptr.alloc(U + 1)); CHK(h->d_gcol.alloc(gnnz));
       HIPCHK(hipMemcpy(h->d_grow_ptr, grp, (U + 1) * sizeof(int64_t), hipMemcpyHostToDevice));
       HIPCHK(hipMemcpy(h->d_gcol, gcl, gnnz * sizeof(uint32_t), hipMemcpyHostToDevice));
-      CHK(dev_upload(&h->d_gunit_ptr, h->h_gunit_ptr.data(), (size_t)U + 1));
-      CHK(dev_upload(&h->d_gunit_user, p.gunit_user.data(), p.gunit_user.size()));
+      CHK(dev_upload(h->d_gunit_ptr, h->h_gunit_ptr.data(), (size_t)U + 1));
+      CHK(dev_upload(h->d_gunit_user, p.gunit_user.data(), p.gunit_user.size()));
     }
     if (h->bucket_sort) {
-      CHK(dev_upload(&h->d_bucket_cut, p.bucket.cut.data(), p.bucket.cut.size()));
-      if (!p.bucket.range_of.empty()) CHK(dev_upload(&h->d_range_of, p.bucket.range_of.data(), (size_t)I));
+      CHK(dev_upload(h->d_bucket_cut, p.bucket.cut.data(), p.bucket.cut.size()));
+      if (!p.bucket.range_of.empty()) CHK(dev_upload(h->d_range_of, p.bucket.range_of.data(), (size_t)I));
     }
-    CHK(dev_upload(&h->d_unit_ptr, h->h_unit_ptr.data(), (size_t)U + 1));
-    CHK(dev_upload(&h->d_unit_user, p.unit_user.data(), p.unit_user.size()));
-    CHK(dev_alloc(&h->d_Hpart, (size_t)h->unit_cap * h->Kp));
-    CHK(dev_alloc(&h->d_uptr_tmp, (size_t)B + 1));
+    CHK(dev_upload(h->d_unit_ptr, h->h_unit_ptr.data(), (size_t)U + 1));
+    CHK(dev_upload(h->d_unit_user, p.unit_user.data(), p.unit_user.size()));
+    CHK(h->d_Hpart.alloc((size_t)h->unit_cap * h->Kp));
+    CHK(h->d_uptr_tmp.alloc((size_t)B + 1));
     {
       const uint32_t one_unit[2] = {0u, 1u};          // explicit-input step: one user, one unit
       HIPCHK(hipMemcpy(h->d_uptr_tmp, one_unit, sizeof one_unit, hipMemcpyHostToDevice));
     }
     for (auto& b : h->ex) {
-      CHK(dev_alloc(&b.item, h->Ecap)); CHK(dev_alloc(&b.val, h->Ecap));
-      CHK(dev_alloc(&b.sorted_item, h->Ecap)); CHK(dev_alloc(&b.sorted_val, h->Ecap));
-      CHK(dev_alloc(&b.seg, 4 * (size_t)I));                   // first | one-past-last position by item, then the same by popularity rank
-      CHK(dev_alloc(&b.dup_of_pos, h->Ecap)); CHK(dev_alloc(&b.dup_of_ex, h->Ecap)); CHK(dev_alloc(&b.dup_count, cdae::DUP_STRIPES));
-      if (packs_rows(h)) CHK(dev_alloc(&b.pack, ((size_t)I + 3) & ~(size_t)3));   // whole wavefronts of the rows [hot_rows, I)
+      CHK(b.item.alloc(h->Ecap)); CHK(b.val.alloc(h->Ecap));
+      CHK(b.sorted_item.alloc(h->Ecap)); CHK(b.sorted_val.alloc(h->Ecap));
+      CHK(b.seg.alloc(4 * (size_t)I));                   // first | one-past-last position by item, then the same by popularity rank
+      CHK(b.dup_of_pos.alloc(h->Ecap)); CHK(b.dup_of_ex.alloc(h->Ecap)); CHK(b.dup_count.alloc(cdae::DUP_STRIPES));
+      if (packs_rows(h)) CHK(b.pack.alloc(((size_t)I + 3) & ~(size_t)3));   // whole wavefronts of the rows [hot_rows, I)
       if (h->counting_sort) {
-        CHK(dev_alloc(&b.item_count, (size_t)I)); CHK(dev_alloc(&b.prefix, (size_t)I + 1));
-        CHK(dev_alloc(&b.rank, (size_t)I)); CHK(dev_alloc(&b.bucketed, h->Ecap));
-        CHK(dev_alloc(&b.tile_hist, (size_t)((h->Ecap + cdae::TILE_EX - 1) / cdae::TILE_EX + 1) * I));
-        CHK(dev_alloc(&b.block_total, 128));
-      } else if (I + (h->shard_sampled() ? 1u : 0u) <= 65536) { CHK(dev_alloc(&b.key16, h->Ecap + 8)); CHK(dev_alloc(&b.sorted_key16, h->Ecap)); }   // (a sampled item shard sorts one more key: VOID = I)
-      if (h->bucket_sort) { CHK(dev_alloc(&b.bucketed, h->Ecap)); }
+        CHK(b.item_count.alloc((size_t)I)); CHK(b.prefix.alloc((size_t)I + 1));
+        CHK(b.rank.alloc((size_t)I)); CHK(b.bucketed.alloc(h->Ecap));
+        CHK(b.tile_hist.alloc((size_t)((h->Ecap + cdae::TILE_EX - 1) / cdae::TILE_EX + 1) * I));
+        CHK(b.block_total.alloc(128));
+      } else if (I + (h->shard_sampled() ? 1u : 0u) <= 65536) { CHK(b.key16.alloc(h->Ecap + 8)); CHK(b.sorted_key16.alloc(h->Ecap)); }   // (a sampled item shard sorts one more key: VOID = I)
+      if (h->bucket_sort) { CHK(b.bucketed.alloc(h->Ecap)); }
       b.cell_tag = 0;
       if (h->bucket_sort && h->d_range_of) {
         // [ranges][units of the largest batch][BKC_SLOTS] words; beyond 256 MiB per set (or 16 384 units) the sort scans instead
         const size_t words = (size_t)h->bucket_ranges * h->unit_cap * cdae::BKC_SLOTS;
         if (h->unit_cap <= cdae::BK_CELL_UNITS_MAX && words * sizeof(uint32_t) <= (256ull << 20)) {
-          CHK(dev_alloc(&b.cells, words));
-          CHK(dev_alloc(&b.cell_flag, 1));
+          CHK(b.cells.alloc(words));
+          CHK(b.cell_flag.alloc(1));
           HIPCHK(hipMemset(b.cell_flag, 0, sizeof(uint32_t)));
           h->cell_units = h->unit_cap;
         }
       }
-      CHK(dev_alloc(&b.wg_state, cdae::BK_MAX_RANGES));
+      CHK(b.wg_state.alloc(cdae::BK_MAX_RANGES));
       HIPCHK(hipMemset(b.wg_state, 0, cdae::BK_MAX_RANGES * sizeof(uint32_t)));
       if (!b.ready) { HIPCHK(hipEventCreateWithFlags(&b.ready, sync_event_flags())); HIPCHK(hipEventCreateWithFlags(&b.released, sync_event_flags())); }
       HIPCHK(hipEventRecord(b.released, h->stream));
     }
-    CHK(dev_alloc(&h->d_D0, IK));
+    CHK(h->d_D0.alloc(IK));
     {
       // one correction row per duplicate negative of a batch (~2 % of the examples at ML-10M shape); beyond the
       // capacity decode falls back to atomics.  Zero-filled once: decode's 16-lane path leaves elements >= 64 NV + 16 NT
@@ -1770,50 +1746,50 @@ int upload_data_set(cdae_hip* h, const cdae::plan::Plan& p, const int64_t* grp, 
       // 16 stripes of 4096 rows with 65 536 rows allocated, and the atomics fallback made training differ from run to run.
       if (h->bucket_sort && h->bucket_ranges <= 32u) h->dup_stripes = 1u;
       if ((uint64_t)h->dup_cap * h->Kp * 4u >= (1ull << 31)) h->fused_possible = h->fused_decode = false;     // (32-bit buffer offsets in the fused launch)
-      CHK(dev_alloc(&h->d_dup_corr, (size_t)h->dup_cap * h->Kp));
+      CHK(h->d_dup_corr.alloc((size_t)h->dup_cap * h->Kp));
       HIPCHK(hipMemset(h->d_dup_corr, 0, (size_t)h->dup_cap * h->Kp * sizeof(float)));
     }
-    CHK(dev_alloc(&h->d_G, h->Ecap));
+    CHK(h->d_G.alloc(h->Ecap));
   }
   if (h->mf) {                                              // IMF / BPR / WRMF: the bias arrays (WRMF: the ones IMF's serving reads)
     const uint64_t inst_cap = p.emax * (h->mf == 2 ? h->hp.num_neg : 1u + h->hp.num_neg);
-    if (!als) CHK(dev_alloc(&h->d_UVpre, (size_t)inst_cap * h->Kp));
-    CHK(dev_alloc(&h->d_ub, (size_t)U)); CHK(dev_alloc(&h->d_ub_ag, (size_t)U));
+    if (!als) CHK(h->d_UVpre.alloc((size_t)inst_cap * h->Kp));
+    CHK(h->d_ub.alloc((size_t)U)); CHK(h->d_ub_ag.alloc((size_t)U));
     h->cnt[CDAE_P_UB] = h->cnt[CDAE_P_UB_AG] = (size_t)U;
     HIPCHK(hipMemset(h->d_ub, 0, (size_t)U * sizeof(float)));
   }
   if (als) {
-    CHK(dev_alloc(&h->d_tptr, I + 1));
-    CHK(dev_alloc(&h->d_tcol, nnz));
+    CHK(h->d_tptr.alloc(I + 1));
+    CHK(h->d_tcol.alloc(nnz));
     HIPCHK(hipMemcpy(h->d_tptr, p.item_major.ptr.data(), (I + 1) * sizeof(int64_t), hipMemcpyHostToDevice));
     if (nnz) HIPCHK(hipMemcpy(h->d_tcol, p.item_major.col.data(), nnz * sizeof(uint32_t), hipMemcpyHostToDevice));
   } else {
     h->sort_tmp_bytes = 0;
-    HIPCHK(rocprim::radix_sort_pairs(nullptr, h->sort_tmp_bytes, h->ex[0].item, h->ex[0].sorted_item, h->ex[0].val,
-                                     h->ex[0].sorted_val, (size_t)std::max<uint64_t>(h->Ecap, 1), 0u, (unsigned)h->sort_bits, h->stream));
+    HIPCHK(rocprim::radix_sort_pairs(nullptr, h->sort_tmp_bytes, h->ex[0].item.p, h->ex[0].sorted_item.p, h->ex[0].val.p,
+                                     h->ex[0].sorted_val.p, (size_t)std::max<uint64_t>(h->Ecap, 1), 0u, (unsigned)h->sort_bits, h->stream));
     if (h->ex[0].key16) {
       size_t bytes16 = 0;
-      HIPCHK(rocprim::radix_sort_pairs(nullptr, bytes16, h->ex[0].key16, h->ex[0].sorted_key16, h->ex[0].val, h->ex[0].sorted_val,
+      HIPCHK(rocprim::radix_sort_pairs(nullptr, bytes16, h->ex[0].key16.p, h->ex[0].sorted_key16.p, h->ex[0].val.p, h->ex[0].sorted_val.p,
                                        (size_t)std::max<uint64_t>(h->Ecap, 1), 0u, (unsigned)h->sort_bits, h->stream));
       h->sort_tmp_bytes = std::max(h->sort_tmp_bytes, bytes16);
     }
     h->sort_tmp_stride = (h->sort_tmp_bytes + 255) & ~(size_t)255;
-    CHK(dev_alloc((char**)&h->d_sort_tmp, 2 * h->sort_tmp_stride));
+    CHK(h->d_sort_tmp.alloc(2 * h->sort_tmp_stride));
     const size_t BK = (size_t)B * h->Kp;
-    CHK(dev_alloc(&h->d_Z, BK)); CHK(dev_alloc(&h->d_Dz, BK)); CHK(dev_alloc(&h->d_HG, BK));
-    if (h->cfg.linear_function) { CHK(dev_alloc(&h->d_Ssum, BK)); CHK(dev_alloc(&h->d_delta_rows, BK)); }
+    CHK(h->d_Z.alloc(BK)); CHK(h->d_Dz.alloc(BK)); CHK(h->d_HG.alloc(BK));
+    if (h->cfg.linear_function) { CHK(h->d_Ssum.alloc(BK)); CHK(h->d_delta_rows.alloc(BK)); }
     if (h->cfg.full_output) {
       h->Bp = (B + 127u) & ~127u;
       // big item spaces and K > 256: 256-row GEMM tiles (the K > 256 launches — gemm1_loss_duo_kernel, gemm_tn_bf16_kernel — want them)
       h->Ip = (I >= 32768 || h->Kp > 256) ? (((uint32_t)I + 255u) & ~255u) : (((uint32_t)I + 127u) & ~127u);
-      CHK(dev_alloc(&h->d_Zb, (size_t)h->Bp * h->Kp)); CHK(dev_alloc(&h->d_ZTb, (size_t)h->Kp * h->Bp));
-      CHK(dev_alloc(&h->d_Db, (size_t)h->Ip * h->Kp)); CHK(dev_alloc(&h->d_DTb, (size_t)h->Kp * h->Ip));
+      CHK(h->d_Zb.alloc((size_t)h->Bp * h->Kp)); CHK(h->d_ZTb.alloc((size_t)h->Kp * h->Bp));
+      CHK(h->d_Db.alloc((size_t)h->Ip * h->Kp)); CHK(h->d_DTb.alloc((size_t)h->Kp * h->Ip));
       // G [Bp x Ip] only where a launch reads it: the NT form of GEMM 2 (K > 256 without gemm_tn_bf16_kernel, or CDAE_FULL_UNFUSED);
       // the fused K <= 256 kernel and the TN form read G^T alone (2 GB less per handle at 1 M items x 1024 users)
-      if ((h->Kp > 256 || h->full_unfused) && !gemm2_tn_path(h)) CHK(dev_alloc(&h->d_Gb, (size_t)h->Bp * h->Ip));
-      CHK(dev_alloc(&h->d_GTb, (size_t)h->Ip * h->Bp));
-      CHK(dev_alloc(&h->d_dD, (size_t)h->Ip * h->Kp));
-      CHK(dev_alloc(&h->d_has_in, (size_t)h->Ip));
+      if ((h->Kp > 256 || h->full_unfused) && !gemm2_tn_path(h)) CHK(h->d_Gb.alloc((size_t)h->Bp * h->Ip));
+      CHK(h->d_GTb.alloc((size_t)h->Ip * h->Bp));
+      CHK(h->d_dD.alloc((size_t)h->Ip * h->Kp));
+      CHK(h->d_has_in.alloc((size_t)h->Ip));
       HIPCHK(hipMemsetAsync(h->d_has_in, 0, (size_t)h->Ip, h->stream));
       {
         // the rated-items bitmap is read by the fused K <= 256 decode only (the K = 512 launches patch their positives in place:
@@ -1821,7 +1797,7 @@ int upload_data_set(cdae_hip* h, const cdae::plan::Plan& p, const int64_t* grp, 
         // 1024-user block at 1 M items)
         if (h->Kp <= 256 && !h->full_unfused) {
           h->bits_stride = (size_t)B * ((I + 31) / 32);
-          CHK(dev_alloc(&h->d_bits_train, cdae_hip::NSETS * h->bits_stride));     // one per example-buffer set
+          CHK(h->d_bits_train.alloc(cdae_hip::NSETS * h->bits_stride));     // one per example-buffer set
         }
         // item slices of the fused decode: slices x Bp/128 workgroups ~ one per CU (measured best at B = 2048: 16 slices; every
         // slice adds a [B x Kp] partial of hg)
@@ -1832,10 +1808,10 @@ int upload_data_set(cdae_hip* h, const cdae::plan::Plan& p, const int64_t* grp, 
     if (h->cfg.full_output || h->item_shard) {
       std::vector<uint32_t> iota((size_t)std::max<uint32_t>(B, h->item_shard ? EVAL_CHUNK : 0u) + 1);
       std::iota(iota.begin(), iota.end(), 0u);
-      CHK(dev_alloc(&h->d_iota, iota.size()));
+      CHK(h->d_iota.alloc(iota.size()));
       HIPCHK(hipMemcpy(h->d_iota, iota.data(), iota.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
       // item shard: [input sums | gathered Wu rows | gathered Uu rows] of a batch, one all-reduce buffer
-      if (h->item_shard) CHK(dev_alloc(&h->d_Hsum, (size_t)SHARD_BLOCKS * B * h->Kp));
+      if (h->item_shard) CHK(h->d_Hsum.alloc((size_t)SHARD_BLOCKS * B * h->Kp));
     }
     {
       size_t rows = 8 * (size_t)h->unit_cap;
@@ -1844,12 +1820,12 @@ int upload_data_set(cdae_hip* h, const cdae::plan::Plan& p, const int64_t* grp, 
         const uint32_t kps = gemm2_k_per_split(h);                                 // unfused path: one [Bp x Kp] slab per contraction split
         rows = std::max(rows, (size_t)((h->Ip + kps - 1) / kps) * h->Bp);
       }
-      CHK(dev_alloc(&h->d_HGpart, rows * h->Kp));
+      CHK(h->d_HGpart.alloc(rows * h->Kp));
     }
   }
-  CHK(dev_alloc(&h->d_touched, (size_t)I));                 // (nothing touches an item of a WRMF handle; the delta entry points read the array)
+  CHK(h->d_touched.alloc((size_t)I));                 // (nothing touches an item of a WRMF handle; the delta entry points read the array)
   HIPCHK(hipMemset(h->d_touched, 0, (size_t)I * sizeof(uint32_t)));
-  if (!als) CHK(dev_alloc(&h->d_uids, (size_t)B));
+  if (!als) CHK(h->d_uids.alloc((size_t)B));
   // weights 0, accumulators 1e-4 (cdae.hpp:114,...), accumulator pad lanes 1: a well-defined state even
   // before init_params / set_param (a zero accumulator pad would make beta == 0 divide 0 by 0)
   auto fillm = [&](float* M, size_t rows, uint32_t K, uint32_t Kp, float v, float pad) {
@@ -2304,9 +2280,9 @@ int recommend_general(cdae_hip* h, uint64_t u_begin, uint64_t u_end, uint32_t to
   Scorer sc;
   CHK(sc.prepare(h, rated ? 1u : (uint32_t)std::min<uint64_t>(h->mf ? EVAL_CHUNK : 4096u, std::max<uint64_t>(h->U, 1)), topk, false));
   const uint32_t B = sc.chunk;
-  uint32_t* d_rated = nullptr;
+  DevBuf<uint32_t> d_rated;                       // (freed on every way out)
   if (rated) {
-    CHK(dev_alloc(&d_rated, std::max<uint32_t>(n_rated, 1)));
+    CHK(d_rated.alloc(n_rated));
     if (n_rated) HIPCHK(hipMemcpyAsync(d_rated, rated, n_rated * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
     const uint32_t one_unit[2] = {0u, 1u};
     HIPCHK(hipMemcpyAsync(h->d_uptr_tmp, one_unit, sizeof one_unit, hipMemcpyHostToDevice, h->stream));
@@ -2334,7 +2310,6 @@ int recommend_general(cdae_hip* h, uint64_t u_begin, uint64_t u_end, uint32_t to
     if (e != hipSuccess) rc = fail("recommend: %s", hipGetErrorString(e));
     else if (out) rc = copy_lists_out(h, (size_t)nb * topk, out + (s0 - u_begin) * topk, nullptr);
   }
-  if (d_rated) (void)hipFree(d_rated);
   return rc;
 }
 
@@ -2667,12 +2642,10 @@ int cdae_hip_set_test_rows(cdae_hip_t* h, const int64_t* test_row_ptr, const uin
   CHK(cdae_internal::validate_test_rows(test_row_ptr, test_col, U, h->item_shard ? h->I_global : h->I, &with_rows));
   const uint64_t nnz = (uint64_t)test_row_ptr[U];
   CHK(quiesce(h));
-  void** old[] = {(void**)&h->d_test_ptr, (void**)&h->d_test_col, (void**)&h->d_topn_pu, (void**)&h->d_topn_out};
-  for (void** p : old) if (*p) { HIPCHK(hipFree(*p)); *p = nullptr; }
-  CHK(dev_alloc(&h->d_test_ptr, U + 1));
-  CHK(dev_alloc(&h->d_test_col, std::max<uint64_t>(nnz, 1)));
-  CHK(dev_alloc(&h->d_topn_pu, U * 8));
-  CHK(dev_alloc(&h->d_topn_out, 16));
+  CHK(h->d_test_ptr.alloc(U + 1));
+  CHK(h->d_test_col.alloc(nnz));
+  CHK(h->d_topn_pu.alloc(U * 8));
+  CHK(h->d_topn_out.alloc(16));
   HIPCHK(hipMemcpy(h->d_test_ptr, test_row_ptr, (U + 1) * sizeof(int64_t), hipMemcpyHostToDevice));
   if (nnz) HIPCHK(hipMemcpy(h->d_test_col, test_col, nnz * sizeof(uint32_t), hipMemcpyHostToDevice));
   h->test_users_with_rows = with_rows;
@@ -2849,7 +2822,7 @@ int rows_run(cdae_hip* h, const RowsArgs& a, const FilterArgs& f = FilterArgs{})
   if (a.t_ptr) {
     CHK(upload_csr(h, h->d_rows_tptr, h->d_rows_tcol, a.t_ptr, a.t_col, R));
     CHK(h->d_rows_pu.ensure(R, 8));
-    if (!h->d_rows_out) CHK(dev_alloc(&h->d_rows_out, 16));
+    if (!h->d_rows_out) CHK(h->d_rows_out.alloc(16));
     HIPCHK(hipMemsetAsync(h->d_rows_out, 0, 16 * sizeof(double), h->stream));
   }
   if (f.excl_ptr) CHK(upload_csr(h, h->d_flt_eptr, h->d_flt_ecol, f.excl_ptr, f.excl_col, R));
@@ -3548,7 +3521,7 @@ int cdae_hip_train_one_user_corruption(cdae_hip_t* h, uint64_t uid, const uint32
   cdae_hip::ExBuf& x = h->ex[set];
   HIPCHK(hipMemcpyAsync(x.item, items.data(), E * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
   HIPCHK(hipMemcpyAsync(x.val, vals.data(), E * sizeof(uint64_t), hipMemcpyHostToDevice, h->stream));
-  HIPCHK(rocprim::radix_sort_pairs(h->d_sort_tmp, h->sort_tmp_bytes, x.item, x.sorted_item, x.val, x.sorted_val, E, 0u,
+  HIPCHK(rocprim::radix_sort_pairs(h->d_sort_tmp.p, h->sort_tmp_bytes, x.item.p, x.sorted_item.p, x.val.p, x.sorted_val.p, E, 0u,
                                    (unsigned)h->sort_bits, h->stream));
   HIPCHK(hipMemsetAsync(x.seg, 0, 4 * (size_t)h->I * sizeof(uint32_t), h->stream));
   HIPCHK(hipMemsetAsync(x.dup_count, 0, cdae::DUP_STRIPES * sizeof(uint32_t), h->stream));
@@ -3562,14 +3535,13 @@ int cdae_hip_train_one_user_corruption(cdae_hip_t* h, uint64_t uid, const uint32
   HIPCHK(hipMemcpyAsync(h->d_uptr_tmp, one_unit, sizeof one_unit, hipMemcpyHostToDevice, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));
   uint32_t* d_in = h->d_uids;                     // capacity min(B, U) >= 1; longer input sets get their own buffer
-  uint32_t* d_in_owned = nullptr;
-  if (n_in > std::min<uint64_t>(h->B, h->U)) { CHK(dev_alloc(&d_in_owned, n_in)); d_in = d_in_owned; }
+  DevBuf<uint32_t> d_in_owned;                    // (freed on every way out)
+  if (n_in > std::min<uint64_t>(h->B, h->U)) { CHK(d_in_owned.alloc(n_in)); d_in = d_in_owned; }
   if (n_in) HIPCHK(hipMemcpyAsync(d_in, in_sorted.data(), n_in * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
   h->prof_q = h->seq;
   int rc = compute_batch(h, set, Batch{uid, 1, 0, E}, 0, 0, d_in, (uint32_t)n_in);
   h->seq++;
   hipError_t se = hipStreamSynchronize(h->stream);
-  if (d_in_owned) (void)hipFree(d_in_owned);
   if (rc) return rc;
   if (se != hipSuccess) return fail("stream synchronize failed: %s", hipGetErrorString(se));
   return 0;
@@ -3580,7 +3552,7 @@ int cdae_hip_delta_begin(cdae_hip_t* h) {
   if (!h || !h->d_shared) return fail("set_interactions must be called first");
   HIPCHK(hipSetDevice(h->device));
   CHK(join_aux(h));
-  if (!h->d_base) { CHK(dev_alloc(&h->d_base, h->n_shared)); CHK(dev_alloc(&h->d_delta, h->n_shared + h->I)); }
+  if (!h->d_base) { CHK(h->d_base.alloc(h->n_shared)); CHK(h->d_delta.alloc(h->n_shared + h->I)); }
   HIPCHK(hipMemcpyAsync(h->d_base, h->d_shared, h->n_shared * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
   HIPCHK(hipMemsetAsync(h->d_touched, 0, h->I * sizeof(uint32_t), h->stream));
   return 0;
@@ -3637,8 +3609,8 @@ int cdae_hip_delta_stage(cdae_hip_t* h) {
   HIPCHK(hipSetDevice(h->device));
   CHK(join_aux(h));
   if (!h->d_recv) {
-    CHK(dev_alloc(&h->d_recv, h->n_shared + 4096));            // slack: collectives may round the count up
-    CHK(dev_alloc(&h->d_snap, h->n_shared));
+    CHK(h->d_recv.alloc(h->n_shared + 4096));            // slack: collectives may round the count up
+    CHK(h->d_snap.alloc(h->n_shared));
     HIPCHK(hipMemsetAsync(h->d_recv, 0, (h->n_shared + 4096) * sizeof(float), h->stream));
   }
   return launch_pipe<cdae::DELTA_STAGE>(h);
@@ -3788,7 +3760,7 @@ uint32_t shard_blocks(const cdae_hip_t* h) { return shard_blocks_of(h); }
 int set_item_shard_positions(cdae_hip_t* h, const uint32_t* len_and_first /* [2 U] */) {
   if (!h || !h->d_shared || !h->item_shard || !len_and_first) return fail("set_item_shard and set_interactions must be called first");
   HIPCHK(hipSetDevice(h->device));
-  if (!h->d_gpos) CHK(dev_alloc(&h->d_gpos, 2 * (size_t)h->U));
+  if (!h->d_gpos) CHK(h->d_gpos.alloc(2 * (size_t)h->U));
   HIPCHK(hipMemcpy(h->d_gpos, len_and_first, 2 * (size_t)h->U * sizeof(uint32_t), hipMemcpyHostToDevice));
   return 0;
 }
@@ -3801,8 +3773,8 @@ uint32_t eval_chunk() { return EVAL_CHUNK; }
 // block 0 = the users' input sums over this shard's rows; blocks 1.. = the Wu / Uu rows of the users this shard owns (zeros for everybody
 // else's: after the all-reduce(sum) every shard holds the owners' rows, bit for bit) — one launch (unit_sum_stage_kernel)
 static int sum_and_stage(cdae_hip* h, const float* hpart, const uint32_t* uptr, uint64_t u0, uint32_t n, float* buf) {
-  const float* ta = h->cfg.user_factor ? h->d_Wu : (h->cfg.linear_function ? h->d_Uu : nullptr);
-  const float* tb = h->cfg.user_factor && h->cfg.linear_function ? h->d_Uu : nullptr;
+  const float* ta = h->cfg.user_factor ? h->d_Wu.p : (h->cfg.linear_function ? h->d_Uu.p : nullptr);
+  const float* tb = h->cfg.user_factor && h->cfg.linear_function ? h->d_Uu.p : nullptr;
   DISPATCH_NI(h->NI, cdae::unit_sum_stage_kernel, dim3((n + 3) / 4), dim3(256), 0, h->stream, h->hp, hpart, uptr, n, u0, ta, tb, buf);
   return 0;
 }
@@ -3841,8 +3813,8 @@ int fs_phase0(cdae_hip_t* h, uint64_t seed, uint32_t epoch, uint64_t s0, uint32_
   if (!h->encode_two_launches && nb <= ENCODE_USERS_MAX) {
     // one launch (round 4): the training encode's workgroup-per-user kernel, stopped at the raw input sum of the local rows, with the
     // owner's private rows staged behind it — the same sums in the same order as the single handle's encode for every user
-    const float* ta = h->cfg.user_factor ? h->d_Wu : (h->cfg.linear_function ? h->d_Uu : nullptr);
-    const float* tb = h->cfg.user_factor && h->cfg.linear_function ? h->d_Uu : nullptr;
+    const float* ta = h->cfg.user_factor ? h->d_Wu.p : (h->cfg.linear_function ? h->d_Uu.p : nullptr);
+    const float* tb = h->cfg.user_factor && h->cfg.linear_function ? h->d_Uu.p : nullptr;
     DISPATCH_NI(h->NI, cdae::encode_users_kernel, dim3(nb), dim3(cdae::ENC_WAVES * cdae::WAVE), 0, h->stream, h->hp, h->d_row_ptr, h->d_col,
                 h->P(CDAE_P_W), uptr, s0, nb, cidx, seed, epoch, (const float*)nullptr, (const float*)nullptr, (float*)nullptr, (float*)nullptr,
                 (float*)nullptr, (const float*)nullptr, (float*)nullptr, (cdae::BF16_T*)nullptr, (cdae::BF16_T*)nullptr, 0u, h->d_Hsum, ta, tb,
