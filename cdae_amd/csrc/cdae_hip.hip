@@ -2541,14 +2541,20 @@ int cdae_hip_encode(cdae_hip_t* h, uint64_t seed, uint32_t epoch, int mode, cons
   CHK(join_aux(h));
   const uint32_t B = (uint32_t)std::min<uint64_t>(h->B, h->U);
   for (size_t i = 0; i < n; ++i) if (uids[i] >= h->U) return fail("user id %u out of range", uids[i]);
-  for (size_t c0 = 0; c0 < n; c0 += B) {
-    const uint32_t nb = (uint32_t)std::min<size_t>(B, n - c0);
+  std::vector<uint32_t> prefix;
+  for (size_t c0 = 0, nb = 0; c0 < n; c0 += nb) {
+    // a chunk: at most B users, and no more work units than the partial-sum rows hold — a list may name its heaviest user any
+    // number of times, which outweighs every batch of distinct users (one user always fits)
+    prefix.assign(1, 0u);
+    for (nb = 0; nb < B && c0 + nb < n; ++nb) {
+      const uint32_t units = h->h_unit_ptr[uids[c0 + nb] + 1] - h->h_unit_ptr[uids[c0 + nb]];
+      if (nb && prefix.back() + units > h->unit_cap) break;
+      prefix.push_back(prefix.back() + units);
+    }
     HIPCHK(hipMemcpyAsync(h->d_uids, uids + c0, nb * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
-    std::vector<uint32_t> prefix(nb + 1, 0u);
-    for (uint32_t i = 0; i < nb; ++i) prefix[i + 1] = prefix[i] + (h->h_unit_ptr[uids[c0 + i] + 1] - h->h_unit_ptr[uids[c0 + i]]);
     HIPCHK(hipMemcpyAsync(h->d_uptr_tmp, prefix.data(), (nb + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));                     // `prefix` is a stack temporary
-    CHK(encode_chunk(h, h->d_uids, 0, nb, mode, CDAE_STREAM_CORRUPT, 0, seed, epoch, prefix[nb]));
+    HIPCHK(hipStreamSynchronize(h->stream));                     // `prefix` is rewritten for the next chunk
+    CHK(encode_chunk(h, h->d_uids, 0, (uint32_t)nb, mode, CDAE_STREAM_CORRUPT, 0, seed, epoch, prefix[nb]));
     HIPCHK(hipMemcpy2DAsync(Z + c0 * h->K, h->K * sizeof(float), h->d_Z, h->Kp * sizeof(float), h->K * sizeof(float), nb,
                             hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));

@@ -296,7 +296,16 @@ int cdae_hip_debug_row_pack(cdae_hip_t* h, uint64_t seed, uint32_t epoch, uint64
 
 /* z for `n` users (get_hidden_values, cdae.hpp:373-416).  mode 0: full train row, scale 1 (the
  * inference form, cdae.hpp:169); mode 1: training corruption of (seed, epoch, corruption 0) with the
- * configured scale.  Z is [n x num_dim] fp32 on the host. */
+ * configured scale.  Z is [n x num_dim] fp32 on the host.  `uids` is any list: any user any number of times, in any order.
+ * The input sum takes the order cdae_hip_recommend_rows documents (groups of `unit` consecutive positions of the row, each group's
+ * kept rows added from 0 in ascending position, the group sums added from 0 in group order); the finish, element by element in fp32:
+ * acc = acc * Uu[u] (linear_function only, a rounded product), h = fmaf(acc, scale, b) — ONE rounding —, h = h + Wu[u]
+ * (user_factor only), z = act(h).  Both are part of the contract (tests/encode_ref.py restates them).
+ * Training encodes a batch of more than 768 users with exactly these two launches.  A batch of at most 768 users takes one launch
+ * (encode_users_kernel) with 16 wavefronts per user: wavefront w adds the group sums w, w + 16, w + 32, ... from 0 in that order,
+ * then the 16 wavefront sums are added from 0 in wavefront order, and the finish is the one above.  For a row of at most 16 groups
+ * (1024 items at unit 64) that is the same sum in the same order; beyond 16 groups it is a different association of the same
+ * terms, so the training z of such a row may differ from cdae_hip_encode(mode 1) in the last bits. */
 int cdae_hip_encode(cdae_hip_t* h, uint64_t seed, uint32_t epoch, int mode, const uint32_t* uids,
                     size_t n, float* Z);
 
