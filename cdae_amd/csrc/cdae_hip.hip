@@ -95,14 +95,18 @@ namespace {
       default: hipLaunchKernelGGL(KERNEL<8>, grid, block, shmem, stream, __VA_ARGS__); break;     \
     }                                                                                             \
   } while (0)
-// address of `KERNEL<NI, ...>` for the handle's NI (hipFuncSetAttribute)
-#define KERNEL_OF_NI(ni, KERNEL, ...)                                                                       \
-  ((ni) == 1 ? (const void*)KERNEL<1, ##__VA_ARGS__> : (ni) == 2 ? (const void*)KERNEL<2, ##__VA_ARGS__>    \
-   : (ni) == 4 ? (const void*)KERNEL<4, ##__VA_ARGS__> : (const void*)KERNEL<8, ##__VA_ARGS__>)
+// f(std::integral_constant<int, NI>) for the handle's NI, where a launch names further template arguments or only the kernel's
+// address is wanted (hipFuncSetAttribute)
+template <class F> auto dispatch_ni(uint32_t ni, F&& f) {
+  if (ni == 1) return f(std::integral_constant<int, 1>{});
+  if (ni == 2) return f(std::integral_constant<int, 2>{});
+  if (ni == 4) return f(std::integral_constant<int, 4>{});
+  return f(std::integral_constant<int, 8>{});
+}
 
 // f(std::integral_constant<int, NCH>) for the contraction length NCH of the matrix-core sweeps (recommend_mfma_kernel,
 // full_rank_mfma_kernel) at num_dim K <= 256: the one place that maps num_dim to it
-template <class F> int dispatch_nch(uint32_t K, F&& f) {
+template <class F> auto dispatch_nch(uint32_t K, F&& f) {
   if (K <= 32) return f(std::integral_constant<int, 4>{});
   if (K <= 64) return f(std::integral_constant<int, 8>{});
   if (K <= 128) return f(std::integral_constant<int, 16>{});
@@ -253,7 +257,6 @@ struct cdae_hip {
   // TOPN metrics on the device (cdae_hip_set_test_rows / cdae_hip_eval_topn): the validation rows as CSR, per-user metric terms
   DevBuf<int64_t> d_test_ptr; DevBuf<uint32_t> d_test_col; DevBuf<double> d_topn_pu, d_topn_out;
   uint64_t test_users_with_rows = 0;
-  bool topn_active = false;             // recommend paths: score every chunk's lists with topn_user_kernel (cdae_hip_eval_topn)
   // cdae_hip_recommend_rows / cdae_hip_eval_topn_rows: the caller's rated sets (CSR + user of every row), target sets and per-row metric
   // terms; grow-only (capacities in rows / items), so a steady-state call allocates nothing
   DevBuf<int64_t> d_rows_ptr, d_rows_tptr;
@@ -2188,14 +2191,18 @@ int fill_stats(cdae_hip* h, cdae_hip_stats* stats) {
 
 }  // namespace
 
-// recommend(), general path (cdae_kernels.hpp recommend_kernel): any num_dim / topk / item count; one workgroup per user.
-// rated != nullptr: ONE user whose input set and mask are the caller's list (sorted, unique) instead of the train row.
+// ---- top-k lists: one sweep behind every entry point that returns them -------------------------------------------------
+// Per chunk an entry point produces hidden rows z and names a mask; TopkSweep::run leaves the chunk's lists in h->d_rec, an optional
+// hook scores them there, copy_lists_out hands them to the caller.  A new list-producing entry point is a z-producer and a mask.
 namespace {
-// cdae_hip_eval_topn: the lists of users [u0, u0 + nu) sit in h->d_rec — score them against the test rows (same stream, no host round trip)
-void topn_chunk(cdae_hip* h, uint32_t topk, uint64_t u0, uint32_t nu) {
-  hipLaunchKernelGGL(cdae::topn_user_kernel, dim3((nu + 255) / 256), dim3(256), 0, h->stream, (const uint32_t*)h->d_rec, topk, u0, nu,
-                     (const int64_t*)h->d_test_ptr, (const uint32_t*)h->d_test_col, (double)h->test_users_with_rows, h->d_topn_pu,
-                     reinterpret_cast<unsigned long long*>(h->d_topn_out + 8));
+// The per-chunk hook of the TOPN entry points: the lists of rows [r0, r0 + nu) sit in h->d_rec — score them against rows of the target
+// CSR (same stream, no host round trip): per-row terms to pu, hit counts to out16[8, 11)
+struct TopnHook { const int64_t* ptr; const uint32_t* col; double rows_with_targets; double* pu; double* out16; };
+int topn_chunk(cdae_hip* h, const TopnHook& t, uint32_t topk, uint64_t r0, uint32_t nu) {
+  hipLaunchKernelGGL(cdae::topn_user_kernel, dim3((nu + 255) / 256), dim3(256), 0, h->stream, (const uint32_t*)h->d_rec, topk, r0, nu,
+                     t.ptr, t.col, t.rows_with_targets, t.pu, reinterpret_cast<unsigned long long*>(t.out16 + 8));
+  HIPCHK(hipGetLastError());
+  return 0;
 }
 // The tail of both TOPN entry points: the per-row terms `pu` of n rows summed in row order into out16[0, 8) (its hit counts are already
 // in [8, 11)), then the sixteen doubles to the host.
@@ -2225,61 +2232,111 @@ ScorePlace score_place(uint64_t items, uint32_t rows) {
   if (lds_scores <= 160 * 1024) return {true, lds_scores, rows};
   return {false, 64, (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(rows, (256ull << 20) / (items * sizeof(float))))};
 }
-// recommend_kernel over this handle's item rows, for the single handle's general path and an item shard's local lists alike.
-// prepare(): score_place's decision, the workspaces (lists in d_rec; with_scores: their scores in d_rec_score) and the dynamic-LDS
-// attribute; launch(): one chunk of at most `chunk` users.
-// prepare(..., items, true) + launch_bits(): the same over `items` rows of any decoder image, masked from a bit table
-// (recommend_kernel<NI, true>: cdae_hip_recommend_rows_filtered); a score row is then `items` floats.
-struct Scorer {
-  bool in_lds = false, with_scores = false;
-  size_t shmem = 0;
-  uint32_t chunk = 0, topk = 0;
-  int prepare(cdae_hip* h, uint32_t users, uint32_t topk_, bool with_scores_, uint64_t items = 0, bool bits_form = false) {
-    if (items == 0) items = h->I;
-    const ScorePlace sp = score_place(items, users);
-    in_lds = sp.in_lds; shmem = sp.shmem; chunk = sp.rows;
-    topk = topk_; with_scores = with_scores_;
-    if (!in_lds) CHK(h->d_score.ensure((size_t)chunk * items));
+// What the rows of a chunk may not return.
+//   CSR:    rows [c0, c0 + nu) of the CSR (ptr, col), as it is: rated_bits_kernel in front of the matrix cores, recommend_kernel's own
+//           CSR mask on the general path.
+//   FILTER: filter_bits_kernel's inputs — rows of the "rated" CSR (ptr, col) or null | rows of the excl CSR (eptr, ecol) or null, at
+//           the places `pos` gives the items (null: their ids).  Both paths mask from the bit table it builds.
+//   LIST:   ONE row (general path only) masked by the sorted list (list, n) instead of its row of (ptr, col).
+struct Mask {
+  enum Kind { CSR, FILTER, LIST } kind;
+  const int64_t* ptr; const uint32_t* col;
+  const int64_t* eptr = nullptr; const uint32_t* ecol = nullptr; const uint32_t* pos = nullptr;
+  const uint32_t* list = nullptr; uint32_t n = 0;
+};
+// The top-k sweep of hidden rows over a decoder image.  Matrix cores (topk <= REC_TOPK_MAX, num_dim <= 256, where the entry point
+// may take them): recommend_mfma_kernel, all rows of a chunk in one launch, masked from bit rows in h->d_bits, the contraction length
+// by dispatch_nch.  General path: recommend_kernel, any num_dim / topk / item count, one workgroup per row, a row's scores where
+// score_place puts them.  The lists land in h->d_rec and, with_scores, their scores in h->d_rec_score.
+struct TopkSweep {
+  cdae::HyperParams hp; const float* D; const float* bp;   // the swept image: hp.num_items rows of (D, bp), the index space of the lists
+  uint32_t topk; bool with_scores;
+  const uint32_t* allow;        // non-null: the image's rows are these items of the catalogue, and the lists' places are mapped back to ids
+  bool mfma;
+  bool in_lds = false; size_t shmem = 0; uint32_t chunk = 0, words = 0;      // prepare()'s
+  TopkSweep(const cdae_hip* h, const cdae::HyperParams& hp_, const float* D_, const float* bp_, uint32_t topk_, bool with_scores_,
+            const uint32_t* allow_ = nullptr, bool may_mfma = true)
+      : hp(hp_), D(D_), bp(bp_), topk(topk_), with_scores(with_scores_), allow(allow_),
+        mfma(may_mfma && topk_ <= (uint32_t)cdae::REC_TOPK_MAX && h->K <= 256) {}
+  // Once per call, for launches of at most `rows` rows: the chunk (the general path's global score workspace may bound it further),
+  // the grow-only workspaces of the path taken, the dynamic-LDS attribute of the kernel it launches.
+  int prepare(cdae_hip* h, uint32_t rows, Mask::Kind kind) {
+    const uint64_t items = hp.num_items;
+    const bool bits_form = kind == Mask::FILTER;
+    const void* kernel;
+    words = (uint32_t)((items + 31) / 32);
+    chunk = rows;
+    if (mfma) {
+      kernel = dispatch_nch(h->K, [&](auto nch) {
+        constexpr int NCH = decltype(nch)::value;
+        shmem = cdae::recommend_mfma_lds_bytes(NCH);
+        return with_scores ? (const void*)cdae::recommend_mfma_kernel<NCH, true> : (const void*)cdae::recommend_mfma_kernel<NCH, false>;
+      });
+    } else {
+      const ScorePlace sp = score_place(items, rows);
+      in_lds = sp.in_lds; shmem = sp.shmem; chunk = sp.rows;
+      if (!in_lds) CHK(h->d_score.ensure((size_t)chunk * items));
+      kernel = dispatch_ni(h->NI, [&](auto ni) {
+        constexpr int NI = decltype(ni)::value;
+        return bits_form ? (const void*)cdae::recommend_kernel<NI, true> : (const void*)cdae::recommend_kernel<NI, false>;
+      });
+    }
     CHK(h->d_rec.ensure((size_t)chunk * topk));
     if (with_scores) CHK(h->d_rec_score.ensure((size_t)chunk * topk));
-    const void* kernel = bits_form ? KERNEL_OF_NI(h->NI, cdae::recommend_kernel, true) : KERNEL_OF_NI(h->NI, cdae::recommend_kernel);
+    if (mfma || bits_form) CHK(h->d_bits.ensure((size_t)chunk * words));
     HIPCHK(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
     return 0;
   }
-  // nb hidden rows z over hp.num_items rows of the decoder image (D, bp), row r masked from words [r words, (r + 1) words) of `bits`
-  template <int NI>
-  void launch_bits_as(cdae_hip* h, const cdae::HyperParams& hp, uint32_t nb, const float* z, const float* D, const float* bp,
-                      const uint32_t* bits, uint32_t words) const {
-    hipLaunchKernelGGL((cdae::recommend_kernel<NI, true>), dim3(nb), dim3(256), shmem, h->stream, hp, (const int64_t*)nullptr,
-                       (const uint32_t*)nullptr, (uint64_t)0, z, D, bp, topk, h->d_rec, in_lds ? (float*)nullptr : h->d_score, bits, words,
-                       with_scores ? h->d_rec_score : (float*)nullptr);
-  }
-  void launch_bits(cdae_hip* h, const cdae::HyperParams& hp, uint32_t nb, const float* z, const float* D, const float* bp,
-                   const uint32_t* bits, uint32_t words) const {
-    switch (h->NI) {
-      case 1: launch_bits_as<1>(h, hp, nb, z, D, bp, bits, words); break;
-      case 2: launch_bits_as<2>(h, hp, nb, z, D, bp, bits, words); break;
-      case 4: launch_bits_as<4>(h, hp, nb, z, D, bp, bits, words); break;
-      default: launch_bits_as<8>(h, hp, nb, z, D, bp, bits, words); break;
+  // nu <= chunk hidden rows z, rows [c0, c0 + nu) of the mask: the bit rows where the path needs them, the sweep, the way back to ids
+  int run(cdae_hip* h, const float* z, uint64_t c0, uint32_t nu, const Mask& m) const {
+    const dim3 blk(256);
+    float* const rec_score = with_scores ? h->d_rec_score.p : nullptr;
+    if (m.kind == Mask::FILTER)
+      hipLaunchKernelGGL(cdae::filter_bits_kernel, dim3((nu + 3) / 4), blk, 0, h->stream, m.ptr, m.col, m.eptr, m.ecol, m.pos, c0, nu, words,
+                         h->d_bits.p);
+    else if (mfma)
+      hipLaunchKernelGGL(cdae::rated_bits_kernel, dim3((nu + 3) / 4), blk, 0, h->stream, m.ptr, m.col, c0, nu, words, h->d_bits.p);
+    if (mfma) {
+      const dim3 grid((nu + cdae::REC_USERS_PER_BLOCK - 1) / cdae::REC_USERS_PER_BLOCK);
+      dispatch_nch(h->K, [&](auto nch) {
+        constexpr int NCH = decltype(nch)::value;
+        const auto launch = [&](auto kernel) {
+          hipLaunchKernelGGL(kernel, grid, blk, shmem, h->stream, hp, z, nu, D, bp, (const uint32_t*)h->d_bits, words, topk, h->d_rec.p, rec_score);
+        };
+        if (with_scores) launch(cdae::recommend_mfma_kernel<NCH, true>);
+        else launch(cdae::recommend_mfma_kernel<NCH, false>);
+      });
+    } else {
+      float* const score_ws = in_lds ? nullptr : h->d_score.p;
+      dispatch_ni(h->NI, [&](auto ni) {
+        constexpr int NI = decltype(ni)::value;
+        if (m.kind == Mask::FILTER)
+          hipLaunchKernelGGL((cdae::recommend_kernel<NI, true>), dim3(nu), blk, shmem, h->stream, hp, (const int64_t*)nullptr,
+                             (const uint32_t*)nullptr, (uint64_t)0, z, D, bp, topk, h->d_rec.p, score_ws, (const uint32_t*)h->d_bits, words, rec_score);
+        else
+          hipLaunchKernelGGL((cdae::recommend_kernel<NI, false>), dim3(nu), blk, shmem, h->stream, hp, m.ptr, m.col, c0, z, D, bp, topk,
+                             h->d_rec.p, score_ws, m.list, m.n, rec_score);
+      });
     }
-  }
-  // users [u0, u0 + nb) with hidden rows z; d_rated != nullptr: the caller's input set instead of the train row (one user);
-  // rows_ptr != nullptr: rows [u0, u0 + nb) of that device CSR are the masks instead of the train rows (cdae_hip_recommend_rows)
-  void launch(cdae_hip* h, uint64_t u0, uint32_t nb, const float* z, const uint32_t* d_rated = nullptr, uint32_t n_rated = 0,
-              const int64_t* rows_ptr = nullptr, const uint32_t* rows_col = nullptr) const {
-    DISPATCH_NI(h->NI, cdae::recommend_kernel, dim3(nb), dim3(256), shmem, h->stream, h->hp, rows_ptr ? rows_ptr : (const int64_t*)h->d_row_ptr,
-                rows_ptr ? rows_col : (const uint32_t*)h->d_col, u0, z, h->dec(),
-                h->P(CDAE_P_BP), topk, h->d_rec, in_lds ? (float*)nullptr : h->d_score, d_rated, n_rated,
-                with_scores ? h->d_rec_score : (float*)nullptr);
+    if (allow)
+      hipLaunchKernelGGL(cdae::remap_ids_kernel, dim3((uint32_t)(((size_t)nu * topk + 255) / 256)), blk, 0, h->stream, allow, (size_t)nu * topk,
+                         h->d_rec.p);
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? 0 : fail("recommend: %s", hipGetErrorString(e));
   }
 };
 
-int recommend_general(cdae_hip* h, uint64_t u_begin, uint64_t u_end, uint32_t topk, uint32_t* out, const uint32_t* rated, uint32_t n_rated) {
+// cdae_hip_recommend_all and cdae_hip_eval_topn (hook != nullptr: every chunk's lists are scored on the device, and out may be null);
+// rated != nullptr (cdae_hip_recommend_user): ONE user whose input set and mask are the caller's list (sorted, unique) instead of the
+// train row, on the general path whatever num_dim is.
+int recommend_run(cdae_hip* h, uint64_t u_begin, uint64_t u_end, uint32_t topk, uint32_t* out, const TopnHook* hook,
+                  const uint32_t* rated = nullptr, uint32_t n_rated = 0) {
+  TopkSweep sweep(h, h->hp, h->dec(), h->P(CDAE_P_BP), topk, false, nullptr, !rated);
   // users per launch: a chunk of the EVALUATION workspace, not of the training batch (through round 3 it was batch_users: a handle
   // with one user per block — the reference schedule — evaluated 16 384 users in 16 384 launches + host round trips, 75 s)
-  Scorer sc;
-  CHK(sc.prepare(h, rated ? 1u : (uint32_t)std::min<uint64_t>(h->mf ? EVAL_CHUNK : 4096u, std::max<uint64_t>(h->U, 1)), topk, false));
-  const uint32_t B = sc.chunk;
+  const uint64_t rows = sweep.mfma ? std::min<uint64_t>(std::max<uint64_t>(u_end - u_begin, 1), EVAL_CHUNK)
+                        : rated    ? 1 : std::min<uint64_t>(h->mf ? EVAL_CHUNK : 4096u, std::max<uint64_t>(h->U, 1));
+  CHK(sweep.prepare(h, (uint32_t)rows, rated ? Mask::LIST : Mask::CSR));
   DevBuf<uint32_t> d_rated;                       // (freed on every way out)
   if (rated) {
     CHK(d_rated.alloc(n_rated));
@@ -2288,54 +2345,53 @@ int recommend_general(cdae_hip* h, uint64_t u_begin, uint64_t u_end, uint32_t to
     HIPCHK(hipMemcpyAsync(h->d_uptr_tmp, one_unit, sizeof one_unit, hipMemcpyHostToDevice, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
   }
-  int rc = 0;
-  for (uint64_t s0 = u_begin; s0 < u_end && !rc; s0 += B) {
-    const uint32_t nb = (uint32_t)std::min<uint64_t>(B, u_end - s0);
+  Mask mask{rated ? Mask::LIST : Mask::CSR, h->d_row_ptr, h->d_col};
+  mask.list = d_rated; mask.n = n_rated;
+  for (uint64_t c0 = u_begin; c0 < u_end; c0 += sweep.chunk) {
+    const uint32_t nu = (uint32_t)std::min<uint64_t>(sweep.chunk, u_end - c0);
+    const float* z;
     if (rated) {
       // get_hidden_values(uid, rated_items) with the default scale 1 (cdae.hpp:169; q == 1 -> empty input, :168-172)
       const bool none = h->hp.keep_thr == 0x100000000ull;
       DISPATCH_NI(h->NI, cdae::encode_partial_kernel, dim3(1), dim3(256), 0, h->stream, h->hp, h->d_row_ptr, h->d_col, h->P(CDAE_P_W),
-                  (const uint32_t*)h->d_uptr_tmp, 1u, (const uint32_t*)nullptr, s0, 1u, 0, CDAE_STREAM_CORRUPT, 0u, (uint64_t)0, 0u, h->d_Hpart,
+                  (const uint32_t*)h->d_uptr_tmp, 1u, (const uint32_t*)nullptr, c0, 1u, 0, CDAE_STREAM_CORRUPT, 0u, (uint64_t)0, 0u, h->d_Hpart,
                   (const uint32_t*)d_rated, none ? 0u : n_rated, (const uint32_t*)nullptr);
       DISPATCH_NI(h->NI, cdae::encode_finish_kernel, dim3(1), dim3(256), 0, h->stream, h->hp, h->d_Hpart, (const uint32_t*)h->d_uptr_tmp, h->d_Wu,
-                  h->P(CDAE_P_B), (const uint32_t*)nullptr, s0, 1u, 0, h->d_Z, (float*)nullptr, (float*)nullptr, h->d_Uu, (float*)nullptr);
-    } else if (!h->mf) {
-      rc = ensure_eval_ws(h, nb, h->h_unit_ptr[s0 + nb] - h->h_unit_ptr[s0]);
-      if (!rc) rc = encode_chunk(h, nullptr, s0, nb, 0, CDAE_STREAM_CORRUPT, 0, 0, 0, 0, h->d_zeval, h->d_hpart_eval, (uint32_t)h->d_hpart_eval.cap);      // cdae.hpp:167-172
-      if (rc) break;
+                  h->P(CDAE_P_B), (const uint32_t*)nullptr, c0, 1u, 0, h->d_Z, (float*)nullptr, (float*)nullptr, h->d_Uu, (float*)nullptr);
+      z = h->d_Z;
+    } else if (h->mf) {
+      z = h->d_Wu + (size_t)c0 * h->Kp;           // IMF / BPR: score = ub + ib + uv . iv (imf.hpp:117-119); ub does not rank
+    } else {
+      CHK(ensure_eval_ws(h, nu, h->h_unit_ptr[c0 + nu] - h->h_unit_ptr[c0]));
+      CHK(encode_chunk(h, nullptr, c0, nu, 0, CDAE_STREAM_CORRUPT, 0, 0, 0, 0, h->d_zeval, h->d_hpart_eval, (uint32_t)h->d_hpart_eval.cap));   // cdae.hpp:167-172, full rows
+      z = h->d_zeval;
     }
-    sc.launch(h, s0, nb, h->mf ? h->d_Wu + (size_t)s0 * h->Kp : (rated ? h->d_Z : h->d_zeval), d_rated, n_rated);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess && h->topn_active) { topn_chunk(h, topk, s0, nb); e = hipGetLastError(); }
-    if (e != hipSuccess) rc = fail("recommend: %s", hipGetErrorString(e));
-    else if (out) rc = copy_lists_out(h, (size_t)nb * topk, out + (s0 - u_begin) * topk, nullptr);
+    CHK(sweep.run(h, z, c0, nu, mask));
+    if (hook) CHK(topn_chunk(h, *hook, topk, c0, nu));
+    if (out) CHK(copy_lists_out(h, (size_t)nu * topk, out + (c0 - u_begin) * topk, nullptr));
   }
-  return rc;
-}
-
-// recommend(), matrix-core path (topk <= REC_TOPK_MAX, num_dim <= 256): recommend_mfma_kernel over nu hidden rows z and their bit
-// rows in h->d_bits, lists to h->d_rec, the contraction length by dispatch_nch.  d_score == nullptr: the instantiations
-// cdae_hip_recommend_all has always launched; otherwise the SCORES ones (cdae_hip_recommend_rows with out_scores).
-// src != nullptr (cdae_hip_recommend_rows_filtered with an allow list): the sweep runs over src->hp.num_items rows of that decoder
-// image instead of the handle's; the bit table in h->d_bits is then in that index space, and so are the ids of the lists.
-bool mfma_path(const cdae_hip* h, uint32_t topk) { return topk <= (uint32_t)cdae::REC_TOPK_MAX && h->K <= 256; }
-struct SweepSrc { cdae::HyperParams hp; const float* D; const float* bp; };
-template <int NCH, bool SCORES>
-int launch_recommend_mfma_as(cdae_hip* h, const float* z, uint32_t nu, uint32_t words, uint32_t topk, float* d_score, const SweepSrc* src) {
-  const size_t lds = cdae::recommend_mfma_lds_bytes(NCH);
-  const dim3 grid((nu + cdae::REC_USERS_PER_BLOCK - 1) / cdae::REC_USERS_PER_BLOCK);
-  HIPCHK(hipFuncSetAttribute((const void*)cdae::recommend_mfma_kernel<NCH, SCORES>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  hipLaunchKernelGGL((cdae::recommend_mfma_kernel<NCH, SCORES>), grid, dim3(256), lds, h->stream, src ? src->hp : h->hp, z, nu,
-                     src ? src->D : (const float*)h->dec(), src ? src->bp : (const float*)h->P(CDAE_P_BP), (const uint32_t*)h->d_bits, words,
-                     topk, h->d_rec, d_score);
   return 0;
 }
-int launch_recommend_mfma(cdae_hip* h, const float* z, uint32_t nu, uint32_t words, uint32_t topk, float* d_score, const SweepSrc* src = nullptr) {
-  return dispatch_nch(h->K, [&](auto nch) {
-    constexpr int NCH = decltype(nch)::value;
-    return d_score ? launch_recommend_mfma_as<NCH, true>(h, z, nu, words, topk, d_score, src)
-                   : launch_recommend_mfma_as<NCH, false>(h, z, nu, words, topk, nullptr, src);
-  });
+// cdae_hip_recommend_all (hook == nullptr) and the run of cdae_hip_eval_topn behind the same argument checks
+int recommend_all(cdae_hip* h, uint64_t u_begin, uint64_t u_end, uint32_t topk, uint32_t* out, const TopnHook* hook) {
+  if (!h || !h->d_shared || (!out && !hook)) return fail("bad argument");
+  if (u_begin > u_end || u_end > h->U) return fail("bad user range");
+  if (topk == 0 || topk > h->I) return fail("topk must be in [1, num_items]");
+  HIPCHK(hipSetDevice(h->device));
+  CHK(join_aux(h));
+  if (!h->user_perm.empty()) {
+    // device rows are in training order: rank every position, hand the lists out by user id
+    std::vector<uint32_t> perm, inv;
+    perm.swap(h->user_perm); inv.swap(h->user_inv);          // (the recursive call sees an identity order)
+    std::vector<uint32_t> all((size_t)h->U * topk);
+    const int rc = recommend_all(h, 0, h->U, topk, all.data(), nullptr);
+    h->user_perm.swap(perm); h->user_inv.swap(inv);
+    if (rc) return rc;
+    for (uint64_t u = u_begin; u < u_end; ++u)
+      std::copy(all.begin() + (size_t)h->user_inv[u] * topk, all.begin() + ((size_t)h->user_inv[u] + 1) * topk, out + (u - u_begin) * topk);
+    return 0;
+  }
+  return recommend_run(h, u_begin, u_end, topk, out, hook);
 }
 }  // namespace
 
@@ -2597,45 +2653,7 @@ int cdae_hip_penalty_loss(cdae_hip_t* h, double* out) {
 }
 
 int cdae_hip_recommend_all(cdae_hip_t* h, uint64_t u_begin, uint64_t u_end, uint32_t topk, uint32_t* out) {
-  if (!h || !h->d_shared || (!out && !h->topn_active)) return fail("bad argument");
-  if (u_begin > u_end || u_end > h->U) return fail("bad user range");
-  if (topk == 0 || topk > h->I) return fail("topk must be in [1, num_items]");
-  HIPCHK(hipSetDevice(h->device));
-  CHK(join_aux(h));
-  if (!h->user_perm.empty()) {
-    // device rows are in training order: rank every position, hand the lists out by user id
-    std::vector<uint32_t> perm, inv;
-    perm.swap(h->user_perm); inv.swap(h->user_inv);          // (the recursive call sees an identity order)
-    std::vector<uint32_t> all((size_t)h->U * topk);
-    const int rc = cdae_hip_recommend_all(h, 0, h->U, topk, all.data());
-    h->user_perm.swap(perm); h->user_inv.swap(inv);
-    if (rc) return rc;
-    for (uint64_t u = u_begin; u < u_end; ++u)
-      std::copy(all.begin() + (size_t)h->user_inv[u] * topk, all.begin() + ((size_t)h->user_inv[u] + 1) * topk, out + (u - u_begin) * topk);
-    return 0;
-  }
-  if (mfma_path(h, topk)) {
-    // matrix-core path: all users of a chunk in one launch (cdae_recommend_kernels.hpp)
-    const uint32_t words = (uint32_t)((h->I + 31) / 32);
-    const uint64_t n_all = u_end - u_begin;
-    const uint32_t UC = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(n_all, 1), EVAL_CHUNK);
-    CHK(h->d_bits.ensure((size_t)UC * words));
-    CHK(h->d_rec.ensure((size_t)UC * topk));
-    for (uint64_t c0 = u_begin; c0 < u_end; c0 += UC) {
-      const uint32_t nu = (uint32_t)std::min<uint64_t>(UC, u_end - c0);
-      if (!h->mf) CHK(ensure_eval_ws(h, nu, h->h_unit_ptr[c0 + nu] - h->h_unit_ptr[c0]));
-      hipLaunchKernelGGL(cdae::rated_bits_kernel, dim3((nu + 3) / 4), dim3(256), 0, h->stream, h->d_row_ptr, h->d_col, c0, nu, words, h->d_bits);
-      const float* zsrc = h->d_zeval;
-      if (h->mf) zsrc = h->d_Wu + (size_t)c0 * h->Kp;      // IMF / BPR: score = ub + ib + uv . iv (imf.hpp:117-119); ub does not rank
-      else CHK(encode_chunk(h, nullptr, c0, nu, 0, CDAE_STREAM_CORRUPT, 0, 0, 0, 0, h->d_zeval, h->d_hpart_eval, (uint32_t)h->d_hpart_eval.cap));   // cdae.hpp:167-172, full rows
-      CHK(launch_recommend_mfma(h, zsrc, nu, words, topk, nullptr));
-      HIPCHK(hipGetLastError());
-      if (h->topn_active) { topn_chunk(h, topk, c0, nu); HIPCHK(hipGetLastError()); }
-      if (out) CHK(copy_lists_out(h, (size_t)nu * topk, out + (c0 - u_begin) * topk, nullptr));
-    }
-    return 0;
-  }
-  return recommend_general(h, u_begin, u_end, topk, out, nullptr, 0);
+  return recommend_all(h, u_begin, u_end, topk, out, nullptr);
 }
 
 // The validation rows TOPN_Evaluation scores against (evaluation.hpp:118-120 builds them as a hashtable on every call): CSR over
@@ -2668,6 +2686,8 @@ int cdae_hip_eval_topn(cdae_hip_t* h, uint32_t topk, double* rets8, uint64_t* hi
   if (h->test_users_with_rows == 0) return fail("no user has test items");
   HIPCHK(hipSetDevice(h->device));
   CHK(join_aux(h));
+  const TopnHook hook{h->d_test_ptr, h->d_test_col, (double)h->test_users_with_rows, h->d_topn_pu, h->d_topn_out};
+  HIPCHK(hipMemsetAsync(h->d_topn_out, 0, 16 * sizeof(double), h->stream));
   if (!h->user_perm.empty()) {
     // IMF / BPR block schedules keep their rows in training order: take the lists by user id, score them from a staged copy
     std::vector<uint32_t> all((size_t)h->U * topk);
@@ -2675,19 +2695,14 @@ int cdae_hip_eval_topn(cdae_hip_t* h, uint32_t topk, double* rets8, uint64_t* hi
     if (ids_out) std::copy(all.begin(), all.end(), ids_out);
     const uint32_t UC = (uint32_t)std::min<uint64_t>(h->U, EVAL_CHUNK);
     CHK(h->d_rec.ensure((size_t)UC * topk));
-    HIPCHK(hipMemsetAsync(h->d_topn_out, 0, 16 * sizeof(double), h->stream));
     for (uint64_t c0 = 0; c0 < h->U; c0 += UC) {
       const uint32_t nu = (uint32_t)std::min<uint64_t>(UC, h->U - c0);
       HIPCHK(hipMemcpyAsync(h->d_rec, all.data() + c0 * topk, (size_t)nu * topk * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
-      topn_chunk(h, topk, c0, nu);
+      CHK(topn_chunk(h, hook, topk, c0, nu));
       HIPCHK(hipStreamSynchronize(h->stream));
     }
   } else {
-    HIPCHK(hipMemsetAsync(h->d_topn_out, 0, 16 * sizeof(double), h->stream));
-    h->topn_active = true;
-    const int rc = cdae_hip_recommend_all(h, 0, h->U, topk, ids_out);
-    h->topn_active = false;
-    if (rc) return rc;
+    CHK(recommend_all(h, 0, h->U, topk, ids_out, &hook));
   }
   return topn_finish(h, h->d_topn_pu, h->U, h->d_topn_out, rets8, hits3);
 }
@@ -2707,7 +2722,7 @@ int cdae_hip_recommend_user(cdae_hip_t* h, uint64_t uid, const uint32_t* rated_i
     if (rated[i] >= h->I) return fail("rated item %u out of range", rated[i]);
     if (i && rated[i] == rated[i - 1]) return fail("duplicate rated item %u", rated[i]);
   }
-  return recommend_general(h, uid, uid + 1, topk, out, rated.data(), (uint32_t)n_rated);
+  return recommend_run(h, uid, uid + 1, topk, out, nullptr, rated.data(), (uint32_t)n_rated);
 }
 
 }  // extern "C"
@@ -2797,15 +2812,15 @@ int rows_encode_chunk(cdae_hip* h, const int64_t* row_ptr, uint64_t c0, uint32_t
   return 0;
 }
 // ---- the top-k run of every rows entry point (cdae_hip_recommend_rows, cdae_hip_eval_topn_rows, cdae_hip_recommend_rows_filtered) ------
-// A chunk's rows are encoded, filter_bits_kernel builds their exclusion rows (rated rows if the call excludes them | excl rows) as a bit
-// table and both top-k paths mask from it; the unfiltered entry points are the run with "exclude rated, no excl rows, no allow list".
-// A run with exactly that filter masks from the rated CSR as it is — rated_bits_kernel in front of the matrix cores, recommend_kernel's
-// own CSR mask on the general path, the kernels those entry points have always launched: through the bit table the general path took
+// The z-producer is rows_encode_chunk.  The mask is Mask::FILTER — filter_bits_kernel builds a chunk's exclusion rows (rated rows if the
+// call excludes them | excl rows) as a bit table and both top-k paths mask from it; the unfiltered entry points are the run with
+// "exclude rated, no excl rows, no allow list".  A run with exactly that filter takes Mask::CSR over the rated CSR as it is, the
+// kernels those entry points have always launched: through the bit table the general path took
 // 0.7 % longer, outside the spread of two runs of the old code (profiles/rows_refactor_ab.txt).  The lists are the same bits either way
 // (tests/test_gpu_rows_filtered.py::test_no_filter_is_recommend_rows).
 // With an allow list the call first packs the allowed decoder rows (once, not per chunk; rebuilt by every call: the decoder can change
-// behind the library's back through cdae_hip_param_device_ptr), the sweeps run over the pack with a by-value copy of hp whose
-// num_items is n_allow, and the lists' places are mapped back to ids.  With targets every chunk's lists are scored on the device.
+// behind the library's back through cdae_hip_param_device_ptr), the sweep runs over the pack with a by-value copy of hp whose
+// num_items is n_allow, and the lists' places are mapped back to ids.  With targets every chunk's lists are scored by the TOPN hook.
 struct FilterArgs {
   const int64_t* excl_ptr = nullptr; const uint32_t* excl_col = nullptr; bool exclude_rated = true;
   const uint32_t* allow = nullptr; uint64_t n_allow = 0;
@@ -2820,6 +2835,24 @@ int validate_allow(const char* fn, const uint32_t* allow, uint64_t n_allow, uint
   }
   return 0;
 }
+// A call's filter to the device (on h->stream): the excl CSR over R rows; the allow list (d_flt_allow) and its inverse, item -> place
+// with 0xFFFFFFFF elsewhere (d_flt_pos) ...
+int filter_upload(cdae_hip* h, const FilterArgs& f, uint64_t R) {
+  if (f.excl_ptr) CHK(upload_csr(h, h->d_flt_eptr, h->d_flt_ecol, f.excl_ptr, f.excl_col, R));
+  if (!f.allow) return 0;
+  const uint32_t na = (uint32_t)f.n_allow;
+  CHK(h->d_flt_allow.ensure(na));
+  CHK(h->d_flt_pos.ensure(h->I));
+  HIPCHK(hipMemcpyAsync(h->d_flt_allow, f.allow, na * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(hipMemsetAsync(h->d_flt_pos, 0xFF, h->I * sizeof(uint32_t), h->stream));
+  hipLaunchKernelGGL(cdae::allow_pos_kernel, dim3((na + 255) / 256), dim3(256), 0, h->stream, (const uint32_t*)h->d_flt_allow, na, h->d_flt_pos.p);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+// ... and the mask it makes with the "rated" CSR (ptr, col), which is null where the call does not exclude those rows
+Mask filter_mask(const cdae_hip* h, const FilterArgs& f, const int64_t* ptr, const uint32_t* col) {
+  return Mask{Mask::FILTER, ptr, col, f.excl_ptr ? h->d_flt_eptr.p : nullptr, h->d_flt_ecol, f.allow ? h->d_flt_pos.p : nullptr};
+}
 int rows_run(cdae_hip* h, const RowsArgs& a, const FilterArgs& f = FilterArgs{}) {
   HIPCHK(hipSetDevice(h->device));
   CHK(join_aux(h));
@@ -2831,93 +2864,51 @@ int rows_run(cdae_hip* h, const RowsArgs& a, const FilterArgs& f = FilterArgs{})
     if (!h->d_rows_out) CHK(h->d_rows_out.alloc(16));
     HIPCHK(hipMemsetAsync(h->d_rows_out, 0, 16 * sizeof(double), h->stream));
   }
-  if (f.excl_ptr) CHK(upload_csr(h, h->d_flt_eptr, h->d_flt_ecol, f.excl_ptr, f.excl_col, R));
-  const uint64_t n = f.allow ? f.n_allow : h->I;                   // the index space of the sweep
-  SweepSrc src{h->hp, h->dec(), h->P(CDAE_P_BP)};
+  const TopnHook hook{h->d_rows_tptr, h->d_rows_tcol, (double)a.with_targets, h->d_rows_pu, h->d_rows_out};
+  CHK(filter_upload(h, f, R));
+  TopkSweep sweep(h, h->hp, h->dec(), h->P(CDAE_P_BP), a.topk, a.out_scores != nullptr, f.allow ? h->d_flt_allow.p : nullptr);
   if (f.allow) {
     const uint32_t na = (uint32_t)f.n_allow;
-    CHK(h->d_flt_allow.ensure(na));
-    CHK(h->d_flt_pos.ensure(h->I));
     CHK(h->d_flt_D.ensure(na, h->Kp));
     CHK(h->d_flt_bp.ensure(na));
-    HIPCHK(hipMemcpyAsync(h->d_flt_allow, f.allow, na * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemsetAsync(h->d_flt_pos, 0xFF, h->I * sizeof(uint32_t), h->stream));
-    hipLaunchKernelGGL(cdae::allow_pos_kernel, dim3((na + 255) / 256), dim3(256), 0, h->stream, (const uint32_t*)h->d_flt_allow, na, h->d_flt_pos.p);
     DISPATCH_NI(h->NI, cdae::pack_decoder_kernel, dim3((na + cdae::PACK_WAVES - 1) / cdae::PACK_WAVES), dim3(cdae::PACK_WAVES * cdae::WAVE), 0,
-                h->stream, (const uint32_t*)h->d_flt_allow, na, h->Kp, src.D, src.bp, h->d_flt_D.p, h->d_flt_bp.p);
+                h->stream, (const uint32_t*)h->d_flt_allow, na, h->Kp, sweep.D, sweep.bp, h->d_flt_D.p, h->d_flt_bp.p);
     HIPCHK(hipGetLastError());
-    src.hp.num_items = na; src.D = h->d_flt_D; src.bp = h->d_flt_bp;
+    sweep.hp.num_items = na; sweep.D = h->d_flt_D; sweep.bp = h->d_flt_bp;
   }
-  const uint32_t topk = a.topk;
-  const bool with_scores = a.out_scores != nullptr;
-  const bool mfma = mfma_path(h, topk);
   const bool csr_mask = f.exclude_rated && !f.excl_ptr && !f.allow;     // the mask is the rated CSR and nothing else
-  const uint32_t words = (uint32_t)((n + 31) / 32);
-  Scorer sc;
-  uint32_t UC = (uint32_t)std::min<uint64_t>(R, EVAL_CHUNK);
-  if (mfma) {
-    CHK(h->d_rec.ensure((size_t)UC * topk));
-    if (with_scores) CHK(h->d_rec_score.ensure((size_t)UC * topk));
-  } else {
-    CHK(sc.prepare(h, (uint32_t)std::min<uint64_t>(R, 4096u), topk, with_scores, n, !csr_mask));
-    UC = sc.chunk;
-  }
-  if (mfma || !csr_mask) CHK(h->d_bits.ensure((size_t)UC * words));
-  CHK(h->d_zeval.ensure(UC, h->Kp));
-  for (uint64_t c0 = 0; c0 < R; c0 += UC) {
-    const uint32_t nu = (uint32_t)std::min<uint64_t>(UC, R - c0);
+  CHK(sweep.prepare(h, (uint32_t)std::min<uint64_t>(R, sweep.mfma ? EVAL_CHUNK : 4096u), csr_mask ? Mask::CSR : Mask::FILTER));
+  CHK(h->d_zeval.ensure(sweep.chunk, h->Kp));
+  const Mask mask = csr_mask ? Mask{Mask::CSR, h->d_rows_ptr, h->d_rows_col}
+                             : filter_mask(h, f, f.exclude_rated ? h->d_rows_ptr.p : nullptr, h->d_rows_col);
+  for (uint64_t c0 = 0; c0 < R; c0 += sweep.chunk) {
+    const uint32_t nu = (uint32_t)std::min<uint64_t>(sweep.chunk, R - c0);
     CHK(rows_encode_chunk(h, a.row_ptr, c0, nu));
-    if (!csr_mask)
-      hipLaunchKernelGGL(cdae::filter_bits_kernel, dim3((nu + 3) / 4), dim3(256), 0, h->stream,
-                         f.exclude_rated ? (const int64_t*)h->d_rows_ptr : (const int64_t*)nullptr, (const uint32_t*)h->d_rows_col,
-                         f.excl_ptr ? (const int64_t*)h->d_flt_eptr : (const int64_t*)nullptr, (const uint32_t*)h->d_flt_ecol,
-                         f.allow ? (const uint32_t*)h->d_flt_pos : (const uint32_t*)nullptr, c0, nu, words, h->d_bits.p);
-    else if (mfma)
-      hipLaunchKernelGGL(cdae::rated_bits_kernel, dim3((nu + 3) / 4), dim3(256), 0, h->stream, (const int64_t*)h->d_rows_ptr,
-                         (const uint32_t*)h->d_rows_col, c0, nu, words, h->d_bits.p);
-    if (mfma) CHK(launch_recommend_mfma(h, h->d_zeval, nu, words, topk, with_scores ? h->d_rec_score.p : nullptr, f.allow ? &src : nullptr));
-    else if (csr_mask) sc.launch(h, c0, nu, h->d_zeval, nullptr, 0, h->d_rows_ptr, h->d_rows_col);
-    else sc.launch_bits(h, src.hp, nu, h->d_zeval, src.D, src.bp, h->d_bits, words);
-    if (f.allow)
-      hipLaunchKernelGGL(cdae::remap_ids_kernel, dim3((uint32_t)(((size_t)nu * topk + 255) / 256)), dim3(256), 0, h->stream,
-                         (const uint32_t*)h->d_flt_allow, (size_t)nu * topk, h->d_rec.p);
-    HIPCHK(hipGetLastError());
-    if (a.t_ptr) {
-      hipLaunchKernelGGL(cdae::topn_user_kernel, dim3((nu + 255) / 256), dim3(256), 0, h->stream, (const uint32_t*)h->d_rec, topk, c0, nu,
-                         (const int64_t*)h->d_rows_tptr, (const uint32_t*)h->d_rows_tcol, (double)a.with_targets, h->d_rows_pu.p,
-                         reinterpret_cast<unsigned long long*>(h->d_rows_out + 8));
-      HIPCHK(hipGetLastError());
-    }
-    CHK(copy_lists_out(h, (size_t)nu * topk, a.out_ids ? a.out_ids + c0 * topk : nullptr, with_scores ? a.out_scores + c0 * topk : nullptr));
+    CHK(sweep.run(h, h->d_zeval, c0, nu, mask));
+    if (a.t_ptr) CHK(topn_chunk(h, hook, a.topk, c0, nu));
+    CHK(copy_lists_out(h, (size_t)nu * a.topk, a.out_ids ? a.out_ids + c0 * a.topk : nullptr, a.out_scores ? a.out_scores + c0 * a.topk : nullptr));
   }
   return 0;
 }
 
 // ---- top-k item neighbours (cdae_hip_similar_items) -----------------------------------------------------------------------------------
-// rows_run with the encoder replaced by a gather: the hidden row of query q is row q of the item table T (COSINE: divided by its norm),
+// The z-producer is a gather: the hidden row of query q is row q of the item table T (COSINE: divided by its norm),
 // the swept image is T itself (DOT without an allow list: in place), or the allowed and / or normalised rows gathered once per call
 // (rebuilt by every call: the parameters can change behind the library's back through cdae_hip_param_device_ptr), the bias is a buffer
-// of +0.0.  The mask is filter_bits_kernel's: its "rated" CSR is (0, 1, 2, ... ; query_items) when the query itself is excluded, its
-// excl CSR the caller's, its pos the allow list's inverse.  Both sweep kernels run as rows_run runs them with an allow list, and the
-// lists' places are mapped back to ids.  One host synchronisation per chunk.
+// of +0.0.  The mask is Mask::FILTER: its "rated" CSR is (0, 1, 2, ... ; query_items) when the query itself is excluded, its
+// excl CSR the caller's, its pos the allow list's inverse.  One host synchronisation per chunk.
 struct SimilarArgs {
   uint64_t n_queries; const uint32_t* query_items; const float* T; bool cosine, exclude_self;
   uint32_t topk; uint32_t* out_ids; float* out_scores;
 };
 // out[p] = row ids[p] (ids == nullptr: row p) of T for p < n, normalised when `cosine`
-template <int NI>
-void gather_rows_as(cdae_hip* h, bool cosine, const uint32_t* ids, uint32_t n, const float* T, float* out) {
-  const dim3 grid((n + cdae::PACK_WAVES - 1) / cdae::PACK_WAVES), block(cdae::PACK_WAVES * cdae::WAVE);
-  if (cosine) hipLaunchKernelGGL((cdae::gather_rows_kernel<NI, true>), grid, block, 0, h->stream, ids, n, h->Kp, T, out);
-  else hipLaunchKernelGGL((cdae::gather_rows_kernel<NI, false>), grid, block, 0, h->stream, ids, n, h->Kp, T, out);
-}
 void gather_rows(cdae_hip* h, bool cosine, const uint32_t* ids, uint32_t n, const float* T, float* out) {
-  switch (h->NI) {
-    case 1: gather_rows_as<1>(h, cosine, ids, n, T, out); break;
-    case 2: gather_rows_as<2>(h, cosine, ids, n, T, out); break;
-    case 4: gather_rows_as<4>(h, cosine, ids, n, T, out); break;
-    default: gather_rows_as<8>(h, cosine, ids, n, T, out); break;
-  }
+  const dim3 grid((n + cdae::PACK_WAVES - 1) / cdae::PACK_WAVES), block(cdae::PACK_WAVES * cdae::WAVE);
+  dispatch_ni(h->NI, [&](auto ni) {
+    constexpr int NI = decltype(ni)::value;
+    if (cosine) hipLaunchKernelGGL((cdae::gather_rows_kernel<NI, true>), grid, block, 0, h->stream, ids, n, h->Kp, T, out);
+    else hipLaunchKernelGGL((cdae::gather_rows_kernel<NI, false>), grid, block, 0, h->stream, ids, n, h->Kp, T, out);
+  });
 }
 int similar_run(cdae_hip* h, const SimilarArgs& a, const FilterArgs& f) {
   HIPCHK(hipSetDevice(h->device));
@@ -2929,55 +2920,27 @@ int similar_run(cdae_hip* h, const SimilarArgs& a, const FilterArgs& f) {
     CHK(h->d_sim_iota.ensure(Q + 1));
     hipLaunchKernelGGL(cdae::iota_ptr_kernel, dim3((uint32_t)((Q + 1 + 255) / 256)), dim3(256), 0, h->stream, (size_t)(Q + 1), h->d_sim_iota.p);
   }
-  if (f.excl_ptr) CHK(upload_csr(h, h->d_flt_eptr, h->d_flt_ecol, f.excl_ptr, f.excl_col, Q));
+  CHK(filter_upload(h, f, Q));
   const uint32_t n = (uint32_t)(f.allow ? f.n_allow : h->I);           // the index space of the sweep
-  if (f.allow) {
-    CHK(h->d_flt_allow.ensure(n));
-    CHK(h->d_flt_pos.ensure(h->I));
-    HIPCHK(hipMemcpyAsync(h->d_flt_allow, f.allow, (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemsetAsync(h->d_flt_pos, 0xFF, h->I * sizeof(uint32_t), h->stream));
-    hipLaunchKernelGGL(cdae::allow_pos_kernel, dim3((n + 255) / 256), dim3(256), 0, h->stream, (const uint32_t*)h->d_flt_allow, n, h->d_flt_pos.p);
-  }
   const bool grew = h->d_sim_zero.cap < n;
   CHK(h->d_sim_zero.ensure(n));
   if (grew) HIPCHK(hipMemsetAsync(h->d_sim_zero, 0, h->d_sim_zero.cap * sizeof(float), h->stream));
-  SweepSrc src{h->hp, a.T, h->d_sim_zero};
-  src.hp.num_items = n;
+  TopkSweep sweep(h, h->hp, a.T, h->d_sim_zero, a.topk, a.out_scores != nullptr, f.allow ? h->d_flt_allow.p : nullptr);
+  sweep.hp.num_items = n;
   if (a.cosine || f.allow) {                                           // the table image of this call
     CHK(h->d_sim_T.ensure(n, h->Kp));
-    gather_rows(h, a.cosine, f.allow ? (const uint32_t*)h->d_flt_allow : (const uint32_t*)nullptr, n, a.T, h->d_sim_T.p);
-    src.D = h->d_sim_T;
+    gather_rows(h, a.cosine, sweep.allow, n, a.T, h->d_sim_T.p);
+    sweep.D = h->d_sim_T;
   }
   HIPCHK(hipGetLastError());
-  const uint32_t topk = a.topk;
-  const bool with_scores = a.out_scores != nullptr;
-  const bool mfma = mfma_path(h, topk);
-  const uint32_t words = (n + 31) / 32;
-  Scorer sc;
-  uint32_t UC = (uint32_t)std::min<uint64_t>(Q, EVAL_CHUNK);
-  if (mfma) {
-    CHK(h->d_rec.ensure((size_t)UC * topk));
-    if (with_scores) CHK(h->d_rec_score.ensure((size_t)UC * topk));
-  } else {
-    CHK(sc.prepare(h, (uint32_t)std::min<uint64_t>(Q, 4096u), topk, with_scores, n, true));
-    UC = sc.chunk;
-  }
-  CHK(h->d_bits.ensure((size_t)UC * words));
-  CHK(h->d_zeval.ensure(UC, h->Kp));
-  for (uint64_t c0 = 0; c0 < Q; c0 += UC) {
-    const uint32_t nu = (uint32_t)std::min<uint64_t>(UC, Q - c0);
+  CHK(sweep.prepare(h, (uint32_t)std::min<uint64_t>(Q, sweep.mfma ? EVAL_CHUNK : 4096u), Mask::FILTER));
+  CHK(h->d_zeval.ensure(sweep.chunk, h->Kp));
+  const Mask mask = filter_mask(h, f, a.exclude_self ? h->d_sim_iota.p : nullptr, h->d_sim_q);
+  for (uint64_t c0 = 0; c0 < Q; c0 += sweep.chunk) {
+    const uint32_t nu = (uint32_t)std::min<uint64_t>(sweep.chunk, Q - c0);
     gather_rows(h, a.cosine, (const uint32_t*)h->d_sim_q + c0, nu, a.T, h->d_zeval.p);
-    hipLaunchKernelGGL(cdae::filter_bits_kernel, dim3((nu + 3) / 4), dim3(256), 0, h->stream,
-                       a.exclude_self ? (const int64_t*)h->d_sim_iota : (const int64_t*)nullptr, (const uint32_t*)h->d_sim_q,
-                       f.excl_ptr ? (const int64_t*)h->d_flt_eptr : (const int64_t*)nullptr, (const uint32_t*)h->d_flt_ecol,
-                       f.allow ? (const uint32_t*)h->d_flt_pos : (const uint32_t*)nullptr, c0, nu, words, h->d_bits.p);
-    if (mfma) CHK(launch_recommend_mfma(h, h->d_zeval, nu, words, topk, with_scores ? h->d_rec_score.p : nullptr, &src));
-    else sc.launch_bits(h, src.hp, nu, h->d_zeval, src.D, src.bp, h->d_bits, words);
-    if (f.allow)
-      hipLaunchKernelGGL(cdae::remap_ids_kernel, dim3((uint32_t)(((size_t)nu * topk + 255) / 256)), dim3(256), 0, h->stream,
-                         (const uint32_t*)h->d_flt_allow, (size_t)nu * topk, h->d_rec.p);
-    HIPCHK(hipGetLastError());
-    CHK(copy_lists_out(h, (size_t)nu * topk, a.out_ids + c0 * topk, with_scores ? a.out_scores + c0 * topk : nullptr));
+    CHK(sweep.run(h, h->d_zeval, c0, nu, mask));
+    CHK(copy_lists_out(h, (size_t)nu * a.topk, a.out_ids + c0 * a.topk, a.out_scores ? a.out_scores + c0 * a.topk : nullptr));
   }
   return 0;
 }
@@ -3059,7 +3022,7 @@ int score_run(cdae_hip* h, uint64_t R, const uint32_t* uids, const int64_t* row_
 
 // ---- exact full-catalogue ranks of named items (cdae_hip_full_rank_rows) -----------------------------------------------------------
 namespace {
-// Chunks: real rows as for the other rows entry points (EVAL_CHUNK on the matrix cores, the Scorer's bounds on the general path), and
+// Chunks: real rows as for the other rows entry points (EVAL_CHUNK on the matrix cores, score_place's bound on the general path), and
 // closed early once they hold FR_TARGET_CHUNK targets, which bounds the per-chunk score / rank buffers (one row may still name every
 // unrated item: a chunk always takes at least one row).  Matrix-core path: a row with n targets is ceil(n / FR_WINDOW) virtual rows in
 // the call's table, and one counting launch takes at most FR_COLS_MAX of them — a row with more is cut across launches that share its z.
@@ -3138,7 +3101,8 @@ int full_rank_run(cdae_hip* h, uint64_t R, const uint32_t* uids, const int64_t* 
     HIPCHK(hipMemcpyAsync(h->d_fr_vrows, h->h_fr_vrows.data(), h->h_fr_vrows.size() * sizeof(uint2), hipMemcpyHostToDevice, h->stream));
   } else {
     if (!sp.in_lds) CHK(h->d_score.ensure(rows_cap * h->I));
-    HIPCHK(hipFuncSetAttribute(KERNEL_OF_NI(h->NI, cdae::full_rank_general_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sp.shmem));
+    const void* kernel = dispatch_ni(h->NI, [](auto ni) { return (const void*)cdae::full_rank_general_kernel<decltype(ni)::value>; });
+    HIPCHK(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sp.shmem));
   }
   for (const FrChunk& c : chunks) {
     if (c.p1 == c.p0) continue;                                    // no row of the chunk has targets: nothing to launch, nothing to write
@@ -3387,22 +3351,16 @@ int als_gram(cdae_hip* h, const float* T, uint64_t rows) {
   return 0;
 }
 // n rows of the CSR (ptr, col) solved against the table Y and h->d_als_G, 32 rows per workgroup
-template <int NI>
-int als_solve_as(cdae_hip* h, const int64_t* ptr, const uint32_t* col, uint64_t n, const float* Y, const float* x0, float* dst, uint32_t steps) {
-  constexpr size_t lds = cdae::als_solve_lds_bytes<NI>();
-  HIPCHK(hipFuncSetAttribute((const void*)cdae::als_solve_kernel<NI>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  hipLaunchKernelGGL((cdae::als_solve_kernel<NI>), dim3((uint32_t)((n + cdae::ALS_BLOCK_ROWS - 1) / cdae::ALS_BLOCK_ROWS)), dim3(cdae::als_waves<NI>() * 64), lds,
-                     h->stream, ptr, col, n, Y, (const float*)h->d_als_G, x0, dst, h->als_alpha, h->als_lambda, steps);
-  HIPCHK(hipGetLastError());
-  return 0;
-}
 int als_solve(cdae_hip* h, const int64_t* ptr, const uint32_t* col, uint64_t n, const float* Y, const float* x0, float* dst, uint32_t steps) {
-  switch (h->NI) {
-    case 1: return als_solve_as<1>(h, ptr, col, n, Y, x0, dst, steps);
-    case 2: return als_solve_as<2>(h, ptr, col, n, Y, x0, dst, steps);
-    case 4: return als_solve_as<4>(h, ptr, col, n, Y, x0, dst, steps);
-    default: return als_solve_as<8>(h, ptr, col, n, Y, x0, dst, steps);
-  }
+  return dispatch_ni(h->NI, [&](auto ni) {
+    constexpr int NI = decltype(ni)::value;
+    constexpr size_t lds = cdae::als_solve_lds_bytes<NI>();
+    HIPCHK(hipFuncSetAttribute((const void*)cdae::als_solve_kernel<NI>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL((cdae::als_solve_kernel<NI>), dim3((uint32_t)((n + cdae::ALS_BLOCK_ROWS - 1) / cdae::ALS_BLOCK_ROWS)), dim3(cdae::als_waves<NI>() * 64), lds,
+                       h->stream, ptr, col, n, Y, (const float*)h->d_als_G, x0, dst, h->als_alpha, h->als_lambda, steps);
+    HIPCHK(hipGetLastError());
+    return 0;
+  });
 }
 int als_check(cdae_hip* h, const char* fn) {
   if (!h) return fail("%s: null handle", fn);
@@ -3960,12 +3918,12 @@ int ev_data_loss(cdae_hip_t* h, uint64_t u0, uint32_t nu, double* sum) {
 int ev_recommend(cdae_hip_t* h, uint64_t u0, uint32_t nu, uint32_t topk, uint32_t* ids, float* scores) {
   HIPCHK(hipSetDevice(h->device));
   if (topk == 0 || topk > h->I) return fail("topk %u exceeds the %llu items of this shard", topk, (unsigned long long)h->I);
-  Scorer sc;
-  CHK(sc.prepare(h, nu, topk, true));
-  for (uint32_t c0 = 0; c0 < nu; c0 += sc.chunk) {
-    const uint32_t nb = std::min(sc.chunk, nu - c0);
-    sc.launch(h, u0 + c0, nb, h->d_zeval + (size_t)c0 * h->Kp);
-    HIPCHK(hipGetLastError());
+  TopkSweep sweep(h, h->hp, h->dec(), h->P(CDAE_P_BP), topk, true, nullptr, false);      // (an item shard: the general path)
+  CHK(sweep.prepare(h, nu, Mask::CSR));
+  const Mask mask{Mask::CSR, h->d_row_ptr, h->d_col};
+  for (uint32_t c0 = 0; c0 < nu; c0 += sweep.chunk) {
+    const uint32_t nb = std::min(sweep.chunk, nu - c0);
+    CHK(sweep.run(h, h->d_zeval + (size_t)c0 * h->Kp, u0 + c0, nb, mask));
     CHK(copy_lists_out(h, (size_t)nb * topk, ids + (size_t)c0 * topk, scores + (size_t)c0 * topk));
   }
   return 0;
