@@ -33,6 +33,8 @@ BPR_DEFAULT_BATCH_USERS = 8    # with batch_users = 0 trains on a BASELINE-sized
 RANK_CANDIDATES_MAX = 4096     # CDAE_RANK_CANDIDATES_MAX (include/cdae_hip.h): candidates per row that score_rows ranks
 NO_USER = 0xFFFFFFFF           # CDAE_NO_USER (include/cdae_hip.h): a row of recommend_rows / eval_topn_rows without a user node
 ALS_USERS, ALS_ITEMS = 0, 1         # CDAE_ALS_USERS / CDAE_ALS_ITEMS: the side a WRMF half-step solves
+WARP_MAX_TRY = 500                  # CDAE_WARP_MAX_TRY (include/cdae_hip.h): draws of one WARP search; cnt == WARP_MAX_TRY: exhausted
+WARP_NONE = 0xFFFFFFFF              # the item of an exhausted search
 ITEMS_OUTPUT, ITEMS_INPUT = 0, 1   # CDAE_ITEMS_OUTPUT / CDAE_ITEMS_INPUT (include/cdae_hip.h): the item table similar_items compares rows of
 SIM_DOT, SIM_COSINE = 0, 1         # CDAE_SIM_DOT / CDAE_SIM_COSINE (include/cdae_hip.h): its score
 DEFAULT_BATCH_USERS = 0        # 0 = the library's default (cdae_hip_default_batch_users: num_users / 160, within [32, 256])
@@ -63,6 +65,11 @@ class _AlsConfig(C.Structure):
     _fields_ = [(n, C.c_uint32) for n in ("struct_size", "num_dim", "cg_steps", "reserved")] + [(n, C.c_double) for n in ("lambda_", "alpha")]
 
 
+class _WarpConfig(C.Structure):
+    _fields_ = [(n, C.c_uint32) for n in ("struct_size", "num_dim", "num_neg", "loss_type", "using_adagrad", "batch_users")] + [
+        (n, C.c_double) for n in ("lambda_", "learn_rate")]
+
+
 class Stats(C.Structure):
     _fields_ = [("wall_seconds", C.c_double), ("users", C.c_uint64), ("examples", C.c_uint64),
                 ("batches", C.c_uint64), ("ms_sample", C.c_double), ("ms_sort", C.c_double),
@@ -83,6 +90,10 @@ EXPORTS = {
     "cdae_hip_als_half_step": (C.c_int, [C.c_void_p, C.c_uint32]),
     "cdae_hip_als_solve_rows": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
     "cdae_hip_als_gram": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t]),
+    "cdae_hip_create_warp": (C.c_int, [C.POINTER(_WarpConfig), C.c_int, C.POINTER(C.c_void_p)]),
+    "cdae_hip_warp_search": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]),
+    "cdae_hip_warp_record_choices": (C.c_int, [C.c_void_p, C.c_uint32]),
+    "cdae_hip_warp_choices": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]),
     "cdae_hip_destroy": (C.c_int, [C.c_void_p]),
     "cdae_hip_set_interactions": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p]),
     "cdae_hip_row_stride": (C.c_uint32, [C.c_void_p]),
@@ -787,6 +798,67 @@ class WRMF(MF):
         _chk(self.lib, self.lib.cdae_hip_als_solve_rows(self.h, n, rp.ctypes.data, rc.ctypes.data, None if a is None else a.ctypes.data,
                                                         cg_steps, out.ctypes.data))
         return out
+
+
+@dataclass
+class WARPConfig:
+    """libcf::WARPConfig (the reference's src/model/recsys/warp.hpp:12-23) with its defaults; beta and using_bias_term are accepted as the
+    reference accepts them and change nothing (warp.hpp never reads beta; the bias steps are comments).  batch_users is not in the
+    reference: 1 (and 0) is its loop, above 1 the block schedule — no block size has been measured for accuracy."""
+    learn_rate: float = 0.1
+    beta: float = 0.0
+    lambda_: float = 0.1
+    lt: int = HINGE
+    num_dim: int = 10
+    num_neg: int = 5
+    using_bias_term: bool = True
+    using_adagrad: bool = True
+    batch_users: int = 1
+
+
+class WARP(MF):
+    """Rank-weighted pairwise matrix factorisation whose negatives are searched for on the device (cdae_hip_create_warp; include/cdae_hip.h
+    has the definition).  The factors and biases live where IMF's do; recommend_all, eval_topn and similar_items are MF's."""
+
+    def __init__(self, mcfg: WARPConfig, device: int = 0):
+        self.lib = load_library()
+        self.cfg = mcfg
+        c = _WarpConfig(C.sizeof(_WarpConfig), mcfg.num_dim, mcfg.num_neg, mcfg.lt, int(mcfg.using_adagrad), mcfg.batch_users,
+                        mcfg.lambda_, mcfg.learn_rate)
+        self.h = C.c_void_p()
+        _chk(self.lib, self.lib.cdae_hip_create_warp(C.byref(c), device, C.byref(self.h)))
+        self.num_users = self.num_items = 0
+        self._rec = None
+
+    def _pairs(self, pos_begin: int, pos_end: int) -> int:
+        lens = np.diff(self._row_ptr)[self.user_order().astype(np.int64)]
+        return int(lens[pos_begin:pos_end].sum()) * self.cfg.num_neg
+
+    def search(self, seed: int, epoch: int, pos_begin: int = 0, pos_end: int | None = None, with_margin: bool = False):
+        """The search of every (position, positive, k) of training positions [pos_begin, pos_end) against the current parameters; nothing
+        is trained.  -> (item, cnt[, margin]) indexed by (row offset of the positive in the range) * num_neg + k; cnt == WARP_MAX_TRY
+        and item == WARP_NONE: exhausted."""
+        pos_end = self.num_users if pos_end is None else pos_end
+        n = self._pairs(pos_begin, pos_end) if 0 <= pos_begin <= pos_end <= self.num_users else 0
+        item, cnt = np.empty(n, dtype=np.uint32), np.empty(n, dtype=np.uint32)
+        margin = np.empty(n, dtype=np.float32) if with_margin else None
+        _chk(self.lib, self.lib.cdae_hip_warp_search(self.h, seed, epoch, pos_begin, pos_end, item.ctypes.data, cnt.ctypes.data,
+                                                     None if margin is None else margin.ctypes.data, n))
+        return (item, cnt, margin) if with_margin else (item, cnt)
+
+    def record_choices(self, on):
+        """on: every training call leaves the (item, cnt) of every pair of the users it trained (choices())"""
+        _chk(self.lib, self.lib.cdae_hip_warp_record_choices(self.h, int(bool(on))))
+
+    def choices(self):
+        """-> (item, cnt) of every pair, [nnz * num_neg] in position order, as the last training calls left them"""
+        n = self._pairs(0, self.num_users)
+        item, cnt = np.empty(n, dtype=np.uint32), np.empty(n, dtype=np.uint32)
+        _chk(self.lib, self.lib.cdae_hip_warp_choices(self.h, item.ctypes.data, cnt.ctypes.data, n))
+        return item, cnt
+
+    def _batch_examples(self, u_begin: int, n_users: int) -> int:
+        return 2 * self._pairs(u_begin, u_begin + n_users)
 
 
 def comm_unique_id() -> bytes:

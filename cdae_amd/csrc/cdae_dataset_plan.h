@@ -274,7 +274,7 @@ struct Args {
   uint64_t U = 0, I = 0;
   const int64_t* row_ptr = nullptr; const uint32_t* col = nullptr;
   const int64_t* whole_row_ptr = nullptr;   // sampled item shard: row_ptr of the WHOLE rows (else unused)
-  uint32_t kind = 0;                        // cdae_hip::mf: 0 CDAE, 1 IMF, 2 BPR, 3 WRMF
+  uint32_t kind = 0;                        // cdae_hip::mf: 0 CDAE, 1 IMF, 2 BPR, 3 WRMF, 4 WARP (sized as BPR with one more sort key: VOID = I)
   bool mf_seq = false, full_output = false, asymmetric = false, item_shard = false;
   uint32_t batch_users = 0;                 // cdae_hip::B, the default already resolved
   uint32_t K = 0, Kp = 0, num_neg = 0;      // num_neg: HyperParams::num_neg (0 for full output)
@@ -339,7 +339,8 @@ inline std::string build(const Args& a, Plan& p) {
   }
   // batch workspace sized for the largest batch of B consecutive users
   p.emax = window_max(p.row_ptr, U, B);
-  p.ex_per_pos = a.kind == 2 ? 2u * a.num_neg : 1u + a.num_neg;
+  const bool pairs = a.kind == 2u || a.kind == 4u;      // two examples per (positive, k)
+  p.ex_per_pos = pairs ? 2u * a.num_neg : 1u + a.num_neg;
   p.Ecap = p.emax * p.ex_per_pos;
   if (shard_sampled) {
     // the example list of a batch is the single-GPU one (every position of the WHOLE rows, every negative draw), entries of other
@@ -349,12 +350,13 @@ inline std::string build(const Args& a, Plan& p) {
     p.gunit_user = unit_owners(p.gunit_ptr);
   }
   if (p.Ecap > 0xFFFFFFF0ull) return refuse("batch of %u users holds %llu examples (> 2^32); lower batch_users", B, (unsigned long long)p.Ecap);
-  const uint64_t keys = I + (shard_sampled ? 1u : 0u);
-  p.counting_sort = I <= TILE_SORT_MAX_ITEMS && a.sort_tile;
+  const uint64_t keys = I + (shard_sampled || a.kind == 4u ? 1u : 0u);     // (WARP: a skipped pair's two examples carry the VOID key I)
+  p.counting_sort = I <= TILE_SORT_MAX_ITEMS && a.sort_tile && a.kind != 4u;
   p.bucket = bucket_cuts(U, I, B, keys, p.Ecap, bucket_max_examples(a.full_output), (double)(shard_sampled ? a.I_global : I),
                          shard_sampled ? (double)a.whole_row_ptr[U] : (double)nnz,
-                         a.kind == 2 ? 2u * a.num_neg : a.num_neg,      // (BPR lists the positive once per pair too: weights only balance, any estimate is legal)
-                         p.pop, !p.counting_sort && !a.mf_seq && !a.sort_library, !a.kind && !a.sort_scan);
+                         pairs ? 2u * a.num_neg : a.num_neg,      // (BPR lists the positive once per pair too: weights only balance, any estimate is legal)
+                         p.pop, !p.counting_sort && !a.mf_seq && !a.sort_library && a.kind != 4u /* WARP orders its lists after phase U: the library sort */,
+                         !a.kind && !a.sort_scan);
   p.unit_ptr = unit_prefix(p.row_ptr, U, p.unit_pos);
   p.unit_user = unit_owners(p.unit_ptr);
   p.unit_cap = (uint32_t)std::max(window_max(p.unit_ptr.data(), U, B), encode_unit_bound(p.unit_ptr, B));

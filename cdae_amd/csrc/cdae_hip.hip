@@ -37,6 +37,7 @@
 #include "cdae_sort_kernels.hpp"
 #include "cdae_mf_kernels.hpp"
 #include "cdae_als_kernels.hpp"
+#include "cdae_warp_kernels.hpp"
 
 #ifdef CDAE_DECODE_TIMING
 #define CDAE_TOUCHED_ARG ((uint32_t*)nullptr)     // the timing build borrows `touched` for its stamps
@@ -293,6 +294,12 @@ struct cdae_hip {
   DevBuf<int64_t> d_tptr; DevBuf<uint32_t> d_tcol;
   DevBuf<float> d_als_G, d_als_part, d_als_x, d_als_out;
   uint32_t als_steps = 0; float als_alpha = 0.f, als_lambda = 0.f;
+  // WARP handles (cdae_hip_create_warp, cdae_warp_kernels.hpp): the rank weights l[num_items] (cdae_warp_host.h, filled per data set); the
+  // record of the last training calls' choices, [nnz * num_neg] by position, allocated by the first cdae_hip_warp_record_choices(1) and
+  // dropped with the data set; the outputs of one chunk of cdae_hip_warp_search (grow-only)
+  DevBuf<float> d_warp_l, d_warp_out_margin;
+  DevBuf<uint32_t> d_warp_rec_item, d_warp_rec_cnt, d_warp_out_item, d_warp_out_cnt;
+  bool warp_record = false;
   // Guest table (cdae_hip_set_guest_nodes, cdae_hip_fold_in_rows with install): a second user table, rows wu | wu_ag | uu | uu_ag of
   // [n_guests x Kp] each, that the rows entry points address as CDAE_GUEST_USER(i).  d_fold: the staging rows the fold-in kernel writes
   // (a chunk's, or the whole call's when it installs); installing EXCHANGES the two sets, so a failed call leaves the table as it was.
@@ -346,7 +353,8 @@ struct cdae_hip {
   void* xchg = nullptr; void (*xchg_free)(void*) = nullptr;   // communicator + schedule of the exchange (cdae_multi.hip)
   uint32_t delta_combine = CDAE_COMBINE_SUM;                  // cdae_hip_delta_set_combine: how staged deltas are folded in (cdae_exchange_algebra.h)
   // IMF / BPR handles (cdae_hip_create_mf, cdae_mf_kernels.hpp): 0 = CDAE, 1 = IMF, 2 = BPR; 3 = WRMF by ALS (cdae_hip_create_als):
-  // IMF's tables and serving, no sampled step — every training path that asks `mf == 2 ? BPR : IMF` is refused before it is reached
+  // IMF's tables and serving, no sampled step — every training path that asks `mf == 2 ? BPR : IMF` is refused before it is reached;
+  // 4 = WARP (cdae_hip_create_warp): IMF's tables and serving, BPR's batch workspace, its own step (compute_batch_warp)
   uint32_t mf = 0, mf_bias = 1;
   // IMF / BPR, batch_users = 1 (the library default: the reference's strictly sequential loop): the users are still taken one after the
   // other and every instance still steps the user vector and the item row(s) in place — but LAUNCHES cover MF_SEQ_USERS users: one
@@ -553,7 +561,8 @@ template <class F> void visit_data_set_bufs(cdae_hip* h, F&& f) {
     h->d_flt_eptr, h->d_flt_ecol, h->d_flt_allow, h->d_flt_pos, h->d_flt_D, h->d_flt_bp,
     h->d_sim_q, h->d_sim_iota, h->d_sim_T, h->d_sim_zero,
     h->d_guest[0], h->d_guest[1], h->d_guest[2], h->d_guest[3], h->d_fold[0], h->d_fold[1], h->d_fold[2], h->d_fold[3],
-    h->d_fold_long, h->d_als_G, h->d_als_part, h->d_als_x, h->d_als_out);
+    h->d_fold_long, h->d_als_G, h->d_als_part, h->d_als_x, h->d_als_out,
+    h->d_warp_l, h->d_warp_rec_item, h->d_warp_rec_cnt, h->d_warp_out_item, h->d_warp_out_cnt, h->d_warp_out_margin);
 }
 // Drops every one of them; the first release error is returned after all have been dropped.
 int drop_data_set_bufs(cdae_hip* h) {
@@ -595,6 +604,7 @@ int free_interaction_state(cdae_hip* h) {
   CHK(drop_data_set_bufs(h));
   h->db_valid = false; h->db_rows_valid = false; h->zb_rows = 0xFFFFFFFFu;
   h->n_guests = 0;
+  h->warp_record = false;
   return 0;
 }
 
@@ -613,6 +623,63 @@ inline bool packs_rows(const cdae_hip* h) { return h->row_pack && h->K <= 256 &&
 // ... and the batches of such a handle that have one: every batch prep_batch ordered (an explicit input set is ordered by its caller)
 inline cdae::RowRecord* pack_of(const cdae_hip* h, const cdae_hip::ExBuf& x, uint64_t E) { return packs_rows(h) && E > 0 ? x.pack.p : nullptr; }
 
+// The item-major order of a batch's example list: x.item / x.val (or the 16-bit keys, or the sample kernel's cells) into x.sorted_val and
+// the segment tables.  prep_batch calls it on a prep stream behind the sampling launch; a WARP handle, whose lists exist only after
+// phase U, on the training stream (compute_batch_warp) — it takes the library sort on the 32-bit keys, VOID key included.
+// void_key: the key of examples that belong to no row of this handle (sorted last: no segment, no duplicate marks), or 0xFFFFFFFF
+int order_examples(cdae_hip* h, cdae_hip::ExBuf& x, uint64_t E, hipStream_t st, void* sort_tmp, uint32_t n_units, bool bucket, bool use_cells,
+                   uint32_t void_key) {
+  using namespace cdae;
+  const uint32_t I = (uint32_t)h->I;
+  const dim3 seg_grid((uint32_t)((E + 256 * SEG_PER_THREAD - 1) / (256 * SEG_PER_THREAD)));
+  if (E == 0) {
+    // nothing to order
+  } else if (h->mf_seq && !h->prep_force_sort) {
+    // the in-place loop reads the user-major list only: no item-major order, no segment table
+  } else if (bucket) {
+    // item-major order, segment tables, duplicate marks: ONE narrow launch (cdae_sort_kernels.hpp bucket_sort_kernel)
+    if (!h->bucket_attr_set) {
+      HIPCHK(hipFuncSetAttribute((const void*)bucket_sort_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)BK_LDS_BYTES));
+      h->bucket_attr_set = true;
+    }
+    hipLaunchKernelGGL(bucket_sort_kernel, dim3(h->bucket_ranges), dim3(BK_THREADS), BK_LDS_BYTES, st, (const uint16_t*)x.key16, (const uint64_t*)x.val,
+                       (uint32_t)E, (const uint32_t*)h->d_bucket_cut, x.wg_state, (const uint32_t*)(use_cells ? x.cells.p : nullptr), n_units,
+                       (const uint32_t*)x.cell_flag, x.cell_tag, x.seg, x.seg + I, (const uint32_t*)h->d_rank_of,
+                       x.seg + 2 * (size_t)I, x.seg + 3 * (size_t)I, x.sorted_val, x.bucketed, x.dup_count, h->dup_cap, x.dup_of_pos, x.dup_of_ex,
+                       h->dup_stripes, h->d_fused_err);
+  } else if (h->counting_sort) {
+    // item-major order by counting, four launches (cdae_sort_kernels.hpp)
+    const uint32_t n_tiles = (uint32_t)((E + TILE_EX - 1) / TILE_EX);
+    const size_t tile_lds = (size_t)I * sizeof(uint32_t);
+    if (tile_lds + 1024 > 64 * 1024 && !h->tile_attr_set) {
+      HIPCHK(hipFuncSetAttribute((const void*)tile_hist_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)tile_lds));
+      HIPCHK(hipFuncSetAttribute((const void*)tile_scatter_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)tile_lds + 1024));
+      h->tile_attr_set = true;
+    }
+    hipLaunchKernelGGL(tile_hist_kernel, dim3(n_tiles), dim3(TILE_THREADS), tile_lds / 2 + 4, st, x.item, (uint32_t)E, I, x.tile_hist);
+    hipLaunchKernelGGL(item_tile_scan_kernel, dim3((I + 255) / 256), dim3(256), 0, st, x.tile_hist, n_tiles, I, x.item_count, x.rank, x.block_total);
+    hipLaunchKernelGGL(tile_scatter_kernel, dim3(n_tiles), dim3(TILE_THREADS), tile_lds + 128 * sizeof(uint32_t), st, x.item, x.val,
+                       (uint32_t)E, I, x.tile_hist, x.item_count, x.rank, x.block_total, x.prefix, x.seg, x.seg + I, x.dup_count, x.bucketed,
+                       (const uint32_t*)h->d_rank_of, x.seg + 2 * (size_t)I, x.seg + 3 * (size_t)I);
+    hipLaunchKernelGGL(segment_sort_kernel, dim3((I + SEGSORT_ITEMS - 1) / SEGSORT_ITEMS), dim3(SEGSORT_THREADS), 0, st, I, x.prefix, x.bucketed,
+                       x.sorted_val, x.item_count, x.dup_count, h->dup_cap, x.dup_of_pos, x.dup_of_ex, h->dup_stripes);
+  } else if (x.key16) {
+    // 16-bit keys: rocPRIM picks onesweep (2 digit passes) instead of block sort + log2(tiles) merge passes
+    HIPCHK(rocprim::radix_sort_pairs(sort_tmp, h->sort_tmp_bytes, x.key16.p, x.sorted_key16.p, x.val.p, x.sorted_val.p,
+                                     (size_t)E, 0u, (unsigned)h->sort_bits, st));
+    hipLaunchKernelGGL(segment_kernel<uint16_t>, seg_grid, dim3(256), 0, st, x.sorted_key16, x.sorted_val, (uint32_t)E,
+                       x.seg, x.seg + I, x.dup_count, h->dup_cap, x.dup_of_pos, x.dup_of_ex, h->dup_stripes,
+                       (const uint32_t*)h->d_rank_of, x.seg + 2 * (size_t)I, x.seg + 3 * (size_t)I, void_key);
+  } else {
+    HIPCHK(rocprim::radix_sort_pairs(sort_tmp, h->sort_tmp_bytes, x.item.p, x.sorted_item.p, x.val.p, x.sorted_val.p,
+                                     (size_t)E, 0u, (unsigned)h->sort_bits, st));
+    hipLaunchKernelGGL(segment_kernel<uint32_t>, seg_grid, dim3(256), 0, st, x.sorted_item, x.sorted_val, (uint32_t)E,
+                       x.seg, x.seg + I, x.dup_count, h->dup_cap, x.dup_of_pos, x.dup_of_ex, h->dup_stripes,
+                       (const uint32_t*)h->d_rank_of, x.seg + 2 * (size_t)I, x.seg + 3 * (size_t)I, void_key);
+  }
+  return 0;
+}
+
 // K1 + sort on the prep stream into example-buffer set `b`
 // lane 1: the second prep stream with the second half of the sort workspace (two batches are prepared side by side)
 int prep_batch(cdae_hip* h, int b, const Batch& bt, uint64_t seed, uint32_t epoch, int lane = 0, uint64_t prof_q = ~0ull) {
@@ -623,6 +690,16 @@ int prep_batch(cdae_hip* h, int b, const Batch& bt, uint64_t seed, uint32_t epoc
   const uint32_t I = (uint32_t)h->I;
   Prof pr;
   HIPCHK(hipStreamWaitEvent(st, x.released, 0));               // the batch that last used this set is done with it
+  if (h->mf == 4u) {
+    // WARP: nothing to draw — the items of a pair are chosen in phase U (warp_user_kernel) and ordered behind it on the training
+    // stream (compute_batch_warp).  Only the per-batch clears of the block schedule: the by-item segment tables, the duplicate counters
+    if (!h->mf_seq) {
+      HIPCHK(hipMemsetAsync(x.seg, 0, 2 * (size_t)I * sizeof(uint32_t), st));
+      HIPCHK(hipMemsetAsync(x.dup_count, 0, cdae::DUP_STRIPES * sizeof(uint32_t), st));
+    }
+    HIPCHK(hipEventRecord(x.ready, st));
+    return 0;
+  }
   CHK(pr.begin(h, F_SAMPLE, st, prof_q));
   const bool shs = h->shard_sampled();
   const uint32_t n_units = shs ? gunits_of(h, bt) : units_of(h, bt);
@@ -653,52 +730,7 @@ int prep_batch(cdae_hip* h, int b, const Batch& bt, uint64_t seed, uint32_t epoc
                      use_cells ? x.cells : (uint32_t*)nullptr, x.cell_flag, x.cell_tag);
   CHK(pr.end());
   CHK(pr.begin(h, F_SORT, st, prof_q));
-  const dim3 seg_grid((uint32_t)((bt.E + 256 * SEG_PER_THREAD - 1) / (256 * SEG_PER_THREAD)));
-  if (bt.E == 0) {
-    // nothing to order
-  } else if (h->mf_seq && !h->prep_force_sort) {
-    // the in-place loop reads the user-major list only: no item-major order, no segment table
-  } else if (bucket) {
-    // item-major order, segment tables, duplicate marks: ONE narrow launch (cdae_sort_kernels.hpp bucket_sort_kernel)
-    if (!h->bucket_attr_set) {
-      HIPCHK(hipFuncSetAttribute((const void*)bucket_sort_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)BK_LDS_BYTES));
-      h->bucket_attr_set = true;
-    }
-    hipLaunchKernelGGL(bucket_sort_kernel, dim3(h->bucket_ranges), dim3(BK_THREADS), BK_LDS_BYTES, st, (const uint16_t*)x.key16, (const uint64_t*)x.val,
-                       (uint32_t)bt.E, (const uint32_t*)h->d_bucket_cut, x.wg_state, (const uint32_t*)(use_cells ? x.cells.p : nullptr), n_units,
-                       (const uint32_t*)x.cell_flag, x.cell_tag, x.seg, x.seg + I, (const uint32_t*)h->d_rank_of,
-                       x.seg + 2 * (size_t)I, x.seg + 3 * (size_t)I, x.sorted_val, x.bucketed, x.dup_count, h->dup_cap, x.dup_of_pos, x.dup_of_ex,
-                       h->dup_stripes, h->d_fused_err);
-  } else if (h->counting_sort) {
-    // item-major order by counting, four launches (cdae_sort_kernels.hpp)
-    const uint32_t n_tiles = (uint32_t)((bt.E + TILE_EX - 1) / TILE_EX);
-    const size_t tile_lds = (size_t)I * sizeof(uint32_t);
-    if (tile_lds + 1024 > 64 * 1024 && !h->tile_attr_set) {
-      HIPCHK(hipFuncSetAttribute((const void*)tile_hist_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)tile_lds));
-      HIPCHK(hipFuncSetAttribute((const void*)tile_scatter_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)tile_lds + 1024));
-      h->tile_attr_set = true;
-    }
-    hipLaunchKernelGGL(tile_hist_kernel, dim3(n_tiles), dim3(TILE_THREADS), tile_lds / 2 + 4, st, x.item, (uint32_t)bt.E, I, x.tile_hist);
-    hipLaunchKernelGGL(item_tile_scan_kernel, dim3((I + 255) / 256), dim3(256), 0, st, x.tile_hist, n_tiles, I, x.item_count, x.rank, x.block_total);
-    hipLaunchKernelGGL(tile_scatter_kernel, dim3(n_tiles), dim3(TILE_THREADS), tile_lds + 128 * sizeof(uint32_t), st, x.item, x.val,
-                       (uint32_t)bt.E, I, x.tile_hist, x.item_count, x.rank, x.block_total, x.prefix, x.seg, x.seg + I, x.dup_count, x.bucketed,
-                       (const uint32_t*)h->d_rank_of, x.seg + 2 * (size_t)I, x.seg + 3 * (size_t)I);
-    hipLaunchKernelGGL(segment_sort_kernel, dim3((I + SEGSORT_ITEMS - 1) / SEGSORT_ITEMS), dim3(SEGSORT_THREADS), 0, st, I, x.prefix, x.bucketed,
-                       x.sorted_val, x.item_count, x.dup_count, h->dup_cap, x.dup_of_pos, x.dup_of_ex, h->dup_stripes);
-  } else if (x.key16) {
-    // 16-bit keys: rocPRIM picks onesweep (2 digit passes) instead of block sort + log2(tiles) merge passes
-    HIPCHK(rocprim::radix_sort_pairs(sort_tmp, h->sort_tmp_bytes, x.key16.p, x.sorted_key16.p, x.val.p, x.sorted_val.p,
-                                     (size_t)bt.E, 0u, (unsigned)h->sort_bits, st));
-    hipLaunchKernelGGL(segment_kernel<uint16_t>, seg_grid, dim3(256), 0, st, x.sorted_key16, x.sorted_val, (uint32_t)bt.E,
-                       x.seg, x.seg + I, x.dup_count, h->dup_cap, x.dup_of_pos, x.dup_of_ex, h->dup_stripes,
-                       (const uint32_t*)h->d_rank_of, x.seg + 2 * (size_t)I, x.seg + 3 * (size_t)I, shs ? I : 0xFFFFFFFFu);
-  } else {
-    HIPCHK(rocprim::radix_sort_pairs(sort_tmp, h->sort_tmp_bytes, x.item.p, x.sorted_item.p, x.val.p, x.sorted_val.p,
-                                     (size_t)bt.E, 0u, (unsigned)h->sort_bits, st));
-    hipLaunchKernelGGL(segment_kernel<uint32_t>, seg_grid, dim3(256), 0, st, x.sorted_item, x.sorted_val, (uint32_t)bt.E,
-                       x.seg, x.seg + I, x.dup_count, h->dup_cap, x.dup_of_pos, x.dup_of_ex, h->dup_stripes,
-                       (const uint32_t*)h->d_rank_of, x.seg + 2 * (size_t)I, x.seg + 3 * (size_t)I, shs ? I : 0xFFFFFFFFu);
-  }
+  CHK(order_examples(h, x, bt.E, st, sort_tmp, n_units, bucket, use_cells, shs ? I : 0xFFFFFFFFu));
   if (RowRecord* const pack = pack_of(h, x, bt.E))
     hipLaunchKernelGGL(row_pack_kernel, dim3(1), dim3(ROW_PACK_THREADS), 0, st, (const uint32_t*)h->d_item_order, (const uint32_t*)(x.seg + 2 * (size_t)I),
                        (const uint32_t*)(x.seg + 3 * (size_t)I), decode_hot_rows(h), I, pack);
@@ -1307,6 +1339,46 @@ int compute_batch_mf(cdae_hip* h, int b, const Batch& bt) {
   return 0;
 }
 
+// WARP: one block of users (cdae_warp_kernels.hpp).  In place (a block of one user, or the sequential launch window) the one launch is the
+// reference loop.  The block schedule: phase U searches, steps the user vectors and writes the block's pair records; the item-major order
+// of those records can only be made now, on this stream (VOID keys of the skipped pairs included); phase I is mf_item_kernel, BPR's record
+// format without bias steps.
+int compute_batch_warp(cdae_hip* h, int b, const Batch& bt, uint64_t seed, uint32_t epoch) {
+  using namespace cdae;
+  cdae_hip::ExBuf& x = h->ex[b];
+  hipStream_t st = h->stream;
+  const uint32_t I = (uint32_t)h->I, nb = bt.nb;
+  const bool in_place = nb == 1 || h->mf_seq;
+  const dim3 blk(in_place ? 64 : 256), grid_users(in_place ? 1 : (nb + 3) / 4);
+  uint32_t* const rec_item = h->warp_record ? h->d_warp_rec_item.p : nullptr;
+  uint32_t* const rec_cnt = h->warp_record ? h->d_warp_rec_cnt.p : nullptr;
+  Prof pr;
+  HIPCHK(hipStreamWaitEvent(st, x.ready, 0));
+  CHK(pr.begin(h, F_DECODE, st));
+  dispatch_ni(h->NI, [&](auto ni) {
+    constexpr int NI = decltype(ni)::value;
+    auto launch = [&](auto kernel) {
+      hipLaunchKernelGGL(kernel, grid_users, blk, 0, st, h->hp, (const int64_t*)h->d_row_ptr, (const uint32_t*)h->d_col, bt.s0, nb, seed, epoch,
+                         (const float*)h->d_warp_l, h->d_Wu.p, h->d_Wu_ag.p, h->P(CDAE_P_W), h->P(CDAE_P_W_AG), (const float*)h->P(CDAE_P_BP),
+                         x.item.p, x.val.p, h->d_UVpre.p, h->d_G.p, rec_item, rec_cnt);
+    };
+    if (in_place) launch(warp_user_kernel<NI, true>); else launch(warp_user_kernel<NI, false>);
+  });
+  CHK(pr.end());
+  if (!in_place) {
+    CHK(pr.begin(h, F_SORT, st));
+    CHK(order_examples(h, x, bt.E, st, h->d_sort_tmp, 0u, false, false, I));
+    CHK(pr.end());
+    CHK(pr.begin(h, F_INPUT, st));
+    DISPATCH_NI(h->NI, mf_item_kernel, dim3((I + 3) / 4), blk, 0, st, h->hp, 0u, h->d_item_order, x.seg, x.seg + I, x.sorted_val,
+                h->d_UVpre, h->d_G, h->P(CDAE_P_W), h->P(CDAE_P_W_AG), h->P(CDAE_P_BP), h->P(CDAE_P_BP_AG));
+    CHK(pr.end());
+  }
+  HIPCHK(hipEventRecord(x.released, st));
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
 // z for nb users: a contiguous range [u0, u0+nb) (d_uids == nullptr) or the list d_uids (prefix in d_uptr_tmp)
 int encode_chunk(cdae_hip* h, const uint32_t* d_uids, uint64_t u0, uint32_t nb, int mode, uint32_t stream_id,
                  uint32_t cidx, uint64_t seed, uint32_t epoch, uint32_t n_units_list = 0, float* z_out = nullptr,
@@ -1503,6 +1575,29 @@ int cdae_hip_create_als(const cdae_als_config* ac, int device_id, cdae_hip_t** o
   h->mf_seq = true; h->B = MF_SEQ_USERS;
   h->als_steps = ac->cg_steps ? ac->cg_steps : CDAE_ALS_DEFAULT_CG_STEPS;
   h->als_alpha = (float)ac->alpha; h->als_lambda = (float)ac->lambda;
+  return 0;
+}
+
+int cdae_hip_create_warp(const cdae_warp_config* wc, int device_id, cdae_hip_t** out) {
+  if (!wc || !out) return fail("null argument");
+  if (wc->struct_size != sizeof(cdae_warp_config)) return fail("cdae_warp_config size mismatch: got %u, want %zu", wc->struct_size, sizeof(cdae_warp_config));
+  if (wc->loss_type > 3u && wc->loss_type != CDAE_LOSS_CROSS_ENTROPY)
+    return fail("loss_type %u unsupported: SQUARE (0), LOGISTIC (1), LOG (2), HINGE (3), CROSS_ENTROPY (5)", wc->loss_type);
+  if (wc->num_neg == 0) return fail("num_neg must be >= 1");
+  cdae_hip_config c = cdae_hip_config();
+  c.struct_size = sizeof(c);
+  c.num_dim = wc->num_dim; c.num_neg = wc->num_neg; c.num_corruptions = 1;
+  c.loss_type = CDAE_LOSS_SQUARE;                          // (validated above; the WARP kernels read hp.loss_type, set below)
+  c.using_adagrad = wc->using_adagrad; c.user_factor = 1;
+  c.batch_users = wc->batch_users ? wc->batch_users : 1u;  // no block size has been measured for accuracy: the default is the reference loop
+  c.lambda = wc->lambda; c.learn_rate = wc->learn_rate; c.corruption_ratio = 0.;
+  c.beta = 0.;                                             // warp.hpp:107-109 divide by sqrt(acc) alone (WARPConfig::beta is never read)
+  CHK(cdae_hip_create(&c, device_id, out));
+  cdae_hip* h = *out;
+  h->mf = 4u; h->mf_bias = 0u;                             // biases are part of the score and of no step (warp.hpp:93-94, 112-113)
+  if (c.batch_users == 1u) { h->mf_seq = true; h->B = MF_SEQ_USERS; }
+  h->hp.loss_type = wc->loss_type;
+  h->hp.lambda = (float)(2.0 * wc->lambda);                // warp.hpp:95-97: the gradients regularise with 2 * lambda
   return 0;
 }
 
@@ -1717,6 +1812,8 @@ int upload_data_set(cdae_hip* h, const cdae::plan::Plan& p, const int64_t* grp, 
         CHK(b.rank.alloc((size_t)I)); CHK(b.bucketed.alloc(h->Ecap));
         CHK(b.tile_hist.alloc((size_t)((h->Ecap + cdae::TILE_EX - 1) / cdae::TILE_EX + 1) * I));
         CHK(b.block_total.alloc(128));
+      } else if (h->mf == 4u) {
+        // WARP: warp_user_kernel writes 32-bit keys only (its lists are ordered by the library sort on x.item, VOID = I included)
       } else if (I + (h->shard_sampled() ? 1u : 0u) <= 65536) { CHK(b.key16.alloc(h->Ecap + 8)); CHK(b.sorted_key16.alloc(h->Ecap)); }   // (a sampled item shard sorts one more key: VOID = I)
       if (h->bucket_sort) { CHK(b.bucketed.alloc(h->Ecap)); }
       b.cell_tag = 0;
@@ -1755,11 +1852,15 @@ int upload_data_set(cdae_hip* h, const cdae::plan::Plan& p, const int64_t* grp, 
     CHK(h->d_G.alloc(h->Ecap));
   }
   if (h->mf) {                                              // IMF / BPR / WRMF: the bias arrays (WRMF: the ones IMF's serving reads)
-    const uint64_t inst_cap = p.emax * (h->mf == 2 ? h->hp.num_neg : 1u + h->hp.num_neg);
+    const uint64_t inst_cap = p.emax * (h->mf == 2 || h->mf == 4 ? h->hp.num_neg : 1u + h->hp.num_neg);
     if (!als) CHK(h->d_UVpre.alloc((size_t)inst_cap * h->Kp));
     CHK(h->d_ub.alloc((size_t)U)); CHK(h->d_ub_ag.alloc((size_t)U));
     h->cnt[CDAE_P_UB] = h->cnt[CDAE_P_UB_AG] = (size_t)U;
     HIPCHK(hipMemset(h->d_ub, 0, (size_t)U * sizeof(float)));
+  }
+  if (h->mf == 4u) {                                        // WARP: the rank weights (warp.hpp:57-60)
+    const std::vector<float> l = cdae::warp_rank_weights(I);
+    CHK(dev_upload(h->d_warp_l, l.data(), l.size()));
   }
   if (als) {
     CHK(h->d_tptr.alloc(I + 1));
@@ -1984,6 +2085,8 @@ namespace {
 constexpr const char* ALS_EVERY_ROW = "a WRMF handle trains by whole half-steps, and a half-step needs every row "
                                       "(cdae_hip_train_epoch, cdae_hip_als_half_step)";
 int als_half_step(cdae_hip* h, uint32_t side);              // (below, beside cdae_hip_als_solve_rows)
+constexpr const char* WARP_NO_LIST = "a WARP handle has no example list before the step: its negatives are searched for in the training "
+                                     "launch (cdae_hip_warp_search returns them)";
 
 int make_plan(cdae_hip* h, uint64_t u_begin, uint64_t u_end, std::vector<Batch>& plan) {
   if (u_begin > u_end || u_end > h->U) return fail("bad user range [%llu, %llu)", (unsigned long long)u_begin, (unsigned long long)u_end);
@@ -2168,7 +2271,8 @@ int enqueue_users(cdae_hip* h, uint64_t seed, uint32_t epoch, uint64_t u_begin, 
       }
     }
     int rc = 0;
-    if (h->mf) rc = compute_batch_mf(h, set, plan[t]);
+    if (h->mf == 4u) rc = compute_batch_warp(h, set, plan[t], seed, epoch);
+    else if (h->mf) rc = compute_batch_mf(h, set, plan[t]);
     else if (h->cfg.full_output) rc = compute_batch_full(h, set, plan[t], seed, epoch);
     else rc = compute_batch(h, set, plan[t], seed, epoch);
     h->skip_ready_wait = false;
@@ -2501,6 +2605,7 @@ int cdae_hip_debug_row_pack(cdae_hip_t* h, uint64_t seed, uint32_t epoch, uint64
   if (!n_records) return fail("null argument");
   if (!h || !h->d_shared) return fail("set_interactions must be called first");
   if (h->mf == 3u) return fail("%s", ALS_EVERY_ROW);
+  if (h->mf == 4u) return fail("%s", WARP_NO_LIST);
   const uint32_t hot = decode_hot_rows(h);
   const uint64_t want = packs_rows(h) ? (((uint64_t)h->I - hot + 3) & ~3ull) : 0;
   if (want > *n_records) return fail("the pack has %llu records, the caller's array holds %llu", (unsigned long long)want, (unsigned long long)*n_records);
@@ -2519,6 +2624,7 @@ int cdae_hip_debug_sample_batch(cdae_hip_t* h, uint64_t seed, uint32_t epoch, ui
                                 uint32_t* dup_of_ex, uint64_t* n_examples) {
   if (!h || !h->d_shared) return fail("set_interactions must be called first");
   if (h->mf == 3u) return fail("%s", ALS_EVERY_ROW);
+  if (h->mf == 4u) return fail("%s", WARP_NO_LIST);
   if (!n_examples) return fail("null argument");
   if (n_users == 0 || u_begin + n_users > h->U) return fail("bad user range [%llu, +%u)", (unsigned long long)u_begin, n_users);
   if (n_users > std::min<uint64_t>(h->B, h->U)) return fail("%u users exceed batch_users %u", n_users, h->B);
@@ -3388,6 +3494,76 @@ int cdae_hip_als_half_step(cdae_hip_t* h, uint32_t side) {
   if (side != CDAE_ALS_USERS && side != CDAE_ALS_ITEMS) return fail("cdae_hip_als_half_step: side must be CDAE_ALS_USERS or CDAE_ALS_ITEMS");
   HIPCHK(hipSetDevice(h->device));
   CHK(als_half_step(h, side));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  return 0;
+}
+
+// ---- WARP (cdae_warp_kernels.hpp) ---------------------------------------------------------------------------------------
+constexpr uint32_t WARP_SEARCH_CHUNK = 8192;      // users (one wavefront each) per launch of cdae_hip_warp_search
+static int warp_check(cdae_hip* h, const char* fn) {
+  if (!h || !h->d_shared) return fail("set_interactions must be called first");
+  if (h->mf != 4u) return fail("%s applies to a WARP handle (cdae_hip_create_warp)", fn);
+  return 0;
+}
+
+int cdae_hip_warp_search(cdae_hip_t* h, uint64_t seed, uint32_t epoch, uint64_t pos_begin, uint64_t pos_end, uint32_t* out_item,
+                         uint32_t* out_cnt, float* out_margin, size_t count) {
+  const char* fn = "cdae_hip_warp_search";
+  CHK(warp_check(h, fn));
+  if (pos_begin > pos_end || pos_end > h->U) return fail("%s: bad range of positions [%llu, %llu)", fn, (unsigned long long)pos_begin, (unsigned long long)pos_end);
+  const uint64_t pairs = cdae::warp_pair_count(h->h_row_ptr.data(), pos_begin, pos_end, h->hp.num_neg);
+  if (count != pairs) return fail("%s: the range holds %llu pairs, the caller's arrays %zu", fn, (unsigned long long)pairs, count);
+  if (pairs && (!out_item || !out_cnt)) return fail("%s: null argument", fn);
+  if (pairs == 0) return 0;
+  HIPCHK(hipSetDevice(h->device));
+  CHK(join_aux(h));
+  // the outputs of the largest chunk
+  uint64_t chunk_pairs = 0;
+  for (uint64_t c0 = pos_begin; c0 < pos_end; c0 += WARP_SEARCH_CHUNK)
+    chunk_pairs = std::max(chunk_pairs, cdae::warp_pair_count(h->h_row_ptr.data(), c0, std::min<uint64_t>(c0 + WARP_SEARCH_CHUNK, pos_end), h->hp.num_neg));
+  CHK(h->d_warp_out_item.ensure(chunk_pairs)); CHK(h->d_warp_out_cnt.ensure(chunk_pairs));
+  if (out_margin) CHK(h->d_warp_out_margin.ensure(chunk_pairs));
+  for (uint64_t c0 = pos_begin; c0 < pos_end; c0 += WARP_SEARCH_CHUNK) {
+    const uint32_t nu = (uint32_t)std::min<uint64_t>(WARP_SEARCH_CHUNK, pos_end - c0);
+    const uint64_t np = cdae::warp_pair_count(h->h_row_ptr.data(), c0, c0 + nu, h->hp.num_neg);
+    if (np == 0) continue;
+    const uint64_t q0 = cdae::warp_pair_count(h->h_row_ptr.data(), pos_begin, c0, h->hp.num_neg);
+    DISPATCH_NI(h->NI, cdae::warp_search_kernel, dim3((nu + 3) / 4), dim3(256), 0, h->stream, h->hp, (const int64_t*)h->d_row_ptr,
+                (const uint32_t*)h->d_col, c0, nu, (int64_t)h->h_row_ptr[c0], seed, epoch, (const float*)h->d_Wu, (const float*)h->P(CDAE_P_W),
+                (const float*)h->P(CDAE_P_BP), h->d_warp_out_item.p, h->d_warp_out_cnt.p, out_margin ? h->d_warp_out_margin.p : (float*)nullptr);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(out_item + q0, h->d_warp_out_item, np * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(out_cnt + q0, h->d_warp_out_cnt, np * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+    if (out_margin) HIPCHK(hipMemcpyAsync(out_margin + q0, h->d_warp_out_margin, np * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));            // the next chunk writes the same buffers
+  }
+  return 0;
+}
+
+int cdae_hip_warp_record_choices(cdae_hip_t* h, uint32_t on) {
+  CHK(warp_check(h, "cdae_hip_warp_record_choices"));
+  HIPCHK(hipSetDevice(h->device));
+  if (on && !h->d_warp_rec_item) {
+    const size_t n = (size_t)cdae::warp_pair_count(h->h_row_ptr.data(), 0, h->U, h->hp.num_neg);
+    CHK(h->d_warp_rec_item.alloc(n)); CHK(h->d_warp_rec_cnt.alloc(n));
+    HIPCHK(hipMemsetAsync(h->d_warp_rec_item, 0xFF, std::max<size_t>(n, 1) * sizeof(uint32_t), h->stream));
+    HIPCHK(hipMemsetAsync(h->d_warp_rec_cnt, 0, std::max<size_t>(n, 1) * sizeof(uint32_t), h->stream));
+  }
+  h->warp_record = on != 0;
+  return 0;
+}
+
+int cdae_hip_warp_choices(cdae_hip_t* h, uint32_t* out_item, uint32_t* out_cnt, size_t count) {
+  const char* fn = "cdae_hip_warp_choices";
+  CHK(warp_check(h, fn));
+  if (!h->d_warp_rec_item) return fail("%s: nothing has been recorded (cdae_hip_warp_record_choices)", fn);
+  const size_t n = (size_t)cdae::warp_pair_count(h->h_row_ptr.data(), 0, h->U, h->hp.num_neg);
+  if (count != n) return fail("%s: the record holds %zu pairs, the caller's arrays %zu", fn, n, count);
+  if (n && (!out_item || !out_cnt)) return fail("%s: null argument", fn);
+  if (n == 0) return 0;
+  HIPCHK(hipSetDevice(h->device));
+  HIPCHK(hipMemcpyAsync(out_item, h->d_warp_rec_item, n * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipMemcpyAsync(out_cnt, h->d_warp_rec_cnt, n * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));
   return 0;
 }

@@ -90,7 +90,10 @@ extern "C" {
  *     CDAE_ITEMS_INPUT, CDAE_SIM_DOT / CDAE_SIM_COSINE — batched top-k item neighbours of named items by dot product or cosine
  *     also under 12, the version unchanged (new entry points; nothing existing changed): cdae_als_config, cdae_hip_create_als,
  *     cdae_hip_als_half_step, cdae_hip_als_solve_rows, cdae_hip_als_gram, CDAE_ALS_USERS / CDAE_ALS_ITEMS — WRMF fitted by alternating
- *     least squares, conjugate gradients per row on the matrix cores */
+ *     least squares, conjugate gradients per row on the matrix cores
+ *     also under 12, the version unchanged (new entry points; nothing existing changed): cdae_warp_config, cdae_hip_create_warp,
+ *     cdae_hip_warp_search, cdae_hip_warp_record_choices, cdae_hip_warp_choices, CDAE_WARP_MAX_TRY — WARP: rank-weighted pairwise
+ *     matrix factorisation whose negatives are searched for on the device */
 #define CDAE_HIP_ABI_VERSION 12
 
 /* numeric values follow libcf::LossType (/root/reference/src/model/loss.hpp:10-18) */
@@ -750,6 +753,54 @@ int cdae_hip_als_solve_rows(cdae_hip_t* h, uint64_t n_rows, const int64_t* row_p
 /* G = T^T T of the current user (CDAE_ALS_USERS) or item (CDAE_ALS_ITEMS) table as the half-steps compute it, [num_dim x num_dim]
  * row-major: a test hook (the same table gives the same bits on every call). */
 int cdae_hip_als_gram(cdae_hip_t* h, uint32_t side, float* out, size_t count);
+
+/* ---- WARP: rank-weighted pairwise matrix factorisation (Weston, Bengio, Usunier, "WSABIE"; the reference's src/model/recsys/warp.hpp,
+ * `class WARP : public IMF`), on the same handle type --------------------------------------------------------------------------------
+ * For users in order, for every positive i of the user in row order, with items_left = num_items - n_u:
+ *     yui = s(i)                                    once per positive: NOT refreshed between its num_neg pairs
+ *     for k < num_neg:
+ *         draw candidates j_0, j_1, ... until s(j_t) > yui - 1 (strict, fp32) or CDAE_WARP_MAX_TRY draws are made; cnt = t + 1
+ *         cnt >= CDAE_WARP_MAX_TRY: the pair is skipped (a violator found at the 500th draw too)
+ *         g = loss'(yui - s(j), 1) * l[items_left / cnt]      integer division; l[idx] = H_{idx + 1}, the harmonic numbers
+ *         uv_u, iv_i, iv_j step as BPR's do, all three from the pre-step values, with 2 lambda regularisation; AdaGrad divides by
+ *         sqrt(acc) — no beta — and biases are part of no step
+ * s(x) = ib[x] + uv_u . iv_x (ub cancels on both sides of the test).  Candidate t of pair (p, k) of a user is
+ * cdae_sample_negative(key, (p * num_neg + k) * CDAE_WARP_MAX_TRY + t, row, n_u, num_items) on the CDAE_STREAM_NEGATIVE key that
+ * IMF / BPR use (include/cdae_rng.h); candidates past the first violator are never looked at.  The rank weights are filled by
+ * cdae_hip_set_interactions: the fp64 recurrence, rounded once to fp32.
+ * Parameters live where IMF's do and cdae_hip_init_params draws them as for IMF (Random() * 0.01, accumulators 1e-4, biases 0, the same
+ * stream keys), so cdae_hip_recommend_all, cdae_hip_eval_topn, cdae_hip_similar_items and get / set_param serve the handle as they
+ * serve an IMF handle; everything that refuses an IMF / BPR handle refuses this one with the same text.  cdae_hip_debug_sample_batch
+ * and cdae_hip_debug_row_pack are refused: there is no example list before the step.
+ * loss_type: the five losses of cdae_mf_config (the reference's default is HINGE).  batch_users: 1 (and 0, which selects 1) is the
+ * reference loop.  A value above 1 is the block schedule of IMF / BPR in cdae_hip_user_order's activity-grouped order: one wavefront per
+ * user of the block searches and steps its user vector against the block-start item rows, then every item row takes its pairs' steps in
+ * (user, pair) order.  No block size has been measured for accuracy, so none is a default. */
+typedef struct cdae_warp_config {
+  uint32_t struct_size;      /* sizeof(cdae_warp_config)                                 */
+  uint32_t num_dim;          /* WARPConfig::num_dim (10)                                 */
+  uint32_t num_neg;          /* WARPConfig::num_neg (5)                                  */
+  uint32_t loss_type;        /* CDAE_LOSS_*: 0, 1, 2, 3 (HINGE, the default), 5          */
+  uint32_t using_adagrad;    /* WARPConfig::using_adagrad (1)                            */
+  uint32_t batch_users;      /* 0 or 1: the reference loop; > 1: block schedule          */
+  double lambda;             /* WARPConfig::lambda (0.1)                                 */
+  double learn_rate;         /* WARPConfig::learn_rate (0.1)                             */
+} cdae_warp_config;
+#define CDAE_WARP_MAX_TRY 500u
+int cdae_hip_create_warp(const cdae_warp_config* cfg, int device_id, cdae_hip_t** out);
+/* The search of every (position, positive, k) of training positions [pos_begin, pos_end) against the current parameters, with the draws
+ * of (seed, epoch); nothing is trained.  out_item[q] / out_cnt[q] with q = (row offset of the positive from pos_begin's first positive)
+ * * num_neg + k; cnt = CDAE_WARP_MAX_TRY and item = 0xFFFFFFFF: exhausted.  out_margin (may be NULL): s(j) - (s(i) - 1) of the chosen
+ * candidate (0 where exhausted).  count must be the range's pair count; it is checked before any launch.  Hard-negative mining for a
+ * caller, and the hook that pins the search: the training kernels call the same device function.  One wavefront per user, chunks of
+ * at most 8 192 users. */
+int cdae_hip_warp_search(cdae_hip_t* h, uint64_t seed, uint32_t epoch, uint64_t pos_begin, uint64_t pos_end,
+                         uint32_t* out_item, uint32_t* out_cnt, float* out_margin /* may be NULL */, size_t count);
+/* With recording on, a training call leaves the (item, cnt) of every pair of the users it trained, in position order (skipped pairs as
+ * above), in a buffer of nnz * num_neg pairs allocated by the first on = 1; pairs of users no call has trained since read 0xFFFFFFFF / 0.
+ * Off by default; off costs nothing.  cdae_hip_warp_choices copies the whole record out (count = nnz * num_neg). */
+int cdae_hip_warp_record_choices(cdae_hip_t* h, uint32_t on);
+int cdae_hip_warp_choices(cdae_hip_t* h, uint32_t* out_item, uint32_t* out_cnt, size_t count);
 
 /* ---- library-owned RCCL communicator and exchange schedule (one process per GPU: bench.py --gpus N) -----------------
  * The all-reduce of the staged deltas runs inside the library, on its own communicator and HIP stream, overlapped with the

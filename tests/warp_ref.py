@@ -1,0 +1,356 @@
+"""Test infrastructure: WARP in numpy, fp64 — the search and the training loop of include/cdae_hip.h's WARP section, written from that
+description and from include/cdae_rng.h (whose mixer is restated here twice: in Python integers, literally, and on numpy uint64 arrays
+for whole batches of draws; tests/test_warp_reference.py holds the two against each other).
+
+  Draws(ptr, col, num_items, num_neg, seed, epoch)   the candidate lists of every pair of a data set whose rows are in POSITION order
+  search(state, draws, pos, p, k)                    the literal search -> (item, cnt, margin)
+  train(state, draws, B, ...)                        one epoch: B = 1 the loop, B > 1 the block schedule; with `choices` it follows the
+                                                     device's decisions and verifies each one within `tol`
+
+A state holds uv, uva [U, K] BY POSITION, iv, iva [I, K], ib [I] as float64 and the hyper-parameters.
+"""
+import numpy as np
+
+MAX_TRY = 500                    # CDAE_WARP_MAX_TRY
+LOOK = MAX_TRY - 1               # draws that can train a pair
+NONE = 0xFFFFFFFF
+NEG_MAX_TRY = 32                 # CDAE_NEG_MAX_TRY
+STREAM_NEGATIVE = 1
+M64 = (1 << 64) - 1
+GOLDEN = 0x9E3779B97F4A7C15
+
+
+# ---- include/cdae_rng.h in Python integers ------------------------------------------------------------------------------------------
+def mix64(x):
+    x ^= x >> 30; x = (x * 0xBF58476D1CE4E5B9) & M64
+    x ^= x >> 27; x = (x * 0x94D049BB133111EB) & M64
+    x ^= x >> 31
+    return x
+
+
+def rng_key(seed, epoch, uid, stream):
+    x = mix64((seed + GOLDEN * (epoch + 1)) & M64)
+    return mix64(x ^ ((uid * 0xD1B54A32D192ED03 + stream + 1) & M64))
+
+
+def rng_draw(key, idx):
+    return mix64((key + GOLDEN * (idx + 1)) & M64) >> 32
+
+
+def sample_negative(key, draw_index, row, num_items):
+    """cdae_sample_negative: `row` any container of the user's positives"""
+    row = set(int(i) for i in row)
+    cand = 0
+    for t in range(NEG_MAX_TRY):
+        cand = (rng_draw(key, draw_index * NEG_MAX_TRY + t) * num_items) >> 32
+        if cand not in row:
+            return cand
+    for _ in range(num_items):
+        cand = 0 if cand + 1 == num_items else cand + 1
+        if cand not in row:
+            return cand
+    return cand
+
+
+def draw_index(p, num_neg, k, t):
+    return (p * num_neg + k) * MAX_TRY + t
+
+
+# ---- the same on uint64 arrays ------------------------------------------------------------------------------------------------------
+def _u(x):
+    return np.uint64(x)
+
+
+def _mix64_v(x):
+    x = x ^ (x >> _u(30)); x = x * _u(0xBF58476D1CE4E5B9)
+    x = x ^ (x >> _u(27)); x = x * _u(0x94D049BB133111EB)
+    return x ^ (x >> _u(31))
+
+
+def sample_negatives(keys, draw_idx, urow, rated, num_items):
+    """cdae_sample_negative for arrays: keys[n], draw_idx[n] uint64, urow[n] the row of `rated` [U, I] bool each draw is rejected against"""
+    keys = np.asarray(keys, dtype=np.uint64); draw_idx = np.asarray(draw_idx, dtype=np.uint64); urow = np.asarray(urow, dtype=np.int64)
+    out = np.zeros(keys.size, dtype=np.int64)
+    todo = np.arange(keys.size)
+    for t in range(NEG_MAX_TRY):
+        if todo.size == 0:
+            return out
+        idx = draw_idx[todo] * _u(NEG_MAX_TRY) + _u(t)
+        r = _mix64_v(keys[todo] + _u(GOLDEN) * (idx + _u(1))) >> _u(32)
+        cand = ((r * _u(num_items)) >> _u(32)).astype(np.int64)
+        out[todo] = cand
+        todo = todo[rated[urow[todo], cand]]
+    for _ in range(num_items):                     # the deterministic walk behind 32 rejected draws
+        if todo.size == 0:
+            break
+        cand = out[todo] + 1
+        cand[cand == num_items] = 0
+        out[todo] = cand
+        todo = todo[rated[urow[todo], cand]]
+    return out
+
+
+class Draws:
+    """The candidates of every pair (position, p, k) of one (data set, num_neg, seed, epoch): they do not depend on the parameters.
+    The first HEAD of every pair are drawn at once; a longer list is drawn when a search asks for it."""
+    HEAD = 16
+
+    def __init__(self, ptr, col, num_items, num_neg, seed, epoch):
+        self.ptr = np.asarray(ptr, dtype=np.int64); self.col = np.asarray(col, dtype=np.int64)
+        self.U, self.I, self.num_neg = self.ptr.size - 1, int(num_items), int(num_neg)
+        self.rated = np.zeros((self.U, self.I), dtype=bool)
+        lens = np.diff(self.ptr)
+        self.user_of = np.repeat(np.arange(self.U), lens)                     # position of every stored interaction
+        self.rated[self.user_of, self.col] = True
+        self.keys = np.array([rng_key(seed, epoch, u, STREAM_NEGATIVE) for u in range(self.U)], dtype=np.uint64)
+        self.p_of = np.arange(self.col.size) - self.ptr[self.user_of]         # index of the interaction in its row
+        n_pairs = self.col.size * self.num_neg
+        r = np.arange(n_pairs) // self.num_neg
+        self.pair_user = self.user_of[r]
+        self.pair_base = ((self.p_of[r] * self.num_neg + np.arange(n_pairs) % self.num_neg) * MAX_TRY).astype(np.uint64)
+        t = np.arange(self.HEAD, dtype=np.uint64)
+        self.head = sample_negatives(np.repeat(self.keys[self.pair_user], self.HEAD), (self.pair_base[:, None] + t[None, :]).ravel(),
+                                     np.repeat(self.pair_user, self.HEAD), self.rated, self.I).reshape(n_pairs, self.HEAD)
+        self.full = {}
+
+    def q(self, pos, p, k):
+        return (int(self.ptr[pos]) + p) * self.num_neg + k
+
+    def candidates(self, q, need):
+        if need <= self.HEAD:
+            return self.head[q, :need]
+        if q not in self.full:
+            u = self.pair_user[q]
+            t = np.arange(LOOK, dtype=np.uint64)
+            self.full[q] = sample_negatives(np.full(LOOK, self.keys[u]), self.pair_base[q] + t, np.full(LOOK, u), self.rated, self.I)
+        return self.full[q][:need]
+
+
+# ---- the model ----------------------------------------------------------------------------------------------------------------------
+class State:
+    def __init__(self, uv, uva, iv, iva, ib, *, lambda_=0.1, learn_rate=0.1, loss=3, adagrad=True, acc0=None):      # (acc0: init_state's)
+        self.uv, self.uva, self.iv, self.iva = (np.array(a, dtype=np.float64) for a in (uv, uva, iv, iva))
+        self.ib = np.array(ib, dtype=np.float64)
+        self.lam2, self.lr, self.loss, self.adagrad = 2.0 * lambda_, learn_rate, loss, adagrad
+        self.l = np.cumsum(1.0 / np.arange(1, self.iv.shape[0] + 1)).astype(np.float32).astype(np.float64)   # rounded once to fp32, as the device's table
+
+
+def loss_grad(loss, pred, truth=1.0):
+    """mf_loss_grad (cdae_mf_kernels.hpp) in fp64: SQUARE 0, LOGISTIC 1, LOG 2, HINGE 3, CROSS_ENTROPY 5"""
+    if loss == 0: return -2.0 * (truth - pred)
+    if loss == 1: return (pred - truth) / (pred * (1.0 - pred))
+    if loss == 2: return -truth / (1.0 + np.exp(pred * truth))
+    if loss == 3: return 0.0 if pred * truth > 1.0 else -truth
+    return 1.0 / (1.0 + np.exp(-pred)) - truth
+
+
+def _step(st, w, a, grad):
+    """one AdaGrad (no beta) or SGD step of the vector w with accumulator a, in place"""
+    if st.adagrad:
+        a += grad * grad
+        w -= st.lr * grad / np.sqrt(a)
+    else:
+        w -= st.lr * grad
+
+
+def _margins(st, uv, iv, cands, thr):
+    return st.ib[cands] + iv[cands] @ uv - thr
+
+
+def _first_violator(st, uv, iv, draws, q, thr, stats):
+    """the free search: -> (cnt, margins of the candidates looked at); cnt == MAX_TRY: exhausted"""
+    done = 0
+    parts = []
+    for need in (draws.HEAD, 64, LOOK):
+        c = draws.candidates(q, need)[done:]
+        m = _margins(st, uv, iv, c, thr)
+        parts.append(m)
+        hit = np.nonzero(m > 0.0)[0]
+        if hit.size:
+            parts[-1] = m[:hit[0] + 1]
+            return done + int(hit[0]) + 1, np.concatenate(parts)
+        done = need
+    return MAX_TRY, np.concatenate(parts)
+
+
+def search(st, draws, pos, p, k):
+    """-> (item, cnt, margin): the first candidate t < 499 with s(j) > s(i) - 1, cnt = t + 1; (NONE, 500, 0.0) when there is none"""
+    i = draws.col[draws.ptr[pos] + p]
+    thr = st.ib[i] + st.iv[i] @ st.uv[pos] - 1.0
+    q = draws.q(pos, p, k)
+    cnt, m = _first_violator(st, st.uv[pos], st.iv, draws, q, thr, None)
+    if cnt >= MAX_TRY:
+        return NONE, MAX_TRY, 0.0
+    return int(draws.candidates(q, cnt)[cnt - 1]), cnt, float(m[cnt - 1])
+
+
+def train(st, draws, B=1, choices=None, tol=1e-3, positions=None):
+    """One epoch over the positions 0 .. U - 1 (or the range `positions`) in blocks of B (a block of one user is the loop).  choices = (item, cnt) by
+    (row offset * num_neg + k) in position order: the decisions to FOLLOW; each is verified —
+      every candidate before cnt has margin <= +tol, the chosen one has margin > -tol, a skipped pair has no candidate with margin > +tol
+      among the first 499 — and `bad` lists the ones that fail.
+    -> dict: comparisons, near (|margin| < tol), disagreements (followed decision != the free one), bad, and what the searches looked like:
+    cnt1, cnt2_64, cnt65_499, exhausted, trained, max_abs_score, mixed_blocks (blocks with both a skipped and a trained pair)."""
+    out = dict(comparisons=0, near=0, disagreements=0, bad=[], cnt1=0, cnt2_64=0, cnt65_499=0, exhausted=0, trained=0, max_abs_score=0.0,
+               mixed_blocks=0)
+    U, nn = draws.U, draws.num_neg
+
+    def decide(uv, iv, pos, p, k, yui):
+        """-> (j, cnt, s(j)) of the decision taken; cnt == MAX_TRY: skipped"""
+        q, thr = draws.q(pos, p, k), yui - 1.0
+        if choices is None:
+            cnt, m = _first_violator(st, uv, iv, draws, q, thr, out)
+        else:
+            cnt = int(choices[1][q])
+            look = LOOK if cnt >= MAX_TRY else max(cnt, 1)
+            c = draws.candidates(q, look)
+            m = _margins(st, uv, iv, c, thr)
+            free = np.nonzero(m > 0.0)[0]
+            free_cnt = int(free[0]) + 1 if free.size else MAX_TRY
+            if cnt >= MAX_TRY:
+                ok = int(choices[0][q]) == NONE and not (m > tol).any()
+            else:
+                ok = 1 <= cnt <= LOOK and int(choices[0][q]) == int(c[cnt - 1]) and not (m[:cnt - 1] > tol).any() and m[cnt - 1] > -tol
+            out["disagreements"] += free_cnt != cnt
+            if not ok:                                   # (reported; the epoch goes on with the free decision)
+                out["bad"].append((pos, p, k, int(choices[0][q]), cnt, free_cnt))
+                cnt, m = _first_violator(st, uv, iv, draws, q, thr, out)
+        out["comparisons"] += m.size
+        out["near"] += int((np.abs(m) < tol).sum())
+        out["max_abs_score"] = max(out["max_abs_score"], float(np.abs(m + thr).max()), abs(yui))
+        key = "exhausted" if cnt >= MAX_TRY else "cnt1" if cnt == 1 else "cnt2_64" if cnt <= 64 else "cnt65_499"
+        out[key] += 1
+        if cnt >= MAX_TRY:
+            return None, cnt, 0.0
+        out["trained"] += 1
+        return int(draws.candidates(q, cnt)[cnt - 1]), cnt, float(m[cnt - 1] + thr)
+
+    first, end = positions if positions is not None else (0, U)
+    for s0 in range(first, end, B):
+        nb = min(B, end - s0)
+        in_place = nb == 1
+        iv0 = st.iv if in_place else st.iv.copy()       # the block schedule reads the item rows as the block found them
+        records = []
+        skipped = trained = 0
+        for pos in range(s0, s0 + nb):
+            row = draws.col[draws.ptr[pos]:draws.ptr[pos + 1]]
+            items_left = draws.I - row.size
+            uv, ua = st.uv[pos], st.uva[pos]
+            for p, i in enumerate(row):
+                yui = st.ib[i] + iv0[i] @ uv             # once per positive
+                for k in range(nn):
+                    j, cnt, yuj = decide(uv, iv0, pos, p, k, yui)
+                    if j is None:
+                        skipped += 1
+                        continue
+                    trained += 1
+                    pred = yui - yuj
+                    if choices is not None and st.loss == 3:
+                        # A followed decision says that the device saw a violator: pred < 1 in ITS arithmetic, while this one may be
+                        # a hair above (a margin inside the band).  HINGE's gradient jumps from -1 to 0 exactly there: it is taken
+                        # on the device's side of the jump.  (The other losses are smooth: a pred off by < tol moves g by < tol.)
+                        pred = min(pred, 1.0)
+                    g = loss_grad(st.loss, pred) * st.l[items_left // cnt]
+                    uv_grad = g * (iv0[i] - iv0[j]) + st.lam2 * uv
+                    if in_place:                         # all three from the pre-step values
+                        gi = g * uv + st.lam2 * st.iv[i]
+                        gj = -g * uv + st.lam2 * st.iv[j]
+                        _step(st, st.iv[i], st.iva[i], gi)
+                        _step(st, st.iv[j], st.iva[j], gj)
+                    else:
+                        records.append((i, j, g, uv.copy()))
+                    _step(st, uv, ua, uv_grad)
+        for i, j, g, uvpre in records:                   # phase I: every item row takes its pairs' steps in (user, pair) order
+            _step(st, st.iv[i], st.iva[i], g * uvpre + st.lam2 * st.iv[i])
+            _step(st, st.iv[j], st.iva[j], -g * uvpre + st.lam2 * st.iv[j])
+        out["mixed_blocks"] += bool(skipped and trained)
+    return out
+
+
+# ---- fixtures shared by tests/test_warp_reference.py (their premises, on the CPU) and tests/test_gpu_warp.py (the trajectories) --------
+STREAM_INIT, P_W, P_WU = 3, 0, 4
+
+
+def init_table(rows, K, which, seed, scale=0.01):
+    """cdae_hip_init_params of an IMF-shaped handle: float32(cdae_init_uniform(key, row * K + k) * scale)"""
+    key = _u(rng_key(seed, 0, which, STREAM_INIT))
+    idx = np.arange(rows * K, dtype=np.uint64)
+    r = _mix64_v(key + _u(GOLDEN) * (idx + _u(1))) >> _u(32)
+    return ((((r.astype(np.float64) + 0.5) * (1.0 / 4294967296.0)) * 2.0 - 1.0) * scale).astype(np.float32).reshape(rows, K)
+
+
+def init_state(U, I, K, seed, **hyper):
+    """the state cdae_hip_init_params(seed) leaves: tables drawn as above, accumulators 1e-4, biases 0.  hyper["acc0"]: a fixture that
+    starts its accumulators elsewhere (the GPU test sets them through set_param)"""
+    acc0 = np.float32(hyper.get("acc0") or 1e-4)
+    return State(init_table(U, K, P_WU, seed), np.full((U, K), acc0), init_table(I, K, P_W, seed), np.full((I, K), acc0), np.zeros(I), **hyper)
+
+
+EPOCHS = 2
+# (name, data set, batch_users, num_dim, num_neg, hyper-parameters beyond WARPConfig's defaults, parameter seed, stream seed)
+# The stream seeds are the first for which the free-running reference reaches every search depth AND is well conditioned: with AdaGrad
+# and no beta a step is lr * grad / sqrt(1e-4 + sum grad^2), a sign function of the gradient while the accumulator is young, so a
+# coordinate whose gradient passes through zero amplifies rounding by lr / sqrt(1e-4) x |g| per step.  On such a trajectory the same
+# numpy loop in float32 ends 1e-3 of the range from its float64 self (stream seed 2 at K = 64: 1.2e-3; the device then measures 1.9e-3),
+# and a parameter bound of 2e-4 would measure the trajectory, not the kernel.  run_free() reports that drift and
+# tests/test_warp_reference.py bounds it at DRIFT_MAX, a quarter of the bound.
+# Where the issue leaves the learn rate open it is chosen so that |score| stays below 16: with AdaGrad and no beta the first step of a
+# coordinate is learn_rate whatever the gradient, so a pair's score moves by about num_dim * learn_rate^2 per step — 0.1 at K = 24 is
+# 0.03 at K = 200 and 0.015 at K = 300 ("tiny" has rows of up to 60 positives: 0.05 for its loop at K = 24).
+#
+# The loop at the K tier edges runs with WARPConfig's defaults, learn rate included, and there a pair's score moves by num_dim * 0.01 per
+# step while the accumulators are young: from cdae_hip_init_params' state (accumulators 1e-4) |score| reaches 26.7 / 24.6 / 57.7 / 47.4 /
+# 93.1 at K = 128 / 129 / 256 / 257 / 512 whatever the seed.  The hyper-parameters stay the defaults; what those five fixtures change is
+# their START: the accumulators begin at acc0 = 3, 5, 10 (about K / 50, the smallest of these at which the free reference stays below 16),
+# so that a step moves a coordinate by at most lr * |g| / sqrt(acc0), a fraction of its value, and not by lr.  The GPU test writes that
+# start through set_param; everything else of the state is init_params'.
+CASES = [(f"d40-loop-K{K}", "d40", 1, K, 5, dict(acc0=a) if a else {}, 11, s)
+         for K, s, a in ((1, 191, 0), (64, 4, 0), (65, 11, 0), (128, 5, 3.0), (129, 1, 3.0), (256, 1, 5.0), (257, 2, 5.0), (512, 5, 10.0))] + [
+    ("d40-loop-sgd", "d40", 1, 200, 5, dict(adagrad=False, learn_rate=0.03), 11, 1),
+    ("d40-loop-log", "d40", 1, 200, 5, dict(loss=2, learn_rate=0.03), 11, 3),
+    ("d40-loop-neg1", "d40", 1, 200, 1, dict(learn_rate=0.03), 11, 29),
+    ("d40-loop-neg12", "d40", 1, 200, 12, dict(learn_rate=0.03), 11, 2),
+    ("tiny-loop", "tiny", 1, 24, 5, dict(learn_rate=0.05), 11, 1),
+    ("d40-block8", "d40", 8, 24, 5, {}, 11, 9),
+    ("tiny-block33-K24", "tiny", 33, 24, 5, {}, 11, 3),
+    ("tiny-block33-K200", "tiny", 33, 200, 5, dict(learn_rate=0.02), 11, 1),
+    ("tiny-block33-K300", "tiny", 33, 300, 5, dict(learn_rate=0.015), 11, 1),
+]
+TOL = 1e-3                       # the band in which an fp32 and an fp64 margin may fall on different sides of 0
+NEAR_SHARE = 1e-3                # ... and the share of comparisons that may lie inside it
+SCORE_MAX = 16.0
+DRIFT_MAX = 5e-5                 # float32 against float64 on the reference alone: a quarter of the GPU test's 2e-4
+
+
+def fixture_data(name):
+    import mf_conflict_ref
+    from cdae_amd import synth
+    return mf_conflict_ref.d40() if name == "d40" else synth.generate_shape("tiny", seed=5)
+
+
+def _as_float32(st):
+    for n in ("uv", "uva", "iv", "iva", "ib", "l"):
+        setattr(st, n, getattr(st, n).astype(np.float32))
+    st.lam2, st.lr = np.float32(st.lam2), np.float32(st.lr)
+    return st
+
+
+def run_free(case):
+    """the free-running reference of one case: -> the totals of train()'s counts over the case's epochs (max_abs_score: the maximum)
+    and `drift`: how far the same run in float32 ends from it, in the measure of the GPU test's bound (max |difference| / (1e-3 + max
+    |value|) over the four tables) — what rounding alone does to this trajectory, whatever the kernel"""
+    name, ds, B, K, nn, hyper, pseed, sseed = case
+    d = fixture_data(ds)
+    st = init_state(d.num_users, d.num_items, K, pseed, **hyper)
+    st32 = _as_float32(init_state(d.num_users, d.num_items, K, pseed, **hyper))
+    tot = {}
+    for ep in range(EPOCHS):
+        draws = Draws(d.train_ptr, d.train_col, d.num_items, nn, sseed, ep)
+        o = train(st, draws, B)
+        train(st32, draws, B)
+        for k, v in o.items():
+            if k != "bad":
+                tot[k] = max(tot.get(k, 0.0), v) if k == "max_abs_score" else tot.get(k, 0) + v
+    tot["drift"] = max(float(np.abs(getattr(st32, n).astype(np.float64) - getattr(st, n)).max() / (1e-3 + np.abs(getattr(st, n)).max()))
+                       for n in ("uv", "uva", "iv", "iva"))
+    return tot
