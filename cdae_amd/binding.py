@@ -70,6 +70,11 @@ class _WarpConfig(C.Structure):
         (n, C.c_double) for n in ("lambda_", "learn_rate")]
 
 
+class _FismConfig(C.Structure):
+    _fields_ = [(n, C.c_uint32) for n in ("struct_size", "num_dim", "num_neg", "loss_type", "using_adagrad", "using_bias_term", "batch_users",
+                                          "reserved")] + [(n, C.c_double) for n in ("lambda_", "learn_rate", "alpha")]
+
+
 class Stats(C.Structure):
     _fields_ = [("wall_seconds", C.c_double), ("users", C.c_uint64), ("examples", C.c_uint64),
                 ("batches", C.c_uint64), ("ms_sample", C.c_double), ("ms_sort", C.c_double),
@@ -94,6 +99,9 @@ EXPORTS = {
     "cdae_hip_warp_search": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]),
     "cdae_hip_warp_record_choices": (C.c_int, [C.c_void_p, C.c_uint32]),
     "cdae_hip_warp_choices": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]),
+    "cdae_hip_create_fism": (C.c_int, [C.POINTER(_FismConfig), C.c_int, C.POINTER(C.c_void_p)]),
+    "cdae_hip_fism_plan": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]),
+    "cdae_hip_fism_set_resident": (C.c_int, [C.c_void_p, C.c_int]),
     "cdae_hip_destroy": (C.c_int, [C.c_void_p]),
     "cdae_hip_set_interactions": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p]),
     "cdae_hip_row_stride": (C.c_uint32, [C.c_void_p]),
@@ -859,6 +867,53 @@ class WARP(MF):
 
     def _batch_examples(self, u_begin: int, n_users: int) -> int:
         return 2 * self._pairs(u_begin, u_begin + n_users)
+
+
+@dataclass
+class FISMConfig:
+    """libcf::FISMConfig (the reference's src/model/recsys/fism.hpp:8-20) with its defaults and SGDConfig's learn rate; alpha is a real
+    number here (the reference's is an int).  using_factor_term = False and using_global_mean are not taken over.  batch_users is not in
+    the reference: 1 (and 0) is its loop; a block schedule is not built."""
+    learn_rate: float = 0.1
+    lambda_: float = 0.01
+    lt: int = SQUARE
+    num_dim: int = 10
+    num_neg: int = 5
+    alpha: float = 1.0
+    using_bias_term: bool = True
+    using_adagrad: bool = True
+    batch_users: int = 1
+
+
+class FISM(MF):
+    """Factored item similarity (cdae_hip_create_fism; include/cdae_hip.h has the definition).  P = P_W, Q = P_V, bi = P_BP, bu = P_UB (and
+    their *_AG accumulators); there is no user table.  A user is the sum of the rows of P of a rated set, so recommend_rows, eval_topn_rows,
+    score_rows, full_rank_rows, recommend_rows_filtered (any rated sets) and similar_items (table "input" = P, "output" = Q) serve the handle
+    as CDAE's methods do, beside recommend_all and eval_topn over the train rows."""
+
+    def __init__(self, mcfg: FISMConfig, device: int = 0):
+        self.lib = load_library()
+        self.cfg = mcfg
+        c = _FismConfig(C.sizeof(_FismConfig), mcfg.num_dim, mcfg.num_neg, mcfg.lt, int(mcfg.using_adagrad), int(mcfg.using_bias_term),
+                        mcfg.batch_users, 0, mcfg.lambda_, mcfg.learn_rate, mcfg.alpha)
+        self.h = C.c_void_p()
+        _chk(self.lib, self.lib.cdae_hip_create_fism(C.byref(c), device, C.byref(self.h)))
+        self.num_users = self.num_items = 0
+        self._rec = None
+
+    def plan(self) -> dict:
+        """{resident_rows, window_instances}: rows of a user the training kernel keeps on chip for a visit (0: all stream; 0 before
+        set_interactions), and the instances one launch holds at most"""
+        r, w = C.c_uint32(0), C.c_uint64(0)
+        _chk(self.lib, self.lib.cdae_hip_fism_plan(self.h, C.byref(r), C.byref(w)))
+        return dict(resident_rows=int(r.value), window_instances=int(w.value))
+
+    def set_resident(self, allow: bool):
+        """allow = False: every row streams through memory; both settings give the same bits"""
+        _chk(self.lib, self.lib.cdae_hip_fism_set_resident(self.h, int(bool(allow))))
+
+    def _batch_examples(self, u_begin: int, n_users: int) -> int:
+        return int(self._row_ptr[u_begin + n_users] - self._row_ptr[u_begin]) * (1 + self.cfg.num_neg)
 
 
 def comm_unique_id() -> bytes:

@@ -274,7 +274,8 @@ struct Args {
   uint64_t U = 0, I = 0;
   const int64_t* row_ptr = nullptr; const uint32_t* col = nullptr;
   const int64_t* whole_row_ptr = nullptr;   // sampled item shard: row_ptr of the WHOLE rows (else unused)
-  uint32_t kind = 0;                        // cdae_hip::mf: 0 CDAE, 1 IMF, 2 BPR, 3 WRMF, 4 WARP (sized as BPR with one more sort key: VOID = I)
+  uint32_t kind = 0;                        // cdae_hip::mf: 0 CDAE, 1 IMF, 2 BPR, 3 WRMF, 4 WARP (sized as BPR with one more sort key: VOID = I),
+                                            // 5 FISM (rows checked as for the SGD handles; no example lists, no batch workspace)
   bool mf_seq = false, full_output = false, asymmetric = false, item_shard = false;
   uint32_t batch_users = 0;                 // cdae_hip::B, the default already resolved
   uint32_t K = 0, Kp = 0, num_neg = 0;      // num_neg: HyperParams::num_neg (0 for full output)
@@ -324,7 +325,7 @@ inline std::string build(const Args& a, Plan& p) {
   // (256 CUs x 4 SIMDs) several thousand wavefronts: small batches take small units.
   const uint32_t B = p.B = (uint32_t)std::min<uint64_t>(a.batch_users, U);
   p.unit_pos = B <= 1024 ? 64u : UNIT_POS_MAX;       // measured at ML-10M shape, batch_users 256 / 512: 64 best (profiles/r02_unit_size.txt)
-  if ((uint64_t)B * a.Kp * sizeof(float) > 0x7FFFFFFFull && a.kind != 3u)      // decode addresses z rows with 31-bit byte offsets (buffer loads, cdae_kernels.hpp)
+  if ((uint64_t)B * a.Kp * sizeof(float) > 0x7FFFFFFFull && a.kind != 3u && a.kind != 5u)      // decode addresses z rows with 31-bit byte offsets (buffer loads, cdae_kernels.hpp)
     return refuse("batch_users %u x row stride %u floats exceeds the 2 GiB the batch's Z may occupy; lower batch_users", B, a.Kp);
   const uint64_t nnz = (uint64_t)p.row_ptr[U];
   p.order = popularity_order(p.pop);
@@ -334,6 +335,10 @@ inline std::string build(const Args& a, Plan& p) {
   p.params = param_layout(I, a.Kp, a.asymmetric);
   if (a.kind == 3u) {                       // WRMF: no example lists, no batch workspace
     p.item_major = item_major_csr(U, I, p.row_ptr, p.col, p.pop);
+    p.unit_ptr.assign(U + 1, 0u);
+    return {};
+  }
+  if (a.kind == 5u) {                       // FISM: its loop draws inside the launch and its encode takes whole rows: no lists, no units
     p.unit_ptr.assign(U + 1, 0u);
     return {};
   }

@@ -38,6 +38,7 @@
 #include "cdae_mf_kernels.hpp"
 #include "cdae_als_kernels.hpp"
 #include "cdae_warp_kernels.hpp"
+#include "cdae_fism_kernels.hpp"
 
 #ifdef CDAE_DECODE_TIMING
 #define CDAE_TOUCHED_ARG ((uint32_t*)nullptr)     // the timing build borrows `touched` for its stamps
@@ -300,6 +301,10 @@ struct cdae_hip {
   DevBuf<float> d_warp_l, d_warp_out_margin;
   DevBuf<uint32_t> d_warp_rec_item, d_warp_rec_cnt, d_warp_out_item, d_warp_out_cnt;
   bool warp_record = false;
+  // FISM handles (cdae_hip_create_fism, cdae_fism_kernels.hpp): scale[n] = n^-alpha for n <= num_items (cdae_fism_host.h, filled per data
+  // set: s_pos = scale[n - 1], s_neg = scale[n], serving scale[size of the rated set]); whether the first rows of a visit stay on chip
+  DevBuf<float> d_fism_scale;
+  double fism_alpha = 1.; bool fism_resident = true;
   // Guest table (cdae_hip_set_guest_nodes, cdae_hip_fold_in_rows with install): a second user table, rows wu | wu_ag | uu | uu_ag of
   // [n_guests x Kp] each, that the rows entry points address as CDAE_GUEST_USER(i).  d_fold: the staging rows the fold-in kernel writes
   // (a chunk's, or the whole call's when it installs); installing EXCHANGES the two sets, so a failed call leaves the table as it was.
@@ -354,7 +359,9 @@ struct cdae_hip {
   uint32_t delta_combine = CDAE_COMBINE_SUM;                  // cdae_hip_delta_set_combine: how staged deltas are folded in (cdae_exchange_algebra.h)
   // IMF / BPR handles (cdae_hip_create_mf, cdae_mf_kernels.hpp): 0 = CDAE, 1 = IMF, 2 = BPR; 3 = WRMF by ALS (cdae_hip_create_als):
   // IMF's tables and serving, no sampled step — every training path that asks `mf == 2 ? BPR : IMF` is refused before it is reached;
-  // 4 = WARP (cdae_hip_create_warp): IMF's tables and serving, BPR's batch workspace, its own step (compute_batch_warp)
+  // 4 = WARP (cdae_hip_create_warp): IMF's tables and serving, BPR's batch workspace, its own step (compute_batch_warp);
+  // 5 = FISM (cdae_hip_create_fism): two item tables (an asymmetric handle's W and V), no user table, no example lists, its own loop
+  // (fism_enqueue) and its own encode in front of the sweeps (fism_encode)
   uint32_t mf = 0, mf_bias = 1;
   // IMF / BPR, batch_users = 1 (the library default: the reference's strictly sequential loop): the users are still taken one after the
   // other and every instance still steps the user vector and the item row(s) in place — but LAUNCHES cover MF_SEQ_USERS users: one
@@ -562,7 +569,8 @@ template <class F> void visit_data_set_bufs(cdae_hip* h, F&& f) {
     h->d_sim_q, h->d_sim_iota, h->d_sim_T, h->d_sim_zero,
     h->d_guest[0], h->d_guest[1], h->d_guest[2], h->d_guest[3], h->d_fold[0], h->d_fold[1], h->d_fold[2], h->d_fold[3],
     h->d_fold_long, h->d_als_G, h->d_als_part, h->d_als_x, h->d_als_out,
-    h->d_warp_l, h->d_warp_rec_item, h->d_warp_rec_cnt, h->d_warp_out_item, h->d_warp_out_cnt, h->d_warp_out_margin);
+    h->d_warp_l, h->d_warp_rec_item, h->d_warp_rec_cnt, h->d_warp_out_item, h->d_warp_out_cnt, h->d_warp_out_margin,
+    h->d_fism_scale);
 }
 // Drops every one of them; the first release error is returned after all have been dropped.
 int drop_data_set_bufs(cdae_hip* h) {
@@ -1601,6 +1609,36 @@ int cdae_hip_create_warp(const cdae_warp_config* wc, int device_id, cdae_hip_t**
   return 0;
 }
 
+int cdae_hip_create_fism(const cdae_fism_config* fc, int device_id, cdae_hip_t** out) {
+  if (!fc || !out) return fail("null argument");
+  if (fc->struct_size != sizeof(cdae_fism_config)) return fail("cdae_fism_config size mismatch: got %u, want %zu", fc->struct_size, sizeof(cdae_fism_config));
+  if (fc->batch_users > 1u)
+    return fail("batch_users %u: a FISM block schedule (several users' visits at once) is not built; 0 or 1 is the loop", fc->batch_users);
+  if (fc->loss_type == 1u) return fail("loss_type LOGISTIC (1) is refused: the reference CHECK-aborts on it (loss.hpp:96); SQUARE (0), LOG (2), CROSS_ENTROPY (5)");
+  if (fc->loss_type == 3u)
+    return fail("loss_type HINGE (3) is refused: its gradient jumps, and a FISM trajectory cannot be pinned across the jump; SQUARE (0), LOG (2), CROSS_ENTROPY (5)");
+  if (fc->loss_type != CDAE_LOSS_SQUARE && fc->loss_type != 2u && fc->loss_type != CDAE_LOSS_CROSS_ENTROPY)
+    return fail("loss_type %u unsupported: SQUARE (0), LOG (2), CROSS_ENTROPY (5)", fc->loss_type);
+  if (fc->num_neg == 0) return fail("num_neg must be >= 1");
+  if (!(fc->alpha >= 0.0) || !(fc->alpha <= 64.0)) return fail("alpha must be in [0, 64], got %g", fc->alpha);
+  cdae_hip_config c = cdae_hip_config();
+  c.struct_size = sizeof(c);
+  c.num_dim = fc->num_dim; c.num_neg = fc->num_neg; c.num_corruptions = 1;
+  c.loss_type = CDAE_LOSS_SQUARE;                          // (validated above; the FISM kernel reads hp.loss_type, set below)
+  c.using_adagrad = fc->using_adagrad;
+  c.asymmetric = 1;                                        // two item tables: P = W (what a rated set sums), Q = V (what the sweeps read)
+  c.batch_users = 1u;
+  c.lambda = fc->lambda; c.learn_rate = fc->learn_rate; c.corruption_ratio = 0.;
+  c.beta = 0.;                                             // fism.hpp:119-120, 145, 161 divide by sqrt(acc) alone
+  CHK(cdae_hip_create(&c, device_id, out));
+  cdae_hip* h = *out;
+  h->mf = 5u; h->mf_bias = fc->using_bias_term ? 1u : 0u;
+  h->mf_seq = true; h->B = MF_SEQ_USERS;
+  h->hp.loss_type = fc->loss_type;                         // (hp.lambda is lambda itself: fism.hpp:113-114, 142, 154)
+  h->fism_alpha = fc->alpha;
+  return 0;
+}
+
 uint32_t cdae_hip_row_stride(const cdae_hip_t* h) { return h ? h->Kp : 0; }
 uint32_t cdae_hip_mf_default_batch_users(uint64_t U, uint32_t pairwise) {
   if (pairwise) return U >= CDAE_BPR_DEFAULT_MIN_USERS ? CDAE_BPR_DEFAULT_BATCH_USERS : 1u;
@@ -1768,11 +1806,16 @@ int upload_data_set(cdae_hip* h, const cdae::plan::Plan& p, const int64_t* grp, 
   CHK(h->d_shared.alloc(h->n_shared));
   HIPCHK(hipMemset(h->d_shared, 0, h->n_shared * sizeof(float)));
   const size_t WR = (size_t)h->wu_rows();                   // private rows held here: every user, or an item shard's own user range
-  h->cnt[CDAE_P_WU] = h->cnt[CDAE_P_WU_AG] = WR * h->Kp;
-  CHK(h->d_Wu.alloc(WR * h->Kp));
-  CHK(h->d_Wu_ag.alloc(WR * h->Kp));
-  HIPCHK(hipMemset(h->d_Wu, 0, std::max<size_t>(WR * h->Kp, 1) * sizeof(float)));
-  HIPCHK(hipMemset(h->d_Wu_ag, 0, std::max<size_t>(WR * h->Kp, 1) * sizeof(float)));
+  const bool fism = h->mf == 5u;     // FISM: no user table (CDAE_P_WU stays unallocated), no hidden bias, no example lists
+  if (fism) {
+    h->cnt[CDAE_P_B] = h->cnt[CDAE_P_B_AG] = 0;
+  } else {
+    h->cnt[CDAE_P_WU] = h->cnt[CDAE_P_WU_AG] = WR * h->Kp;
+    CHK(h->d_Wu.alloc(WR * h->Kp));
+    CHK(h->d_Wu_ag.alloc(WR * h->Kp));
+    HIPCHK(hipMemset(h->d_Wu, 0, std::max<size_t>(WR * h->Kp, 1) * sizeof(float)));
+    HIPCHK(hipMemset(h->d_Wu_ag, 0, std::max<size_t>(WR * h->Kp, 1) * sizeof(float)));
+  }
   if (h->cfg.linear_function) {
     h->cnt[CDAE_P_UU] = h->cnt[CDAE_P_UU_AG] = WR * h->Kp;
     CHK(h->d_Uu.alloc(WR * h->Kp));
@@ -1780,7 +1823,8 @@ int upload_data_set(cdae_hip* h, const cdae::plan::Plan& p, const int64_t* grp, 
   }
 
   const bool als = h->mf == 3u;      // WRMF: no example lists, no batch workspace — the item-major CSR of its item half-step instead
-  if (!als) {
+  const bool lists = !als && !fism;
+  if (lists) {
     if (h->shard_sampled()) {
       const size_t gnnz = (size_t)grp[U];
       CHK(h->d_grow_ptr.alloc(U + 1)); CHK(h->d_gcol.alloc(gnnz));
@@ -1853,7 +1897,7 @@ int upload_data_set(cdae_hip* h, const cdae::plan::Plan& p, const int64_t* grp, 
   }
   if (h->mf) {                                              // IMF / BPR / WRMF: the bias arrays (WRMF: the ones IMF's serving reads)
     const uint64_t inst_cap = p.emax * (h->mf == 2 || h->mf == 4 ? h->hp.num_neg : 1u + h->hp.num_neg);
-    if (!als) CHK(h->d_UVpre.alloc((size_t)inst_cap * h->Kp));
+    if (lists) CHK(h->d_UVpre.alloc((size_t)inst_cap * h->Kp));
     CHK(h->d_ub.alloc((size_t)U)); CHK(h->d_ub_ag.alloc((size_t)U));
     h->cnt[CDAE_P_UB] = h->cnt[CDAE_P_UB_AG] = (size_t)U;
     HIPCHK(hipMemset(h->d_ub, 0, (size_t)U * sizeof(float)));
@@ -1867,6 +1911,9 @@ int upload_data_set(cdae_hip* h, const cdae::plan::Plan& p, const int64_t* grp, 
     CHK(h->d_tcol.alloc(nnz));
     HIPCHK(hipMemcpy(h->d_tptr, p.item_major.ptr.data(), (I + 1) * sizeof(int64_t), hipMemcpyHostToDevice));
     if (nnz) HIPCHK(hipMemcpy(h->d_tcol, p.item_major.col.data(), nnz * sizeof(uint32_t), hipMemcpyHostToDevice));
+  } else if (fism) {                                        // FISM: the scale table (cdae_fism_host.h)
+    const std::vector<float> sc = cdae::fism_scale_table(I, h->fism_alpha);
+    CHK(dev_upload(h->d_fism_scale, sc.data(), sc.size()));
   } else {
     h->sort_tmp_bytes = 0;
     HIPCHK(rocprim::radix_sort_pairs(nullptr, h->sort_tmp_bytes, h->ex[0].item.p, h->ex[0].sorted_item.p, h->ex[0].val.p,
@@ -1929,7 +1976,7 @@ int upload_data_set(cdae_hip* h, const cdae::plan::Plan& p, const int64_t* grp, 
   }
   CHK(h->d_touched.alloc((size_t)I));                 // (nothing touches an item of a WRMF handle; the delta entry points read the array)
   HIPCHK(hipMemset(h->d_touched, 0, (size_t)I * sizeof(uint32_t)));
-  if (!als) CHK(h->d_uids.alloc((size_t)B));
+  if (lists) CHK(h->d_uids.alloc((size_t)B));
   // weights 0, accumulators 1e-4 (cdae.hpp:114,...), accumulator pad lanes 1: a well-defined state even
   // before init_params / set_param (a zero accumulator pad would make beta == 0 divide 0 by 0)
   auto fillm = [&](float* M, size_t rows, uint32_t K, uint32_t Kp, float v, float pad) {
@@ -1966,13 +2013,14 @@ int cdae_hip_init_params(cdae_hip_t* h, uint64_t seed) {
   auto fill = [&](float* M, size_t rows, uint32_t K, uint32_t Kp, float v) {     // accumulator pads are 1, others 0
     hipLaunchKernelGGL(fill_matrix_kernel, blocks(rows * Kp), dim3(256), 0, h->stream, M, rows, K, Kp, v, v == 0.f ? 0.f : 1.f);
   };
-  if (h->mf) {                                             // imf.hpp:57-69: Random() * 0.01, accumulators 1e-4, biases 0; wrmf.hpp:47-48: Random() * 0.001
-    const double mf_scale = h->mf == 3u ? 0.001 : 0.01;
+  if (h->mf) {                                             // imf.hpp:57-69: Random() * 0.01, accumulators 1e-4, biases 0; wrmf.hpp:47-48, fism.hpp:66-68: Random() * 0.001
+    const double mf_scale = h->mf == 3u || h->mf == 5u ? 0.001 : 0.01;
     auto init01 = [&](float* M, size_t rows, uint32_t id, uint64_t row0) {
       hipLaunchKernelGGL(init_matrix_kernel, blocks(rows * h->Kp), dim3(256), 0, h->stream, M, rows, h->K, h->Kp,
                          cdae_rng_key(seed, 0, id, CDAE_STREAM_INIT), mf_scale, row0);
     };
-    init01(h->d_Wu, h->U, CDAE_P_WU, h->uid_offset); fill(h->d_Wu_ag, h->U, h->K, h->Kp, 1e-4f);
+    if (h->mf == 5u) { init01(h->P(CDAE_P_V), h->I, CDAE_P_V, 0); fill(h->P(CDAE_P_V_AG), h->I, h->K, h->Kp, 1e-4f); }   // FISM: Q, and no user table
+    else { init01(h->d_Wu, h->U, CDAE_P_WU, h->uid_offset); fill(h->d_Wu_ag, h->U, h->K, h->Kp, 1e-4f); }
     init01(h->P(CDAE_P_W), h->I, CDAE_P_W, 0); fill(h->P(CDAE_P_W_AG), h->I, h->K, h->Kp, 1e-4f);
     fill(h->d_ub, h->U, 1, 1, 0.f); fill(h->d_ub_ag, h->U, 1, 1, 1e-4f);
     fill(h->P(CDAE_P_BP), h->I, 1, 1, 0.f); fill(h->P(CDAE_P_BP_AG), h->I, 1, 1, 1e-4f);
@@ -2087,6 +2135,50 @@ constexpr const char* ALS_EVERY_ROW = "a WRMF handle trains by whole half-steps,
 int als_half_step(cdae_hip* h, uint32_t side);              // (below, beside cdae_hip_als_solve_rows)
 constexpr const char* WARP_NO_LIST = "a WARP handle has no example list before the step: its negatives are searched for in the training "
                                      "launch (cdae_hip_warp_search returns them)";
+
+constexpr const char* FISM_NO_LIST = "a FISM handle has no example list and no batch workspace: its instances are drawn in the training "
+                                     "launch (cdae_hip_train_users runs the loop)";
+constexpr const char* FISM_NO_NODE = "a FISM handle has no user node: its hidden row is a sum over the rated set it is given";
+
+// FISM: the loop over users [u_begin, u_end) (cdae_fism_kernels.hpp) — one launch of ONE workgroup per window of users
+// (cdae_fism_host.h fism_windows), all on the training stream
+int fism_enqueue(cdae_hip* h, uint64_t seed, uint32_t epoch, uint64_t u_begin, uint64_t u_end) {
+  using namespace cdae;
+  if (u_begin > u_end || u_end > h->U) return fail("bad user range [%llu, %llu)", (unsigned long long)u_begin, (unsigned long long)u_end);
+  CHK(join_aux(h));
+  const std::vector<uint64_t> cuts = fism_windows(h->h_row_ptr.data(), u_begin, u_end, h->hp.num_neg, FISM_WINDOW_INSTANCES);
+  const uint32_t res_rows = fism_resident_rows(h->NI, h->fism_resident);
+  for (size_t t = 0; t + 1 < cuts.size(); ++t) {
+    const uint64_t s0 = cuts[t];
+    const uint32_t nb = (uint32_t)(cuts[t + 1] - s0);
+    Prof pr;
+    h->prof_q = h->seq;
+    CHK(pr.begin(h, F_DECODE, h->stream));
+    dispatch_ni(h->NI, [&](auto ni) {
+      constexpr int NI = decltype(ni)::value;
+      auto launch = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3(1), dim3(FISM_WAVES * WAVE), 0, h->stream, h->hp, h->mf_bias, res_rows, (const int64_t*)h->d_row_ptr,
+                           (const uint32_t*)h->d_col, s0, nb, seed, epoch, (const float*)h->d_fism_scale, h->P(CDAE_P_W), h->P(CDAE_P_W_AG),
+                           h->P(CDAE_P_V), h->P(CDAE_P_V_AG), h->P(CDAE_P_BP), h->P(CDAE_P_BP_AG), h->d_ub.p, h->d_ub_ag.p);
+      };
+      if (h->hp.adagrad) launch(fism_user_kernel<NI, true>); else launch(fism_user_kernel<NI, false>);
+    });
+    CHK(pr.end());
+    HIPCHK(hipGetLastError());
+    h->seq++;
+    h->acc_examples += fism_instance_count(h->h_row_ptr.data(), s0, s0 + nb, h->hp.num_neg);
+    h->acc_batches += 1u; h->acc_users += nb;
+  }
+  return 0;
+}
+
+// FISM: z of rows [c0, c0 + nu) of a device CSR into h->d_zeval (nu rows of Kp floats, allocated by the caller)
+int fism_encode(cdae_hip* h, const int64_t* d_ptr, const uint32_t* d_col, uint64_t c0, uint32_t nu) {
+  DISPATCH_NI(h->NI, cdae::fism_encode_rows_kernel, dim3((nu + 3) / 4), dim3(256), 0, h->stream, d_ptr, d_col, c0, nu,
+              (const float*)h->d_fism_scale, (const float*)h->P(CDAE_P_W), h->d_zeval.p);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
 
 int make_plan(cdae_hip* h, uint64_t u_begin, uint64_t u_end, std::vector<Batch>& plan) {
   if (u_begin > u_end || u_end > h->U) return fail("bad user range [%llu, %llu)", (unsigned long long)u_begin, (unsigned long long)u_end);
@@ -2224,6 +2316,7 @@ int drop_prefetched(cdae_hip* h, size_t keep) {
 // sampling + sorting of batch t+1 (prep stream) overlaps the training of batch t (main stream).
 int enqueue_users(cdae_hip* h, uint64_t seed, uint32_t epoch, uint64_t u_begin, uint64_t u_end) {
   if (h->mf == 3u) return fail("%s", ALS_EVERY_ROW);
+  if (h->mf == 5u) return fism_enqueue(h, seed, epoch, u_begin, u_end);
   if (h->item_shard) return fail("an item shard trains in phases under cdae_hip_multi_train_epoch, not on its own");
   std::vector<Batch> plan;
   CHK(make_plan(h, u_begin, u_end, plan));
@@ -2463,6 +2556,10 @@ int recommend_run(cdae_hip* h, uint64_t u_begin, uint64_t u_end, uint32_t topk, 
       DISPATCH_NI(h->NI, cdae::encode_finish_kernel, dim3(1), dim3(256), 0, h->stream, h->hp, h->d_Hpart, (const uint32_t*)h->d_uptr_tmp, h->d_Wu,
                   h->P(CDAE_P_B), (const uint32_t*)nullptr, c0, 1u, 0, h->d_Z, (float*)nullptr, (float*)nullptr, h->d_Uu, (float*)nullptr);
       z = h->d_Z;
+    } else if (h->mf == 5u) {
+      CHK(h->d_zeval.ensure(sweep.chunk, h->Kp));           // FISM: z = n^-alpha * the sum of the train row's rows of P
+      CHK(fism_encode(h, h->d_row_ptr, h->d_col, c0, nu));
+      z = h->d_zeval;
     } else if (h->mf) {
       z = h->d_Wu + (size_t)c0 * h->Kp;           // IMF / BPR: score = ub + ib + uv . iv (imf.hpp:117-119); ub does not rank
     } else {
@@ -2574,6 +2671,7 @@ int cdae_hip_enqueue_users(cdae_hip_t* h, uint64_t seed, uint32_t epoch, uint64_
 int cdae_hip_prefetch_users(cdae_hip_t* h, uint64_t seed, uint32_t epoch, uint64_t u_begin, uint64_t u_end) {
   if (!h || !h->d_shared) return fail("set_interactions must be called first");
   if (h->mf == 3u) return fail("%s", ALS_EVERY_ROW);
+  if (h->mf == 5u) return 0;                               // FISM: nothing is prepared ahead of the loop
   HIPCHK(hipSetDevice(h->device));
   std::vector<Batch> plan;
   CHK(make_plan(h, u_begin, u_end, plan));
@@ -2606,6 +2704,7 @@ int cdae_hip_debug_row_pack(cdae_hip_t* h, uint64_t seed, uint32_t epoch, uint64
   if (!h || !h->d_shared) return fail("set_interactions must be called first");
   if (h->mf == 3u) return fail("%s", ALS_EVERY_ROW);
   if (h->mf == 4u) return fail("%s", WARP_NO_LIST);
+  if (h->mf == 5u) return fail("%s", FISM_NO_LIST);
   const uint32_t hot = decode_hot_rows(h);
   const uint64_t want = packs_rows(h) ? (((uint64_t)h->I - hot + 3) & ~3ull) : 0;
   if (want > *n_records) return fail("the pack has %llu records, the caller's array holds %llu", (unsigned long long)want, (unsigned long long)*n_records);
@@ -2625,6 +2724,7 @@ int cdae_hip_debug_sample_batch(cdae_hip_t* h, uint64_t seed, uint32_t epoch, ui
   if (!h || !h->d_shared) return fail("set_interactions must be called first");
   if (h->mf == 3u) return fail("%s", ALS_EVERY_ROW);
   if (h->mf == 4u) return fail("%s", WARP_NO_LIST);
+  if (h->mf == 5u) return fail("%s", FISM_NO_LIST);
   if (!n_examples) return fail("null argument");
   if (n_users == 0 || u_begin + n_users > h->U) return fail("bad user range [%llu, +%u)", (unsigned long long)u_begin, n_users);
   if (n_users > std::min<uint64_t>(h->B, h->U)) return fail("%u users exceed batch_users %u", n_users, h->B);
@@ -2696,6 +2796,7 @@ int cdae_hip_train_epoch(cdae_hip_t* h, uint64_t seed, uint32_t epoch, cdae_hip_
 
 int cdae_hip_encode(cdae_hip_t* h, uint64_t seed, uint32_t epoch, int mode, const uint32_t* uids, size_t n, float* Z) {
   if (!h || !h->d_shared) return fail("set_interactions must be called first");
+  if (h->mf == 5u) return fail("cdae_hip_encode: %s (cdae_hip_score_rows and cdae_hip_recommend_rows serve it)", FISM_NO_NODE);
   if (h->mf) return fail("cdae_hip_encode does not apply to an IMF / BPR handle");
   if ((!uids || !Z) && n) return fail("null argument");
   if (mode != 0 && mode != 1) return fail("mode must be 0 or 1");
@@ -2819,6 +2920,7 @@ int cdae_hip_recommend_user(cdae_hip_t* h, uint64_t uid, const uint32_t* rated_i
   if (topk == 0 || topk > h->I) return fail("topk must be in [1, num_items]");
   if (n_rated && !rated_items) return fail("null argument");
   if (n_rated + topk > h->I) return fail("%zu rated items leave fewer than topk = %u candidates", n_rated, topk);
+  if (h->mf == 5u) return fail("cdae_hip_recommend_user is not built for a FISM handle: cdae_hip_recommend_rows ranks any rated set as it stands");
   if (h->mf) return fail("cdae_hip_recommend_user does not apply to an IMF / BPR handle (its score does not depend on the rated set)");
   HIPCHK(hipSetDevice(h->device));
   CHK(join_aux(h));
@@ -2874,7 +2976,7 @@ int rows_check_uids(cdae_hip* h, const char* fn, const uint32_t* uids, uint64_t 
 }
 int rows_check(cdae_hip* h, const char* fn, const RowsArgs& a) {
   if (!h) return fail("%s: null handle", fn);
-  if (h->mf) return fail("%s does not apply to an IMF / BPR handle (its score does not depend on the rated set)", fn);
+  if (h->mf && h->mf != 5u) return fail("%s does not apply to an IMF / BPR handle (its score does not depend on the rated set)", fn);
   if (h->item_shard) return fail("%s applies to a whole model, not to an item shard", fn);
   if (!h->d_shared) return fail("%s: cdae_hip_set_interactions first", fn);
   if (a.topk == 0 || a.topk > h->I) return fail("%s: topk must be in [1, num_items]", fn);
@@ -2902,6 +3004,7 @@ int rows_upload(cdae_hip* h, uint64_t R, const uint32_t* uids, const int64_t* ro
 inline uint32_t rows_empty_input(const cdae_hip* h) { return h->hp.keep_thr == 0x100000000ull ? 1u : 0u; }   // cdae.hpp:168-172 (q == 1)
 // ... and z of rows [c0, c0 + nu) of that CSR to h->d_zeval (nu rows of Kp floats, allocated by the caller)
 int rows_encode_chunk(cdae_hip* h, const int64_t* row_ptr, uint64_t c0, uint32_t nu) {
+  if (h->mf == 5u) return fism_encode(h, h->d_rows_ptr, h->d_rows_col, c0, nu);     // FISM: no node, no hidden bias, rows of any length
   const uint32_t empty_input = rows_empty_input(h);
   const float* Gwu = h->n_guests ? h->d_guest[0].p : nullptr;   // the guest table's Wu / Uu rows (uids with the top bit), if there is one
   const float* Guu = h->n_guests ? h->d_guest[2].p : nullptr;
@@ -3239,6 +3342,7 @@ namespace {
 constexpr float NODE_INIT[4] = {0.f, cdae::FOLD_AG_INIT, 1.f, cdae::FOLD_AG_INIT};     // wu | wu_ag | uu | uu_ag of a row without a node
 int fold_check(cdae_hip* h, const char* fn) {
   if (!h) return fail("%s: null handle", fn);
+  if (h->mf == 5u) return fail("%s: %s; there is nothing to fit", fn, FISM_NO_NODE);
   if (h->mf) return fail("%s does not apply to an IMF / BPR handle (its users are trained rows, not input nodes)", fn);
   if (h->item_shard) return fail("%s applies to a whole model, not to an item shard", fn);
   if (!h->d_shared) return fail("%s: cdae_hip_set_interactions first", fn);
@@ -3568,6 +3672,22 @@ int cdae_hip_warp_choices(cdae_hip_t* h, uint32_t* out_item, uint32_t* out_cnt, 
   return 0;
 }
 
+// ---- FISM (cdae_fism_kernels.hpp) ---------------------------------------------------------------------------------------
+int cdae_hip_fism_plan(const cdae_hip_t* h, uint32_t* resident_rows, uint64_t* window_instances) {
+  if (!h) return fail("null handle");
+  if (h->mf != 5u) return fail("cdae_hip_fism_plan applies to a FISM handle (cdae_hip_create_fism)");
+  if (resident_rows) *resident_rows = h->d_shared ? cdae::fism_resident_rows(h->NI, h->fism_resident) : 0u;
+  if (window_instances) *window_instances = cdae::FISM_WINDOW_INSTANCES;
+  return 0;
+}
+
+int cdae_hip_fism_set_resident(cdae_hip_t* h, int allow) {
+  if (!h) return fail("null handle");
+  if (h->mf != 5u) return fail("cdae_hip_fism_set_resident applies to a FISM handle (cdae_hip_create_fism)");
+  h->fism_resident = allow != 0;
+  return 0;
+}
+
 int cdae_hip_als_gram(cdae_hip_t* h, uint32_t side, float* out, size_t count) {
   CHK(als_check(h, "cdae_hip_als_gram"));
   if (side != CDAE_ALS_USERS && side != CDAE_ALS_ITEMS) return fail("cdae_hip_als_gram: side must be CDAE_ALS_USERS or CDAE_ALS_ITEMS");
@@ -3627,6 +3747,7 @@ int cdae_hip_train_one_user_corruption(cdae_hip_t* h, uint64_t uid, const uint32
   if (!h || !h->d_shared) return fail("set_interactions must be called first");
   if (uid >= h->U) return fail("user id %llu out of range", (unsigned long long)uid);
   if (h->cfg.full_output) return fail("train_one_user_corruption takes an explicit negative list; it is not available in full_output mode");
+  if (h->mf == 5u) return fail("train_one_user_corruption: %s", FISM_NO_LIST);
   if (h->mf) return fail("train_one_user_corruption does not apply to an IMF / BPR handle");
   if ((n_in && !input_items) || (n_neg && !negative_items)) return fail("null argument");
   HIPCHK(hipSetDevice(h->device));
@@ -3690,6 +3811,7 @@ int cdae_hip_train_one_user_corruption(cdae_hip_t* h, uint64_t uid, const uint32
 // ---- data-parallel exchange ---------------------------------------------------------------------
 int cdae_hip_delta_begin(cdae_hip_t* h) {
   if (!h || !h->d_shared) return fail("set_interactions must be called first");
+  if (h->mf == 5u) return fail("cdae_hip_delta_begin: %s", cdae_internal::exchange_refusal(h));
   HIPCHK(hipSetDevice(h->device));
   CHK(join_aux(h));
   if (!h->d_base) { CHK(h->d_base.alloc(h->n_shared)); CHK(h->d_delta.alloc(h->n_shared + h->I)); }
@@ -3794,6 +3916,9 @@ int fail(const char* fmt, ...) {
   return 1;
 }
 int device_of(const cdae_hip_t* h) { return h->device; }
+const char* exchange_refusal(const cdae_hip_t* h) {
+  return h->mf == 5u ? "a FISM handle trains alone: its loop is one workgroup on one device, and no delta or exchange schedule is built for it" : nullptr;
+}
 hipStream_t main_stream(cdae_hip_t* h) { return h->stream; }
 hipStream_t aux_stream(cdae_hip_t* h) { return h->aux; }
 uint64_t num_users(const cdae_hip_t* h) { return h->U; }

@@ -21,6 +21,7 @@ namespace cdae_internal {
 int fail(const char* fmt, ...);                 // sets cdae_hip_last_error(), returns 1
 
 int device_of(const cdae_hip_t* h);
+const char* exchange_refusal(const cdae_hip_t* h);   // why this handle takes part in no delta / exchange call (a FISM handle), or nullptr
 hipStream_t main_stream(cdae_hip_t* h);
 hipStream_t aux_stream(cdae_hip_t* h);         // second stream of the handle (full-output path: the b recurrence); idle in the sampled path
 uint64_t num_users(const cdae_hip_t* h);

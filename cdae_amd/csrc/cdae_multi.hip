@@ -141,6 +141,7 @@ void free_exchange(void* p) {
 }
 
 int make_exchange(cdae_hip_t* h, Exchange** out) {
+  if (const char* why = cdae_internal::exchange_refusal(h)) return fail("%s", why);
   if (cdae_internal::exchange_slot(h)) { *out = (Exchange*)cdae_internal::exchange_slot(h); return 0; }
   HIPCHK(hipSetDevice(cdae_internal::device_of(h)));
   Exchange* x = new Exchange();

@@ -93,7 +93,9 @@ extern "C" {
  *     least squares, conjugate gradients per row on the matrix cores
  *     also under 12, the version unchanged (new entry points; nothing existing changed): cdae_warp_config, cdae_hip_create_warp,
  *     cdae_hip_warp_search, cdae_hip_warp_record_choices, cdae_hip_warp_choices, CDAE_WARP_MAX_TRY — WARP: rank-weighted pairwise
- *     matrix factorisation whose negatives are searched for on the device */
+ *     matrix factorisation whose negatives are searched for on the device
+ *     also under 12, the version unchanged (new entry points; nothing existing changed): cdae_fism_config, cdae_hip_create_fism,
+ *     cdae_hip_fism_plan, cdae_hip_fism_set_resident — FISM: factored item similarity, the user's rows kept on chip for a visit */
 #define CDAE_HIP_ABI_VERSION 12
 
 /* numeric values follow libcf::LossType (/root/reference/src/model/loss.hpp:10-18) */
@@ -801,6 +803,64 @@ int cdae_hip_warp_search(cdae_hip_t* h, uint64_t seed, uint32_t epoch, uint64_t 
  * Off by default; off costs nothing.  cdae_hip_warp_choices copies the whole record out (count = nnz * num_neg). */
 int cdae_hip_warp_record_choices(cdae_hip_t* h, uint32_t on);
 int cdae_hip_warp_choices(cdae_hip_t* h, uint32_t* out_item, uint32_t* out_cnt, size_t count);
+
+/* ---- FISM: factored item similarity (Kabbur, Ning, Karypis, "FISM: Factored Item Similarity Models for Top-N Recommender Systems",
+ * KDD'13; the reference's src/model/recsys/fism.hpp), on the same handle type ------------------------------------------------------
+ * A user is the sum of the input rows P[j] of their items, an item is scored against a second table Q: there is no user table.
+ * For users in id order, with R_u in CSR order, n = n_u:
+ *     s_pos = (n - 1)^-alpha, and 0 when n = 1;  s_neg = n^-alpha        fp64 pow, rounded once to fp32 (a table filled by
+ *                                                                         cdae_hip_set_interactions)
+ *     x = sum_{j in R_u} P[j]                                  fp32, at the start of the visit
+ *     for p < n, i = R_u[p]; for k <= num_neg:
+ *         k = 0: item i, label 1, rated, s = s_pos
+ *         k >= 1: item = cdae_sample_negative(key, p * num_neg + (k - 1), row, n, num_items), s = s_neg
+ *                 (the CDAE_STREAM_NEGATIVE key and draw index of IMF; label -1 for LOG, else 0)
+ *         v    = rated ? x - P[i] : x                          fism.hpp:210-216
+ *         pred = [bu[u] + bi[item]] + s * (v . Q[item])        biases only with using_bias_term
+ *         g    = loss'(pred, label)
+ *         bu[u], bi[item] step on g + lambda * b               fism.hpp:113-124
+ *         every j in R_u (j != i when rated): P[j] steps on g * s * Q[item] + lambda * P[j]   (Q[item] before its own step)   :140-149
+ *         Q[item] steps on g * s * v + lambda * Q[item]        :151-164
+ *         x += sum_j (P[j] after - P[j] before)                :148, 165
+ * AdaGrad is acc += grad^2; p -= lr * grad / sqrt(acc) — no beta; with using_adagrad = 0 plain SGD.  cdae_hip_init_params draws P and
+ * Q as Random() * 0.001 (fism.hpp:66, 68) on the init stream with the keys of CDAE_P_W and CDAE_P_V; accumulators 1e-4, biases 0.
+ * ONE deliberate difference from the reference: it keeps x_ as a users x K table built at reset (:70-77), moves x_[u] only by u's own
+ * steps (:165) and reads it in recommend (:183), so x_[u] goes stale with every other user's step on a shared row and is never
+ * refreshed.  Here x is the sum of the CURRENT rows at the start of each visit, carried exactly as above inside the visit, and serving
+ * computes it from the rated set it is given: the paper's algorithm, no user table, servable for rows outside the training set.  There
+ * is no switch for the stale table.  Not taken from the reference: using_factor_term = 0, and using_global_mean (predict never reads it).
+ * Parameters: P = CDAE_P_W / _W_AG, Q = CDAE_P_V / _V_AG, bi = CDAE_P_BP / _BP_AG, bu = CDAE_P_UB / _UB_AG; CDAE_P_WU, _UU and _B are
+ * not allocated.  loss_type: 0 (SQUARE, the default), 2 (LOG), 5 (CROSS_ENTROPY); LOGISTIC and HINGE are refused.  batch_users: 0 or 1,
+ * the loop; a block schedule is not built.
+ * Training: cdae_hip_train_epoch, _train_users (any sub-range) and _enqueue_users run the loop, one launch per window of users holding
+ * at most window_instances instances (a user is never cut); stats.users / examples / batches = users trained, sum (1 + num_neg) n_u,
+ * launches.  data_loss and penalty_loss return 0 as for IMF.  Refused: debug_sample_batch, debug_row_pack, encode,
+ * train_one_user_corruption, fold_in_rows (nothing to fit), recommend_user (cdae_hip_recommend_rows serves any rated set), the delta /
+ * exchange calls, the ALS and WARP calls.
+ * Serving: z = n^-alpha * sum_{j in rated} P[j] (n the size of the rated set; 0 for an empty one), D = Q, b' = bi, through the sweeps
+ * of every list-producing entry point: cdae_hip_recommend_all and _eval_topn (the train rows), _recommend_rows, _eval_topn_rows,
+ * _score_rows, _full_rank_rows, _recommend_rows_filtered (any rated sets; uids are validated and not otherwise read) and
+ * _similar_items (CDAE_ITEMS_INPUT = P, CDAE_ITEMS_OUTPUT = Q).  bu is constant within a row and is left out of served scores.  A
+ * candidate that is in its row's rated set (score_rows, exclude_rated = 0) is scored from the full x, not leave-one-out. */
+typedef struct cdae_fism_config {
+  uint32_t struct_size;      /* sizeof(cdae_fism_config)                                 */
+  uint32_t num_dim;          /* FISMConfig::num_dim (10)                                 */
+  uint32_t num_neg;          /* FISMConfig::num_neg (5)                                  */
+  uint32_t loss_type;        /* CDAE_LOSS_*: 0 (SQUARE, the default), 2, 5               */
+  uint32_t using_adagrad;    /* FISMConfig::using_adagrad (1)                            */
+  uint32_t using_bias_term;  /* FISMConfig::using_bias_term (1)                          */
+  uint32_t batch_users;      /* 0 or 1: the loop                                         */
+  uint32_t reserved;         /* 0                                                        */
+  double lambda;             /* FISMConfig::lambda (0.01)                                */
+  double learn_rate;         /* SGDConfig::learn_rate (0.1)                              */
+  double alpha;              /* FISMConfig::alpha (1); a real number here                */
+} cdae_fism_config;
+int cdae_hip_create_fism(const cdae_fism_config* cfg, int device_id, cdae_hip_t** out);
+/* resident_rows: how many of a user's rows the training kernel keeps on chip for a whole visit at this handle's num_dim (0: every row
+ * streams through memory; 0 before cdae_hip_set_interactions).  window_instances: the instances one launch holds at most. */
+int cdae_hip_fism_plan(const cdae_hip_t* h, uint32_t* resident_rows, uint64_t* window_instances);
+/* allow = 0: every row streams through memory.  Both settings give the same bits (as cdae_hip_set_decode_fused). */
+int cdae_hip_fism_set_resident(cdae_hip_t* h, int allow);
 
 /* ---- library-owned RCCL communicator and exchange schedule (one process per GPU: bench.py --gpus N) -----------------
  * The all-reduce of the staged deltas runs inside the library, on its own communicator and HIP stream, overlapped with the

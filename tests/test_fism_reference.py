@@ -1,0 +1,113 @@
+"""CPU: tests/fism_ref.py, the fp64 restatement of FISM that tests/test_gpu_fism.py holds the device to — the premise of its bound (every
+case's float32 run ends within DRIFT_MAX of the float64 one, so that 2e-4 on the device measures the kernel and not the trajectory), the
+gradients it steps on against finite differences of the loss, and that the restated algorithm learns."""
+import numpy as np
+import pytest
+
+import fism_ref as fr
+
+
+@pytest.mark.parametrize("name", [c[0] for c in fr.CASES])
+def test_the_float32_reference_stays_within_the_drift_premise(name):
+    r = fr.run_free(fr.case(name))
+    print(f"{name}: drift {r['drift']:.2e} (recorded {fr.DRIFTS[name]:.2e}), max |pred| {r['max_abs_pred']:.3g}")
+    assert r["drift"] <= fr.DRIFT_MAX, r
+    assert r["drift"] == pytest.approx(fr.DRIFTS[name], rel=0.05)          # the figure in the file is this run's
+    assert r["max_abs_pred"] < 16.0
+
+
+def test_the_cases_cover_what_the_gpu_test_names():
+    by = {c[0]: c for c in fr.CASES}
+    assert {by[f"d40-K{K}"][2] for K in (1, 64, 65, 128, 129, 256, 257, 512)} == {1, 64, 65, 128, 129, 256, 257, 512}      # both edges of every NI tier
+    assert by["d40-sgd"][4]["adagrad"] is False and by["d40-ce"][4]["loss"] == 5 and by["d40-log"][4]["loss"] == 2
+    assert (by["d40-neg1"][3], by["d40-neg12"][3], by["d12-neg12"][3]) == (1, 12, 12) and by["d40-nobias"][4]["bias"] is False
+    assert [by[n][4]["alpha"] for n in ("d40-alpha0", "d40-alpha05", "d40-alpha1")] == [0.0, 0.5, 1.0]
+    for c in fr.CASES:
+        assert c[4].get("learn_rate", 0.1) in (0.1, 0.03, 0.01) and c[4]["alpha"] == (1.0 if c[0].startswith("seam") or c[0] == "d40-alpha1" else
+                                                                                     0.0 if c[0] == "d40-alpha0" else 0.5)
+    assert sorted(np.diff(fr.fixture_data("ones").train_ptr).tolist())[0] == 1 and max(np.diff(fr.fixture_data("ones").train_ptr)) == 2
+    win = fr.fixture_data("win")
+    assert int(win.train_ptr[-1]) * 6 > fr.WINDOW_INSTANCES
+    for K in (64, 256, 512):
+        C, W = fr.resident_rows(K), fr.WAVES
+        d = fr.fixture_data(f"seam{K}")
+        assert sorted(np.diff(d.train_ptr).tolist()) == sorted((1, 2, W - 1, W, W + 1, C - 1, C, C + 1, 2 * C + 1)) and d.num_items == 2 * C + 200
+    # duplicate negatives inside one user: D12's longest row leaves 3 items for 12 draws per positive
+    d12 = fr.fixture_data("d12")
+    neg = fr.negatives(d12.train_ptr, d12.train_col, 12, 12, 1, 0, 3)
+    assert all(np.unique(row).size < row.size for row in neg)
+
+
+def loss_value(loss, pred, label):
+    if loss == 0:
+        return (label - pred) ** 2
+    assert loss == 5
+    return (1.0 - label) * pred + np.log1p(np.exp(-pred))
+
+
+@pytest.mark.parametrize("loss", [0, 5])
+@pytest.mark.parametrize("rated", [True, False])
+def test_the_gradients_are_the_derivatives_of_the_loss(loss, rated):
+    """P, Q and both biases: the gradient train() steps on against central differences of loss + lambda / 2 |.|^2 (fism.hpp's L2 terms)"""
+    rng = np.random.default_rng(3)
+    I, U, K = 12, 2, 5
+    st = fr.State(rng.normal(0, 0.5, (I, K)), rng.normal(0, 0.5, (I, K)), U, loss=loss, alpha=0.5, lambda_=0.07)
+    st.bi[:] = rng.normal(0, 0.3, I); st.bu[:] = rng.normal(0, 0.3, U)
+    rows = np.array([1, 4, 5, 9, 10])
+    item = 5 if rated else 7
+    g = fr.grads(st, 1, rows, item, rated)
+
+    def numeric(arr, index):
+        h = 1e-6
+        old = arr[index]
+        arr[index] = old + h; up = fr.instance_loss(st, 1, rows, item, rated, loss_value)
+        arr[index] = old - h; dn = fr.instance_loss(st, 1, rows, item, rated, loss_value)
+        arr[index] = old
+        return (up - dn) / (2 * h)
+
+    for r, j in enumerate(g["idx"]):
+        for k in range(K):
+            assert numeric(st.P, (j, k)) == pytest.approx(g["P"][r, k], rel=1e-6, abs=1e-8)
+    if rated:                                              # the rated item's own row is part of no step (j != i)
+        assert item not in g["idx"] and numeric(st.P, (item, 0)) == 0.0
+    for k in range(K):
+        assert numeric(st.Q, (item, k)) == pytest.approx(g["Q"][k], rel=1e-6, abs=1e-8)
+    assert numeric(st.bu, 1) == pytest.approx(g["bu"], rel=1e-6, abs=1e-8)
+    assert numeric(st.bi, item) == pytest.approx(g["bi"], rel=1e-6, abs=1e-8)
+
+
+def recall_at_10(scores, d):
+    hits = total = 0.0
+    users = 0
+    for u in range(d.num_users):
+        test = d.test_col[d.test_ptr[u]:d.test_ptr[u + 1]]
+        if test.size == 0:
+            continue
+        s = scores(u).copy()
+        s[d.train_col[d.train_ptr[u]:d.train_ptr[u + 1]]] = -np.inf
+        top = np.argsort(-s, kind="stable")[:10]
+        total += np.isin(top, test).sum() / test.size
+        users += 1
+    return total / users
+
+
+def test_the_reference_learns_to_rank_held_out_items():
+    """After EPOCHS (two) epochs on "tiny" the fp64 reference ranks held-out items better than popularity does (Recall@10).
+    Two epochs over 300 users are few: from the 1e-3 initial factors AdaGrad's steps shrink as 1 / sqrt(steps taken), and at FISM's
+    default learn rate the item factors have not yet overtaken what the item biases alone (popularity) give.  So this test takes a three
+    times larger rate, 0.3, with the paper's mid alpha 0.5 and K = 16.  Measured (popularity 0.2377), Recall@10 after epoch 1, 2[, 3, 4]:
+      K 16, rate 0.3,  alpha 0.5         0.2207  0.2441     <- this test
+      K 16, rate 0.1,  alpha 0.5         0.2057  0.2271  0.2350  0.2419   (overtakes popularity in its fourth epoch)
+      K 32, rate 0.1,  alpha 0.5         0.2227  0.2389
+      K 16, rate 0.03, alpha 0.5         -       0.2346
+      K 10, rate 0.1,  alpha 1 (defaults) 0.2224  0.2150  0.2186  0.2157
+      K 16, rate 0.1,  alpha 0.5, num_neg 12 / CE / CE and num_neg 12:  0.2184 / 0.2143 / 0.2130 after epoch 2"""
+    d = fr.fixture_data("tiny")
+    st = fr.init_state(d.num_items, d.num_users, 16, fr.PSEED, alpha=0.5, learn_rate=0.3)
+    for ep in range(fr.EPOCHS):
+        fr.train(st, d.train_ptr, d.train_col, 1, ep)
+    pop = np.bincount(d.train_col, minlength=d.num_items).astype(np.float64)
+    r_pop = recall_at_10(lambda u: pop, d)
+    r_fism = recall_at_10(lambda u: st.Q @ fr.hidden(st, d.train_col[d.train_ptr[u]:d.train_ptr[u + 1]]) + st.bi, d)
+    print(f"Recall@10: FISM {r_fism:.4f}, popularity {r_pop:.4f}")
+    assert r_fism > r_pop
