@@ -49,14 +49,17 @@ inline std::string refuse(const char* fmt, ...) {
 }
 
 // Rows: monotone row_ptr, ids below I, strictly ascending inside a row; `sampled` handles (every kind but an item shard, which sees
-// only its slice of every row, and WRMF, which samples nothing) also refuse a row with no item or with every item.  pop[i] = users of item i.
-inline std::string check_rows(uint64_t U, uint64_t I, const int64_t* row_ptr, const uint32_t* col, bool sampled, std::vector<uint64_t>& pop) {
+// only its slice of every row, and WRMF, which samples nothing) also refuse a row with every item and, unless `empty_ok`, a row with no
+// item.  empty_ok is FISM's: a user without train items takes no step there (include/cdae_hip.h), and is served z = 0.
+// pop[i] = users of item i.
+inline std::string check_rows(uint64_t U, uint64_t I, const int64_t* row_ptr, const uint32_t* col, bool sampled, bool empty_ok,
+                              std::vector<uint64_t>& pop) {
   pop.assign(I, 0);
   for (uint64_t u = 0; u < U; ++u) {
     const int64_t a = row_ptr[u], b = row_ptr[u + 1];
     if (b < a) return refuse("row_ptr is not monotone at user %llu", (unsigned long long)u);
     if (sampled) {
-      if (b <= a) return refuse("user %llu has no training item (the reference CHECK-fails too, cdae.hpp:139)", (unsigned long long)u);
+      if (b <= a && !empty_ok) return refuse("user %llu has no training item (the reference CHECK-fails too, cdae.hpp:139)", (unsigned long long)u);
       if ((uint64_t)(b - a) >= I) return refuse("user %llu rated every item: no negative can be sampled", (unsigned long long)u);
     }
     for (int64_t p = a; p < b; ++p) {
@@ -275,7 +278,7 @@ struct Args {
   const int64_t* row_ptr = nullptr; const uint32_t* col = nullptr;
   const int64_t* whole_row_ptr = nullptr;   // sampled item shard: row_ptr of the WHOLE rows (else unused)
   uint32_t kind = 0;                        // cdae_hip::mf: 0 CDAE, 1 IMF, 2 BPR, 3 WRMF, 4 WARP (sized as BPR with one more sort key: VOID = I),
-                                            // 5 FISM (rows checked as for the SGD handles; no example lists, no batch workspace)
+                                            // 5 FISM (rows checked as for the SGD handles, but a row may be empty; no example lists, no batch workspace)
   bool mf_seq = false, full_output = false, asymmetric = false, item_shard = false;
   uint32_t batch_users = 0;                 // cdae_hip::B, the default already resolved
   uint32_t K = 0, Kp = 0, num_neg = 0;      // num_neg: HyperParams::num_neg (0 for full output)
@@ -312,7 +315,7 @@ inline std::string build(const Args& a, Plan& p) {
     if (!e.empty()) return e;
     p.row_ptr = p.act.row_ptr.data(); p.col = p.act.col.data();       // from here on: rows by POSITION
   }
-  std::string e = check_rows(U, I, p.row_ptr, p.col, !a.item_shard && a.kind != 3u, p.pop);
+  std::string e = check_rows(U, I, p.row_ptr, p.col, !a.item_shard && a.kind != 3u, a.kind == 5u, p.pop);
   if (!e.empty()) return e;
   p.own_u0 = a.own_u0; p.own_u1 = a.own_u1;
   if (a.item_shard) {

@@ -10,7 +10,8 @@
 //                                 rows and leaves its column sums of (after - before) in LDS; after one more barrier every wavefront
 //                                 adds them to its copy of x in wavefront order.  Wavefront 0 steps Q[item] and bi[item]; bu is
 //                                 carried by every wavefront and stored by wavefront 0 at the end of the visit.  For k = 0 the owner
-//                                 of P[i] publishes it through LDS first.
+//                                 of P[i] publishes it through LDS first.  A user with no items is passed over before the
+//                                 visit's first load and barrier.
 //   fism_encode_rows_kernel<NI>   serving: z = scale[n] * sum of the rated rows of P, a wavefront per row of a chunk.
 // Summation orders (they do not depend on where a row lives, so res_rows = 0 gives the same bits):
 //   a wavefront sums its rows' contributions in position order from 0.f; the FISM_WAVES sums are added in wavefront order from 0.f;
@@ -71,6 +72,9 @@ fism_user_kernel(HyperParams hp, uint32_t bias_term, uint32_t res_rows /* 0 or F
     const uint64_t uid = u0 + slot;
     const int64_t r0 = row_ptr[uid];
     const uint32_t n = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(row_ptr[uid + 1] - r0));
+    // A user without train items takes no step: no instance, bu[uid] and its accumulator keep their bits, and scale[n - 1] below does
+    // not exist.  n is the same in every wavefront and no barrier of this visit has been reached, so all of them leave together.
+    if (n == 0u) continue;
     const uint32_t* row = col + r0;
     const uint32_t n_res = min(n, res_rows);                   // positions [0, n_res) are resident
     const float s_pos = scale[n - 1u], s_neg = scale[n];

@@ -834,7 +834,10 @@ int cdae_hip_warp_choices(cdae_hip_t* h, uint32_t* out_item, uint32_t* out_cnt, 
  * the loop; a block schedule is not built.
  * Training: cdae_hip_train_epoch, _train_users (any sub-range) and _enqueue_users run the loop, one launch per window of users holding
  * at most window_instances instances (a user is never cut); stats.users / examples / batches = users trained, sum (1 + num_neg) n_u,
- * launches.  data_loss and penalty_loss return 0 as for IMF.  Refused: debug_sample_batch, debug_row_pack, encode,
+ * launches.  cdae_hip_set_interactions accepts rows without items on a FISM handle (a row with every item is refused as for the SGD
+ * handles).  A user without train items (n = 0; s_pos does not exist) takes no step: it is counted in stats.users, adds 0 to
+ * stats.examples, and bu[u] and its accumulator keep their bits; the kernel passes it over before the visit's first load, and a window
+ * of such users alone is still one launch.  data_loss and penalty_loss return 0 as for IMF.  Refused: debug_sample_batch, debug_row_pack, encode,
  * train_one_user_corruption, fold_in_rows (nothing to fit), recommend_user (cdae_hip_recommend_rows serves any rated set), the delta /
  * exchange calls, the ALS and WARP calls.
  * Serving: z = n^-alpha * sum_{j in rated} P[j] (n the size of the rated set; 0 for an empty one), D = Q, b' = bi, through the sweeps

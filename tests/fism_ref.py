@@ -3,7 +3,8 @@ that description.  The project's streams (include/cdae_rng.h) are the ones tests
 
   init_state(I, U, K, seed, **hyper)      the state cdae_hip_init_params(seed) leaves
   train(st, ptr, col, seed, epoch, ...)   one epoch of the loop over users in id order (or a sub-range)
-  hidden(st, rated)                       z of a rated set: n^-alpha * the sum of its rows of P
+  negatives(...), candidates(...)         a user's drawn negatives, and the 32 candidates behind each of them
+  hidden(st, rated)                     z of a rated set: n^-alpha * the sum of its rows of P
   grads(st, u, rows, item, rated)         the gradients one instance steps on, for the finite-difference check
 
 A state holds P, Pa, Q, Qa [I, K], bi, bia [I], bu, bua [U] as float64 (or, for the drift measure, all float32) and the hyper-parameters.
@@ -12,7 +13,7 @@ import functools
 
 import numpy as np
 
-from warp_ref import rng_key, sample_negatives, init_table, loss_grad, STREAM_NEGATIVE
+from warp_ref import rng_key, rng_draw, sample_negatives, init_table, loss_grad, STREAM_NEGATIVE, NEG_MAX_TRY
 
 P_W, P_V = 0, 2
 WAVES = 8                        # FISM_WAVES (cdae_amd/csrc/cdae_fism_host.h)
@@ -77,6 +78,15 @@ def negatives(ptr, col, num_items, num_neg, seed, epoch, u):
     key = rng_key(seed, epoch, u, STREAM_NEGATIVE)
     return sample_negatives(np.full(m, key, dtype=np.uint64), np.arange(m, dtype=np.uint64), np.zeros(m, dtype=np.int64), rated,
                             num_items).reshape(row.size, num_neg)
+
+
+def candidates(ptr, col, num_items, num_neg, seed, epoch, u):
+    """cand[p][k][t]: the NEG_MAX_TRY candidates of draw p * num_neg + k of user u, none rejected yet (include/cdae_rng.h, in Python
+    integers).  negatives() is the first of them the user has not rated, or the walk from the last when all are rated."""
+    n = int(ptr[u + 1] - ptr[u])
+    key = rng_key(seed, epoch, u, STREAM_NEGATIVE)
+    return np.array([[[(rng_draw(key, (p * num_neg + k) * NEG_MAX_TRY + t) * num_items) >> 32 for t in range(NEG_MAX_TRY)]
+                      for k in range(num_neg)] for p in range(n)], dtype=np.int64).reshape(n, num_neg, NEG_MAX_TRY)
 
 
 def neg_label(loss):
@@ -170,6 +180,9 @@ def seam_lengths(K):
     return (1, 2, WAVES - 1, WAVES, WAVES + 1, C - 1, C, C + 1, 2 * C + 1)
 
 
+GAPS_LENGTHS = (0, 3, 0, 0, 8, 5, 0, 9, 2, 7, 0)
+
+
 @functools.lru_cache(maxsize=None)
 def fixture_data(name):
     import mf_conflict_ref
@@ -184,6 +197,10 @@ def fixture_data(name):
         return rows_data((1, 2, 1, 1, 2, 2, 1), 9)
     if name == "win":                    # 2 754 instances at num_neg 5: more than one launch window
         return rows_data((17, 9, 22, 14, 30, 11, 25, 19, 8, 27, 13, 21, 16, 29, 10, 24, 18, 12, 26, 15, 23, 20, 9, 11), 60)
+    if name == "gaps":                   # users without train items: the first, the last, two in a row, one between trained users
+        return rows_data(GAPS_LENGTHS, 12)
+    if name == "dense":                  # two users have rated 11 of 12 items: draws whose 32 candidates are all rated take the walk
+        return rows_data((11, 4, 0, 10, 1, 11), 12)
     if name.startswith("seam"):          # seam64 / seam256 / seam512
         K = int(name[4:])
         return rows_data(seam_lengths(K), 2 * resident_rows(K) + 200)
@@ -276,4 +293,16 @@ _case("win", "win", 64, 5, {'alpha': 0.5, 'learn_rate': 0.03}, 1, 2.30e-05)
 _case("seam64", "seam64", 64, 5, {'alpha': 1.0, 'learn_rate': 0.03}, 1, 4.89e-06)
 _case("seam256", "seam256", 256, 5, {'alpha': 1.0, 'learn_rate': 0.03}, 1, 2.63e-06)
 _case("seam512", "seam512", 512, 5, {'alpha': 1.0, 'learn_rate': 0.03}, 1, 1.45e-06)
+_case("gaps-K24", "gaps", 24, 5, {'alpha': 0.5}, 1, 1.05e-05)
+_case("gaps-K200", "gaps", 200, 5, {'alpha': 0.5, 'learn_rate': 0.03}, 1, 2.07e-05)
+_case("dense", "dense", 24, 5, {'alpha': 0.5}, 1, 4.88e-06)
+_case("d12-neg64", "d12", 24, 64, {'alpha': 0.5}, 1, 3.36e-05)
+_case("d12-neg65", "d12", 24, 65, {'alpha': 0.5}, 1, 3.96e-05)
+_case("d12-neg130", "d12", 24, 130, {'alpha': 0.5, 'learn_rate': 0.03}, 2, 3.68e-05)
+_case("d40-neg65", "d40", 200, 65, {'alpha': 0.5, 'learn_rate': 0.01}, 2, 4.88e-05)
+_case("d40-sgd-K64", "d40", 64, 5, {'adagrad': False, 'alpha': 0.5}, 1, 7.36e-07)
+_case("d40-sgd-K128", "d40", 128, 5, {'adagrad': False, 'alpha': 0.5}, 1, 7.03e-07)
+_case("d40-sgd-K512", "d40", 512, 5, {'adagrad': False, 'alpha': 0.5}, 1, 7.65e-07)
+_case("d40-nobias-K64", "d40", 64, 5, {'bias': False, 'alpha': 0.5, 'learn_rate': 0.03}, 1, 7.47e-06)
+_case("d40-nobias-K512", "d40", 512, 5, {'bias': False, 'alpha': 0.5, 'learn_rate': 0.03}, 1, 1.30e-05)
 # CASES-END

@@ -14,14 +14,14 @@ P_COUNT = 14
 # ---- the rules ----------------------------------------------------------------------------------------------------------------------
 
 
-def check_rows(U, I, ptr, col, sampled):
+def check_rows(U, I, ptr, col, sampled, empty_ok=False):
     """(refusal or None, popularity): the first offence in user order, inside a row in position order"""
     pop = np.zeros(I, np.uint64)
     for u in range(U):
         a, b = int(ptr[u]), int(ptr[u + 1])
         if b < a:
             return f"row_ptr is not monotone at user {u}", pop
-        if sampled and b <= a:
+        if sampled and b <= a and not empty_ok:          # (FISM: such a user takes no step)
             return f"user {u} has no training item (the reference CHECK-fails too, cdae.hpp:139)", pop
         if sampled and b - a >= I:
             return f"user {u} rated every item: no negative can be sampled", pop
@@ -158,7 +158,7 @@ def plan(L, **kw):
         perm = activity_order(U, B0, ptr)
         ptr, col = permute_rows(ptr, col, perm)
         p.update(user_perm=perm, user_inv=inverse(perm), perm_ptr=ptr, perm_col=col, permuted=1)
-    refusal, pop = check_rows(U, I, ptr, col, not a["item_shard"] and kind != 3)
+    refusal, pop = check_rows(U, I, ptr, col, not a["item_shard"] and kind != 3, kind == 5)
     if refusal:
         return refusal
     own_u0, own_u1 = a["own_u0"], a["own_u1"]
@@ -171,7 +171,7 @@ def plan(L, **kw):
         return "whole-row row_ptr[0] must be 0"
     B = min(B0, U)
     unit_pos = 64 if B <= 1024 else L["UNIT_POS_MAX"]
-    if B * a["Kp"] * 4 > 0x7FFFFFFF and kind != 3:
+    if B * a["Kp"] * 4 > 0x7FFFFFFF and kind not in (3, 5):
         return f"batch_users {B} x row stride {a['Kp']} floats exceeds the 2 GiB the batch's Z may occupy; lower batch_users"
     nnz = int(ptr[U])
     order = popularity_order(pop)
@@ -184,6 +184,8 @@ def plan(L, **kw):
     if kind == 3:
         tptr, tcol = item_major(U, I, ptr, col, pop)
         return dict(p, tptr=tptr, tcol=tcol, unit_ptr=np.zeros(U + 1, np.uint32))
+    if kind == 5:                                  # FISM: no example lists, no units
+        return dict(p, unit_ptr=np.zeros(U + 1, np.uint32))
     emax = window_max(ptr, U, B)
     ex_per_pos = 2 * a["num_neg"] if kind == 2 else 1 + a["num_neg"]
     Ecap = emax * ex_per_pos

@@ -304,5 +304,10 @@ def test_the_kinds_exempt_from_the_row_refusals(sl):
     assert both(sl, rows, 3, batch_users=2, item_shard=1, full_output=1, num_neg=0)["pop"].tolist() == [1, 1, 1]
     assert both(sl, rows, 3, kind=3, mf_seq=1, batch_users=256)["pop"].tolist() == [1, 1, 1]
     assert isinstance(sl.plan(U=2, I=3, row_ptr=csr(rows)[0], col=csr(rows)[1], Kp=64, batch_users=2, kind=1), str)
+    # FISM: a user without train items takes no step, so a row may be empty; a full one leaves no negative to draw and is refused
+    p = both(sl, [[], [0, 1], [], []], 3, kind=5, mf_seq=1, asymmetric=1, batch_users=1)
+    assert p["pop"].tolist() == [1, 1, 0] and p["unit_ptr"].tolist() == [0] * 5 and (p["Ecap"], p["unit_cap"]) == (0, 0)
+    kw = dict(U=2, I=3, row_ptr=csr(rows)[0], col=csr(rows)[1], K=24, Kp=64, num_neg=5, batch_users=1, kind=5, mf_seq=1, asymmetric=1)
+    assert sl.plan(**kw) == "user 1 rated every item: no negative can be sampled" == pr.plan(sl.limits, **kw)
     # the 2 GiB limit is on the largest batch, not on batch_users: fewer users than that are fine
     assert both(sl, [[0]] * 1023, 2, batch_users=1 << 20, Kp=1 << 19)["B"] == 1023

@@ -1,6 +1,8 @@
 """CPU: tests/fism_ref.py, the fp64 restatement of FISM that tests/test_gpu_fism.py holds the device to — the premise of its bound (every
 case's float32 run ends within DRIFT_MAX of the float64 one, so that 2e-4 on the device measures the kernel and not the trajectory), the
-gradients it steps on against finite differences of the loss, and that the restated algorithm learns."""
+gradients it steps on against finite differences of the loss, and that the restated algorithm learns.  Also what the fixtures are
+for: the empty rows of "gaps", the draws of "dense" that reach the walk behind 32 rejected candidates, the second round of negatives at
+num_neg 65 and 130 — and that a trajectory with either draw done wrong ends far outside the device bound on every table."""
 import numpy as np
 import pytest
 
@@ -36,6 +38,87 @@ def test_the_cases_cover_what_the_gpu_test_names():
     d12 = fr.fixture_data("d12")
     neg = fr.negatives(d12.train_ptr, d12.train_col, 12, 12, 1, 0, 3)
     assert all(np.unique(row).size < row.size for row in neg)
+    # users without train items: the first, the last, two in a row, one between trained users; at NI = 1 and at NI = 4
+    lens = np.diff(fr.fixture_data("gaps").train_ptr).tolist()
+    assert tuple(lens) == fr.GAPS_LENGTHS and lens[0] == 0 and lens[-1] == 0
+    assert any(a == 0 and b == 0 for a, b in zip(lens, lens[1:])) and any(a > 0 and b == 0 and c > 0 for a, b, c in zip(lens, lens[1:], lens[2:]))
+    assert (by["gaps-K24"][1:4], by["gaps-K200"][1:4]) == (("gaps", 24, 5), ("gaps", 200, 5))
+    # rows that leave one item to draw from
+    assert sorted(np.diff(fr.fixture_data("dense").train_ptr).tolist()) == [0, 1, 4, 10, 11, 11] and fr.fixture_data("dense").num_items == 12
+    assert by["dense"][1:4] == ("dense", 24, 5)
+    # the second round of the 64 negatives a wavefront draws at once: a full round, one more, two rounds and two more; at NI = 1 and NI = 4
+    assert [by[n][1:4] for n in REFILL + ("d12-neg64",)] == [("d12", 24, 65), ("d12", 24, 130), ("d40", 200, 65), ("d12", 24, 64)]
+    # plain SGD and no bias terms at the other three NI tiers (K = 200 has them above)
+    for K in (64, 128, 512):
+        assert by[f"d40-sgd-K{K}"][1:4] == ("d40", K, 5) and by[f"d40-sgd-K{K}"][4]["adagrad"] is False
+    for K in (64, 512):
+        assert by[f"d40-nobias-K{K}"][1:4] == ("d40", K, 5) and by[f"d40-nobias-K{K}"][4]["bias"] is False
+
+
+REFILL = ("d12-neg65", "d12-neg130", "d40-neg65")          # num_neg above the 64 negatives one round holds
+ROUND = 64
+
+
+@pytest.mark.parametrize("name", REFILL)
+def test_a_kernel_that_replays_its_first_round_draws_other_items(name):
+    """at the case's seed, in both epochs, every user has a positive p and a k >= 64 whose negative is not the one of k % 64"""
+    _, ds, K, nn, hyper, sseed = fr.case(name)
+    d = fr.fixture_data(ds)
+    for ep in range(fr.EPOCHS):
+        for u in range(d.num_users):
+            neg = fr.negatives(d.train_ptr, d.train_col, d.num_items, nn, sseed, ep, u)
+            assert neg.shape == (d.train_ptr[u + 1] - d.train_ptr[u], nn)
+            assert (neg[:, ROUND:] != neg[:, np.arange(ROUND, nn) % ROUND]).any(), (ep, u)
+
+
+def without_the_walk(ptr, col, num_items, num_neg, seed, epoch, u):
+    """fr.negatives, wrong: a draw whose 32 candidates are all rated keeps the last of them -> (negatives, such draws)"""
+    cand = fr.candidates(ptr, col, num_items, num_neg, seed, epoch, u)
+    rated = np.isin(cand, col[ptr[u]:ptr[u + 1]])
+    first = np.where(rated.all(axis=2), cand.shape[2] - 1, np.argmin(rated, axis=2))
+    return np.take_along_axis(cand, first[:, :, None], axis=2)[:, :, 0], int(rated.all(axis=2).sum())
+
+
+def test_dense_rows_send_draws_to_the_walk():
+    """in each epoch of "dense" at least one draw finds all 32 candidates rated; every other draw is the first unrated candidate, and a
+    walked one is an unrated item that is not the last candidate"""
+    _, ds, K, nn, hyper, sseed = fr.case("dense")
+    d = fr.fixture_data(ds)
+    for ep in range(fr.EPOCHS):
+        walked = 0
+        for u in range(d.num_users):
+            row = d.train_col[d.train_ptr[u]:d.train_ptr[u + 1]]
+            neg = fr.negatives(d.train_ptr, d.train_col, d.num_items, nn, sseed, ep, u)
+            wrong, w = without_the_walk(d.train_ptr, d.train_col, d.num_items, nn, sseed, ep, u)
+            assert int((neg != wrong).sum()) == w and not np.isin(neg, row).any()
+            walked += w
+        print(f"dense, epoch {ep}: {walked} draws take the walk")
+        assert walked >= 1
+
+
+@pytest.mark.parametrize("name", REFILL + ("dense",))
+def test_the_fixtures_tell_a_wrong_draw_from_the_right_one(name, monkeypatch):
+    """The fp64 reference with wrong negatives — the first round replayed (neg[:, k] = neg[:, k % 64]), or for "dense" the last rejected
+    candidate kept instead of the walk — ends at least 10 x BOUND from the reference on every one of the six tables: a kernel with either
+    fault cannot pass test_gpu_fism.py's bound on any table."""
+    c = fr.case(name)
+    d = fr.fixture_data(c[1])
+    right = fr.reference(name)
+    true_negatives = fr.negatives
+
+    def wrong(ptr, col, num_items, num_neg, seed, epoch, u):
+        if name == "dense":
+            return without_the_walk(ptr, col, num_items, num_neg, seed, epoch, u)[0]
+        neg = true_negatives(ptr, col, num_items, num_neg, seed, epoch, u)
+        return neg[:, np.arange(num_neg) % ROUND]
+
+    monkeypatch.setattr(fr, "negatives", wrong)
+    st = fr.new_state(c)
+    for ep in range(fr.EPOCHS):
+        fr.train(st, d.train_ptr, d.train_col, c[5], ep)
+    dist = {n: fr.measure(getattr(st, n), getattr(right, n)) for n in fr.State.TABLES}
+    print(f"{name}: " + ", ".join(f"{n} {e:.2e}" for n, e in dist.items()))
+    assert min(dist.values()) >= 10 * fr.BOUND, dist
 
 
 def loss_value(loss, pred, label):

@@ -3,7 +3,8 @@ z = n^-alpha * (sum of the rated rows of P) is integer-valued and every score z 
 (helpers.assert_fp32_exact, the condition tests/test_gpu_rank_exact.py relies on): alpha = 0 with rated sets of any size, alpha = 1 with
 sets of 2, 4, 8, 16 items and P in multiples of 16.  Every list, score, rank and TOPN figure must then equal the numpy rules of the
 existing reference helpers (helpers.rank_total_order, filtered_ref, score_rows_ref, full_rank_ref, similar_ref, oracle.eval_topn) bit for
-bit.  bu is set to non-zero values and must not show in any served score.  One test holds the refusals of a FISM handle.
+bit.  bu is set to non-zero values and must not show in any served score.  One test holds the refusals of a FISM handle, one the train
+rows without items that a FISM handle accepts.
 """
 import numpy as np
 import pytest
@@ -143,6 +144,24 @@ def test_every_served_entry_point_is_exact(K, alpha):
         gi, gs = m.recommend_rows_filtered(ptr, col, topk=12, with_scores=True, **kw)
         np.testing.assert_array_equal(gi, wi, err_msg=str(kw.keys()))
         np.testing.assert_array_equal(gs, ws, err_msg=str(kw.keys()))
+
+
+@pytest.mark.parametrize("K", (64, 257))
+def test_train_rows_without_items_are_served_their_biases(K):
+    """a FISM handle takes train rows without items (the first, the last, two in a row): z = 0, so recommend_all ranks bi alone for them
+    and every other user's list is what it was"""
+    U, alpha = 11, 0.0
+    full = make_data(alpha, U, seed=K)
+    rows = [r if u not in (0, 4, 5, U - 1) else r[:0] for u, r in enumerate(rows_of(full))]
+    ptr, col = filtered_ref.csr(rows)
+    d = synth.Interactions(U, I, ptr.astype(np.int64), col.astype(np.uint32), np.zeros(U + 1, np.int64), np.empty(0, np.uint32))
+    t = int_tables(K, U, seed=K + 1)
+    m = model(K, alpha, d, t)
+    S = expected_scores(t, alpha, rows)
+    np.testing.assert_array_equal(S[0], t["bi"].astype(np.int64))
+    want = rank_total_order(S, d.train_ptr, d.train_col, 17)
+    for topk in (10, 17):
+        np.testing.assert_array_equal(m.recommend_all(topk), want[:, :topk], err_msg=f"recommend_all topk {topk}")
 
 
 def pow2_table(K, seed, value):

@@ -31,6 +31,15 @@ SPECS = [(f"d40-K{K}", "d40", K, 5, A) for K in (1, 64, 65, 128, 129, 256, 257, 
     ("seam64", "seam64", 64, 5, dict(alpha=1.0)),
     ("seam256", "seam256", 256, 5, dict(alpha=1.0)),
     ("seam512", "seam512", 512, 5, dict(alpha=1.0)),
+    ("gaps-K24", "gaps", 24, 5, A),
+    ("gaps-K200", "gaps", 200, 5, A),
+    ("dense", "dense", 24, 5, A),
+    ("d12-neg64", "d12", 24, 64, A),
+    ("d12-neg65", "d12", 24, 65, A),
+    ("d12-neg130", "d12", 24, 130, A),
+    ("d40-neg65", "d40", 200, 65, A),
+] + [(f"d40-sgd-K{K}", "d40", K, 5, dict(adagrad=False, alpha=0.5)) for K in (64, 128, 512)] + [
+    (f"d40-nobias-K{K}", "d40", K, 5, dict(bias=False, alpha=0.5)) for K in (64, 512)
 ]
 RATES = (0.1, 0.03, 0.01)
 SEEDS = (1, 2, 3)
