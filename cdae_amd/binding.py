@@ -100,6 +100,7 @@ EXPORTS = {
     "cdae_hip_warp_record_choices": (C.c_int, [C.c_void_p, C.c_uint32]),
     "cdae_hip_warp_choices": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]),
     "cdae_hip_create_fism": (C.c_int, [C.POINTER(_FismConfig), C.c_int, C.POINTER(C.c_void_p)]),
+    "cdae_hip_create_fism_pair": (C.c_int, [C.POINTER(_FismConfig), C.c_int, C.POINTER(C.c_void_p)]),
     "cdae_hip_fism_plan": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]),
     "cdae_hip_fism_set_resident": (C.c_int, [C.c_void_p, C.c_int]),
     "cdae_hip_destroy": (C.c_int, [C.c_void_p]),
@@ -891,13 +892,15 @@ class FISM(MF):
     score_rows, full_rank_rows, recommend_rows_filtered (any rated sets) and similar_items (table "input" = P, "output" = Q) serve the handle
     as CDAE's methods do, beside recommend_all and eval_topn over the train rows."""
 
+    _create = "cdae_hip_create_fism"
+
     def __init__(self, mcfg: FISMConfig, device: int = 0):
         self.lib = load_library()
         self.cfg = mcfg
         c = _FismConfig(C.sizeof(_FismConfig), mcfg.num_dim, mcfg.num_neg, mcfg.lt, int(mcfg.using_adagrad), int(mcfg.using_bias_term),
                         mcfg.batch_users, 0, mcfg.lambda_, mcfg.learn_rate, mcfg.alpha)
         self.h = C.c_void_p()
-        _chk(self.lib, self.lib.cdae_hip_create_fism(C.byref(c), device, C.byref(self.h)))
+        _chk(self.lib, getattr(self.lib, self._create)(C.byref(c), device, C.byref(self.h)))
         self.num_users = self.num_items = 0
         self._rec = None
 
@@ -914,6 +917,26 @@ class FISM(MF):
 
     def _batch_examples(self, u_begin: int, n_users: int) -> int:
         return int(self._row_ptr[u_begin + n_users] - self._row_ptr[u_begin]) * (1 + self.cfg.num_neg)
+
+
+@dataclass
+class FISMPConfig(FISMConfig):
+    """libcf::FISMPConfig (the reference's src/model/recsys/fism_pair.hpp) with its defaults: lambda 0.01, SQUARE, 10 dimensions, 5 negatives,
+    alpha 1, AdaGrad, bias terms.  lt is SQUARE (the paper's (1 - d)^2) or LOG (the BPR criterion on the difference); CROSS_ENTROPY is
+    refused, its gradient at label 1 being LOG's."""
+
+
+class FISMP(FISM):
+    """FISMauc, the pairwise form of FISM (cdae_hip_create_fism_pair; include/cdae_hip.h has the definition): a FISM handle in everything
+    but its training loop, which steps on pairs (rated item, drawn negative) of one shared neighbourhood vector.  There is no user bias:
+    P_UB / P_UB_AG are not allocated.  stats.examples counts pairs, num_neg per stored interaction."""
+    _create = "cdae_hip_create_fism_pair"
+
+    def __init__(self, mcfg: FISMPConfig, device: int = 0):
+        super().__init__(mcfg, device)
+
+    def _batch_examples(self, u_begin: int, n_users: int) -> int:
+        return int(self._row_ptr[u_begin + n_users] - self._row_ptr[u_begin]) * self.cfg.num_neg
 
 
 def comm_unique_id() -> bytes:

@@ -1,6 +1,6 @@
 // cdae_fism_host.h — the arithmetic of a FISM handle (cdae_fism_kernels.hpp) that runs on the host or on both sides:
-// the scale table, the residency plan, the launch windows and the instance count.  Plain C++ with no HIP header, so
-// src/fism_check.cpp compiles it with the host sanitizers.
+// the scale table, the residency plan, the launch windows and the instance count; for the pairwise handle (§8n) the pair count and the
+// windows in pairs.  Plain C++ with no HIP header, so src/fism_check.cpp and src/fism_pair_check.cpp compile it with the host sanitizers.
 #pragma once
 #include <stdint.h>
 
@@ -44,6 +44,26 @@ inline std::vector<uint64_t> fism_windows(const int64_t* row_ptr, uint64_t u_beg
   while (u < u_end) {
     uint64_t e = u + 1;
     while (e < u_end && fism_instance_count(row_ptr, u, e + 1, num_neg) <= cap) ++e;
+    cuts.push_back(e);
+    u = e;
+  }
+  return cuts;
+}
+
+// ---- the pairwise handle (cdae_hip_create_fism_pair, cdae_fism_pair_kernels.hpp) ---------------------------------------
+// pairs of rows [r_begin, r_end) of a CSR: num_neg per stored interaction
+inline uint64_t fism_pair_count(const int64_t* row_ptr, uint64_t r_begin, uint64_t r_end, uint32_t num_neg) {
+  return (uint64_t)(row_ptr[r_end] - row_ptr[r_begin]) * (uint64_t)num_neg;
+}
+
+// The launch windows of users [u_begin, u_end) in pairs: fism_windows with the pair count.  A window takes users while its pairs stay
+// within `cap`, and always at least one (a user is never cut).
+inline std::vector<uint64_t> fism_pair_windows(const int64_t* row_ptr, uint64_t u_begin, uint64_t u_end, uint32_t num_neg, uint64_t cap) {
+  std::vector<uint64_t> cuts{u_begin};
+  uint64_t u = u_begin;
+  while (u < u_end) {
+    uint64_t e = u + 1;
+    while (e < u_end && fism_pair_count(row_ptr, u, e + 1, num_neg) <= cap) ++e;
     cuts.push_back(e);
     u = e;
   }

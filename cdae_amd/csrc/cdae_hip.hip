@@ -39,6 +39,7 @@
 #include "cdae_als_kernels.hpp"
 #include "cdae_warp_kernels.hpp"
 #include "cdae_fism_kernels.hpp"
+#include "cdae_fism_pair_kernels.hpp"
 
 #ifdef CDAE_DECODE_TIMING
 #define CDAE_TOUCHED_ARG ((uint32_t*)nullptr)     // the timing build borrows `touched` for its stamps
@@ -305,6 +306,7 @@ struct cdae_hip {
   // set: s_pos = scale[n - 1], s_neg = scale[n], serving scale[size of the rated set]); whether the first rows of a visit stay on chip
   DevBuf<float> d_fism_scale;
   double fism_alpha = 1.; bool fism_resident = true;
+  bool fism_pair = false;        // FISMauc (cdae_hip_create_fism_pair, cdae_fism_pair_kernels.hpp): the pair loop; no user bias is allocated
   // Guest table (cdae_hip_set_guest_nodes, cdae_hip_fold_in_rows with install): a second user table, rows wu | wu_ag | uu | uu_ag of
   // [n_guests x Kp] each, that the rows entry points address as CDAE_GUEST_USER(i).  d_fold: the staging rows the fold-in kernel writes
   // (a chunk's, or the whole call's when it installs); installing EXCHANGES the two sets, so a failed call leaves the table as it was.
@@ -361,7 +363,7 @@ struct cdae_hip {
   // IMF's tables and serving, no sampled step — every training path that asks `mf == 2 ? BPR : IMF` is refused before it is reached;
   // 4 = WARP (cdae_hip_create_warp): IMF's tables and serving, BPR's batch workspace, its own step (compute_batch_warp);
   // 5 = FISM (cdae_hip_create_fism): two item tables (an asymmetric handle's W and V), no user table, no example lists, its own loop
-  // (fism_enqueue) and its own encode in front of the sweeps (fism_encode)
+  // (fism_enqueue) and its own encode in front of the sweeps (fism_encode); with fism_pair (cdae_hip_create_fism_pair) the pair loop
   uint32_t mf = 0, mf_bias = 1;
   // IMF / BPR, batch_users = 1 (the library default: the reference's strictly sequential loop): the users are still taken one after the
   // other and every instance still steps the user vector and the item row(s) in place — but LAUNCHES cover MF_SEQ_USERS users: one
@@ -1609,6 +1611,17 @@ int cdae_hip_create_warp(const cdae_warp_config* wc, int device_id, cdae_hip_t**
   return 0;
 }
 
+int cdae_hip_create_fism_pair(const cdae_fism_config* fc, int device_id, cdae_hip_t** out) {
+  if (!fc || !out) return fail("null argument");
+  if (fc->struct_size != sizeof(cdae_fism_config)) return fail("cdae_fism_config size mismatch: got %u, want %zu", fc->struct_size, sizeof(cdae_fism_config));
+  if (fc->loss_type == CDAE_LOSS_CROSS_ENTROPY)
+    return fail("loss_type CROSS_ENTROPY (5) is refused on a pairwise FISM handle: at label 1, the only label a pair has, its gradient is "
+                "LOG's; SQUARE (0), LOG (2)");
+  CHK(cdae_hip_create_fism(fc, device_id, out));             // (every other refusal is FISM's)
+  (*out)->fism_pair = true;
+  return 0;
+}
+
 int cdae_hip_create_fism(const cdae_fism_config* fc, int device_id, cdae_hip_t** out) {
   if (!fc || !out) return fail("null argument");
   if (fc->struct_size != sizeof(cdae_fism_config)) return fail("cdae_fism_config size mismatch: got %u, want %zu", fc->struct_size, sizeof(cdae_fism_config));
@@ -1898,9 +1911,13 @@ int upload_data_set(cdae_hip* h, const cdae::plan::Plan& p, const int64_t* grp, 
   if (h->mf) {                                              // IMF / BPR / WRMF: the bias arrays (WRMF: the ones IMF's serving reads)
     const uint64_t inst_cap = p.emax * (h->mf == 2 || h->mf == 4 ? h->hp.num_neg : 1u + h->hp.num_neg);
     if (lists) CHK(h->d_UVpre.alloc((size_t)inst_cap * h->Kp));
-    CHK(h->d_ub.alloc((size_t)U)); CHK(h->d_ub_ag.alloc((size_t)U));
-    h->cnt[CDAE_P_UB] = h->cnt[CDAE_P_UB_AG] = (size_t)U;
-    HIPCHK(hipMemset(h->d_ub, 0, (size_t)U * sizeof(float)));
+    if (h->fism_pair) {                                     // FISMauc: bu cancels in every difference; CDAE_P_UB / _UB_AG are not allocated
+      h->cnt[CDAE_P_UB] = h->cnt[CDAE_P_UB_AG] = 0;
+    } else {
+      CHK(h->d_ub.alloc((size_t)U)); CHK(h->d_ub_ag.alloc((size_t)U));
+      h->cnt[CDAE_P_UB] = h->cnt[CDAE_P_UB_AG] = (size_t)U;
+      HIPCHK(hipMemset(h->d_ub, 0, (size_t)U * sizeof(float)));
+    }
   }
   if (h->mf == 4u) {                                        // WARP: the rank weights (warp.hpp:57-60)
     const std::vector<float> l = cdae::warp_rank_weights(I);
@@ -2022,7 +2039,7 @@ int cdae_hip_init_params(cdae_hip_t* h, uint64_t seed) {
     if (h->mf == 5u) { init01(h->P(CDAE_P_V), h->I, CDAE_P_V, 0); fill(h->P(CDAE_P_V_AG), h->I, h->K, h->Kp, 1e-4f); }   // FISM: Q, and no user table
     else { init01(h->d_Wu, h->U, CDAE_P_WU, h->uid_offset); fill(h->d_Wu_ag, h->U, h->K, h->Kp, 1e-4f); }
     init01(h->P(CDAE_P_W), h->I, CDAE_P_W, 0); fill(h->P(CDAE_P_W_AG), h->I, h->K, h->Kp, 1e-4f);
-    fill(h->d_ub, h->U, 1, 1, 0.f); fill(h->d_ub_ag, h->U, 1, 1, 1e-4f);
+    if (h->d_ub) { fill(h->d_ub, h->U, 1, 1, 0.f); fill(h->d_ub_ag, h->U, 1, 1, 1e-4f); }
     fill(h->P(CDAE_P_BP), h->I, 1, 1, 0.f); fill(h->P(CDAE_P_BP_AG), h->I, 1, 1, 1e-4f);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(h->stream));
@@ -2140,13 +2157,15 @@ constexpr const char* FISM_NO_LIST = "a FISM handle has no example list and no b
                                      "launch (cdae_hip_train_users runs the loop)";
 constexpr const char* FISM_NO_NODE = "a FISM handle has no user node: its hidden row is a sum over the rated set it is given";
 
-// FISM: the loop over users [u_begin, u_end) (cdae_fism_kernels.hpp) — one launch of ONE workgroup per window of users
-// (cdae_fism_host.h fism_windows), all on the training stream
+// FISM: the loop over users [u_begin, u_end) (cdae_fism_kernels.hpp; a pairwise handle: cdae_fism_pair_kernels.hpp,
+// §8n) — one launch of ONE workgroup per window of users (cdae_fism_host.h fism_windows / fism_pair_windows), all on the training stream
 int fism_enqueue(cdae_hip* h, uint64_t seed, uint32_t epoch, uint64_t u_begin, uint64_t u_end) {
   using namespace cdae;
   if (u_begin > u_end || u_end > h->U) return fail("bad user range [%llu, %llu)", (unsigned long long)u_begin, (unsigned long long)u_end);
   CHK(join_aux(h));
-  const std::vector<uint64_t> cuts = fism_windows(h->h_row_ptr.data(), u_begin, u_end, h->hp.num_neg, FISM_WINDOW_INSTANCES);
+  const bool pair = h->fism_pair;    // FISMauc: the pair loop (cdae_fism_pair_kernels.hpp, §8n); a window holds FISM_WINDOW_INSTANCES pairs
+  const std::vector<uint64_t> cuts = pair ? fism_pair_windows(h->h_row_ptr.data(), u_begin, u_end, h->hp.num_neg, FISM_WINDOW_INSTANCES)
+                                          : fism_windows(h->h_row_ptr.data(), u_begin, u_end, h->hp.num_neg, FISM_WINDOW_INSTANCES);
   const uint32_t res_rows = fism_resident_rows(h->NI, h->fism_resident);
   for (size_t t = 0; t + 1 < cuts.size(); ++t) {
     const uint64_t s0 = cuts[t];
@@ -2161,12 +2180,19 @@ int fism_enqueue(cdae_hip* h, uint64_t seed, uint32_t epoch, uint64_t u_begin, u
                            (const uint32_t*)h->d_col, s0, nb, seed, epoch, (const float*)h->d_fism_scale, h->P(CDAE_P_W), h->P(CDAE_P_W_AG),
                            h->P(CDAE_P_V), h->P(CDAE_P_V_AG), h->P(CDAE_P_BP), h->P(CDAE_P_BP_AG), h->d_ub.p, h->d_ub_ag.p);
       };
-      if (h->hp.adagrad) launch(fism_user_kernel<NI, true>); else launch(fism_user_kernel<NI, false>);
+      auto launch_pair = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3(1), dim3(FISM_WAVES * WAVE), 0, h->stream, h->hp, h->mf_bias, res_rows, (const int64_t*)h->d_row_ptr,
+                           (const uint32_t*)h->d_col, s0, nb, seed, epoch, (const float*)h->d_fism_scale, h->P(CDAE_P_W), h->P(CDAE_P_W_AG),
+                           h->P(CDAE_P_V), h->P(CDAE_P_V_AG), h->P(CDAE_P_BP), h->P(CDAE_P_BP_AG));
+      };
+      if (pair) { if (h->hp.adagrad) launch_pair(fism_pair_user_kernel<NI, true>); else launch_pair(fism_pair_user_kernel<NI, false>); }
+      else if (h->hp.adagrad) launch(fism_user_kernel<NI, true>); else launch(fism_user_kernel<NI, false>);
     });
     CHK(pr.end());
     HIPCHK(hipGetLastError());
     h->seq++;
-    h->acc_examples += fism_instance_count(h->h_row_ptr.data(), s0, s0 + nb, h->hp.num_neg);
+    h->acc_examples += pair ? fism_pair_count(h->h_row_ptr.data(), s0, s0 + nb, h->hp.num_neg)
+                            : fism_instance_count(h->h_row_ptr.data(), s0, s0 + nb, h->hp.num_neg);
     h->acc_batches += 1u; h->acc_users += nb;
   }
   return 0;

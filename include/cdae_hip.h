@@ -95,7 +95,9 @@ extern "C" {
  *     cdae_hip_warp_search, cdae_hip_warp_record_choices, cdae_hip_warp_choices, CDAE_WARP_MAX_TRY — WARP: rank-weighted pairwise
  *     matrix factorisation whose negatives are searched for on the device
  *     also under 12, the version unchanged (new entry points; nothing existing changed): cdae_fism_config, cdae_hip_create_fism,
- *     cdae_hip_fism_plan, cdae_hip_fism_set_resident — FISM: factored item similarity, the user's rows kept on chip for a visit */
+ *     cdae_hip_fism_plan, cdae_hip_fism_set_resident — FISM: factored item similarity, the user's rows kept on chip for a visit
+ *     also under 12, the version unchanged (a new entry point; nothing existing changed): cdae_hip_create_fism_pair — FISMauc, the
+ *     pairwise form of FISM on the FISM handle */
 #define CDAE_HIP_ABI_VERSION 12
 
 /* numeric values follow libcf::LossType (/root/reference/src/model/loss.hpp:10-18) */
@@ -864,6 +866,39 @@ int cdae_hip_create_fism(const cdae_fism_config* cfg, int device_id, cdae_hip_t*
 int cdae_hip_fism_plan(const cdae_hip_t* h, uint32_t* resident_rows, uint64_t* window_instances);
 /* allow = 0: every row streams through memory.  Both settings give the same bits (as cdae_hip_set_decode_fused). */
 int cdae_hip_fism_set_resident(cdae_hip_t* h, int allow);
+
+/* ---- FISMauc: the pairwise (ranking) form of FISM from the same paper (the reference's src/model/recsys/fism_pair.hpp), on a FISM
+ * handle.  It takes cdae_fism_config as it stands (reserved stays 0) and everything of a FISM handle but the training loop: the scale
+ * table, the residency plan (cdae_hip_fism_plan, _fism_set_resident), the launch windows, the negative stream, rows without items, the
+ * serving encode and every sweep behind it, and every FISM refusal.
+ * For users in id order, with R_u in CSR order, n = n_u and s = (n - 1)^-alpha (FISM's s_pos: 0 for a lone positive):
+ *     x = sum_{r in R_u} P[r]                                  fp32, at the start of the visit (FISM's order)
+ *     for p < n, i = R_u[p]; for k < num_neg:
+ *         j    = cdae_sample_negative(key, p * num_neg + k, row, n, num_items)     FISM's key (CDAE_STREAM_NEGATIVE) and draw index
+ *         v    = x - P[i]                                      the current x; P[i] takes no step while i is the positive
+ *         d    = [bi[i] - bi[j]] + s * (v . (Q[i] - Q[j]))     biases only with using_bias_term; no bu anywhere
+ *         g    = loss'(d, 1)
+ *         bi[i] steps on g + lambda * bi[i];  bi[j] steps on -g + lambda * bi[j]
+ *         every r in R_u, r != i: P[r] steps on g * s * (Q[i] - Q[j]) + lambda * P[r]   (both Q rows from before their own steps)
+ *         Q[i] steps on g * s * v + lambda * Q[i];  Q[j] steps on -g * s * v + lambda * Q[j]
+ *         x += sum_r (P[r] after - P[r] before)
+ * Both predictions are formed at the CURRENT parameters for every pair: a negative that repeats inside a positive sees its earlier step.
+ * AdaGrad without beta from accumulators of 1e-4, or plain SGD; cdae_hip_init_params as for FISM.
+ * Taken from fism_pair.hpp: the structure of the step (:110-160), the (n - 1)^-alpha scale for BOTH items of the pair (:137, 147, 148)
+ * and the Q gradients on x - P[i].  Deliberately different from it (the file does not compile as it stands: it includes a path that
+ * does not exist): it never overrides predict_user_item_rating, so its negative prediction is always 0 — here d is the difference of
+ * two real predictions; it forms the positive's prediction once, before the loop over negatives, and keeps it while the parameters
+ * move — here every pair reads the current Q[i], bi[i] and x; its AdaGrad accumulators start at 0, so a zero gradient divides 0 by 0
+ * — here 1e-4; it declares bu and never steps it — here there is no bu: it cancels in d, and CDAE_P_UB / _UB_AG are not allocated (asking
+ * for them is refused); it keeps the stale x_ table that the FISM handle already declined.
+ * loss_type: 0 (SQUARE, the paper's (1 - d)^2, the default) or 2 (LOG of the difference: the BPR criterion).  CROSS_ENTROPY (5) is
+ * refused: at label 1 its gradient is LOG's.  LOGISTIC and HINGE are refused as for FISM.  batch_users: 0 or 1.
+ * Training: as for FISM, one launch per window of users holding at most window_instances PAIRS (a user is never cut).  stats.examples
+ * is the number of pairs, num_neg * nnz of the range; stats.users and stats.batches as for FISM.  A user with n = 0 takes no step and is
+ * counted; a user with n = 1 has an empty neighbourhood (s = 0, v = 0) and its pairs still step bi and the lambda terms.  data_loss and
+ * penalty_loss return 0.  Both residency settings give the same bits.
+ * Serving: exactly a FISM handle's (z = n^-alpha * sum of the rated rows of P, D = Q, b' = bi). */
+int cdae_hip_create_fism_pair(const cdae_fism_config* cfg, int device_id, cdae_hip_t** out);
 
 /* ---- library-owned RCCL communicator and exchange schedule (one process per GPU: bench.py --gpus N) -----------------
  * The all-reduce of the staged deltas runs inside the library, on its own communicator and HIP stream, overlapped with the

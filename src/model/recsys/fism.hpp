@@ -56,7 +56,7 @@ class FISM : public IMF {
     c.batch_users = 1;
     c.lambda = lambda_; c.learn_rate = learn_rate_; c.alpha = alpha_;
     cdae_hip_t* raw = nullptr;
-    CDAE_HIP_CHECK(cdae_hip_create_fism(&c, static_cast<int>(mf_env_u64("CDAE_DEVICE", 0)), &raw));
+    CDAE_HIP_CHECK(create_handle(&c, static_cast<int>(mf_env_u64("CDAE_DEVICE", 0)), &raw));
     dev_.reset(raw, [](cdae_hip_t* h) { cdae_hip_destroy(h); });
     auto csr = std::make_shared<Csr>();
     data_->to_csr(0, 1, csr->row_ptr, csr->col);
@@ -115,6 +115,8 @@ class FISM : public IMF {
   DMatrix get_input_vecs() { return matrix(CDAE_P_W, num_items_); }       // p_
 
  protected:
+  // which entry point makes the handle (libcf::FISMP, fism_pair.hpp: cdae_hip_create_fism_pair)
+  virtual int create_handle(const cdae_fism_config* c, int device, cdae_hip_t** out) const { return cdae_hip_create_fism(c, device, out); }
   double alpha_ = 1.;
 };
 
