@@ -2,9 +2,8 @@
 // src/model/recsys/fism_pair.hpp), DESIGN.md §8n.  A pair (i, j) of a rated item and a drawn negative shares ONE neighbourhood vector
 // v = x - P[i]; its difference d = [bi[i] - bi[j]] + s v . (Q[i] - Q[j]) takes one sweep of the user's rows with qd = Q[i] - Q[j], so a
 // positive costs num_neg sweeps against FISM's 1 + num_neg.
-//   fism_pair_user_kernel<NI, ADA>   the design of fism_user_kernel (cdae_fism_kernels.hpp): ONE workgroup of FISM_WAVES wavefronts walks
-//                                    the launch's users, row position q belongs to wavefront q % FISM_WAVES, the first res_rows positions
-//                                    stay in registers with their accumulators for the visit, and x keeps §8m's summation order.
+//   fism_pair_user_kernel<NI, ADA>   ONE workgroup of FISM_WAVES wavefronts walks the launch's users on the visit frame of
+//                                    cdae_fism_kernels.hpp (row ownership, resident rows, the order of every sum: stated there).
 //                                    Per positive: the owner of P[i] publishes it through LDS ONCE for its pairs; every
 //                                    wavefront loads Q[i], its accumulator and bi[i] and carries them through the positive's pairs,
 //                                    stepping them redundantly (same instructions, same bits: the way fism_user_kernel carries bu);
@@ -24,7 +23,7 @@ __global__ void __launch_bounds__(FISM_WAVES * WAVE)
 fism_pair_user_kernel(HyperParams hp, uint32_t bias_term, uint32_t res_rows /* 0 or FISM_WAVES * fism_resident_slots(NI) */,
                       const int64_t* __restrict__ row_ptr, const uint32_t* __restrict__ col, uint64_t u0, uint32_t nb, uint64_t seed,
                       uint32_t epoch, const float* __restrict__ scale /* [num_items + 1] */, float* P, float* P_ag, float* Q, float* Q_ag,
-                      float* BI, float* BI_ag) {
+                      float* BI, float* BI_ag, float* /* BU */, float* /* BU_ag: fism_user_kernel's arguments; bu cancels in a pair */) {
   constexpr uint32_t W = FISM_WAVES;
   constexpr uint32_t OUT = W - 1u;                             // the output wavefront
   constexpr int R = (int)fism_resident_slots(NI);
@@ -34,13 +33,6 @@ fism_pair_user_kernel(HyperParams hp, uint32_t bias_term, uint32_t res_rows /* 0
   const uint32_t w = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x / WAVE));
   const uint32_t lane = threadIdx.x % WAVE, lo = lane * NI;
   uint32_t par = 0;
-  auto total = [&](uint32_t b, float (&t)[NI]) {               // the FISM_WAVES sums of set `b`, in wavefront order from 0.f
-#pragma unroll
-    for (int i = 0; i < NI; ++i) t[i] = 0.f;
-    for (uint32_t ww = 0; ww < W; ++ww)
-#pragma unroll
-      for (int i = 0; i < NI; ++i) t[i] += s_d[b][ww][lo + i];
-  };
   for (uint32_t slot = 0; slot < nb; ++slot) {
     const uint64_t uid = u0 + slot;
     const int64_t r0 = row_ptr[uid];
@@ -53,54 +45,18 @@ fism_pair_user_kernel(HyperParams hp, uint32_t bias_term, uint32_t res_rows /* 0
     float pr[R][NI], pa[R][NI];
     {
       float part[NI];
-#pragma unroll
-      for (int i = 0; i < NI; ++i) part[i] = 0.f;
-#pragma unroll
-      for (int sl = 0; sl < R; ++sl) {
-        const uint32_t qp = w + W * (uint32_t)sl;
-        if (qp < n_res) {
-          const uint32_t it = (uint32_t)__builtin_amdgcn_readfirstlane((int)row[qp]);
-          fism_load_row<NI>(pr[sl], P + (size_t)it * KP, lo);
-          fism_load_row<NI>(pa[sl], P_ag + (size_t)it * KP, lo);
-#pragma unroll
-          for (int i = 0; i < NI; ++i) part[i] += pr[sl][i];
-        } else {
-#pragma unroll
-          for (int i = 0; i < NI; ++i) { pr[sl][i] = 0.f; pa[sl][i] = 1.f; }
-        }
-      }
-      for (uint32_t qp = res_rows + w; qp < n; qp += W) {
-        const uint32_t it = (uint32_t)__builtin_amdgcn_readfirstlane((int)row[qp]);
-        float t[NI];
-        fism_load_row<NI>(t, P + (size_t)it * KP, lo);
-#pragma unroll
-        for (int i = 0; i < NI; ++i) part[i] += t[i];
-      }
+      fism_visit_load<NI, R>(pr, pa, part, row, n, n_res, res_rows, w, lo, P, P_ag);
 #pragma unroll
       for (int i = 0; i < NI; ++i) s_d[par][w][lo + i] = part[i];
     }
     __syncthreads();
     float x[NI];
-    total(par, x);
+    fism_total<NI>(s_d[par], lo, x);
     par ^= 1u;
     for (uint32_t p = 0; p < n; ++p) {
       const uint32_t item_i = (uint32_t)__builtin_amdgcn_readfirstlane((int)row[p]);
       // the owner of P[i] publishes it, once for the positive's pairs
-      if (w == p % W) {
-        float t[NI];
-        if (p < n_res) {
-#pragma unroll
-          for (int sl = 0; sl < R; ++sl)
-            if ((uint32_t)sl == p / W) {
-#pragma unroll
-              for (int i = 0; i < NI; ++i) t[i] = pr[sl][i];
-            }
-        } else {
-          fism_load_row<NI>(t, P + (size_t)item_i * KP, lo);
-        }
-#pragma unroll
-        for (int i = 0; i < NI; ++i) s_pi[lo + i] = t[i];
-      }
+      fism_publish<NI, R>(s_pi, pr, p, n_res, w, lo, P + (size_t)item_i * KP);
       // every wavefront: Q[i], its accumulator and bi[i], carried through the pairs (nobody has stored them since the last barrier
       // behind a vmcnt(0): a negative of this user is never i)
       float qi[NI], qia[NI];
@@ -142,16 +98,7 @@ fism_pair_user_kernel(HyperParams hp, uint32_t bias_term, uint32_t res_rows /* 0
           const uint32_t qp = w + W * (uint32_t)sl;
           if (qp < n_res && qp != p) fism_row_step<NI, ADA>(hp, pr[sl], pa[sl], qd, gs, d);
         }
-        for (uint32_t qp = res_rows + w; qp < n; qp += W) {
-          if (qp == p) continue;
-          const uint32_t it = (uint32_t)__builtin_amdgcn_readfirstlane((int)row[qp]);
-          float tw[NI], ta[NI];
-          fism_load_row<NI>(tw, P + (size_t)it * KP, lo);
-          fism_load_row<NI>(ta, P_ag + (size_t)it * KP, lo);
-          fism_row_step<NI, ADA>(hp, tw, ta, qd, gs, d);
-          vstore<NI>(P + (size_t)it * KP + lo, tw);
-          vstore<NI>(P_ag + (size_t)it * KP + lo, ta);
-        }
+        fism_sweep_streamed<NI, ADA>(hp, row, n, res_rows, w, lo, p, P, P_ag, qd, gs, d);
 #pragma unroll
         for (int i = 0; i < NI; ++i) s_d[par][w][lo + i] = d[i];
         // the output wavefront: Q[j] on -g s v + lambda Q[j], bi[j] on -g + lambda bi[j]
@@ -180,22 +127,14 @@ fism_pair_user_kernel(HyperParams hp, uint32_t bias_term, uint32_t res_rows /* 0
         __builtin_amdgcn_s_waitcnt(WAIT_VM0);                  // this pair's stores are in memory before anybody reads them again
         __syncthreads();
         float t[NI];
-        total(par, t);
+        fism_total<NI>(s_d[par], lo, t);
 #pragma unroll
         for (int i = 0; i < NI; ++i) x[i] += t[i];
         par ^= 1u;
       }
     }
     // the resident rows go back; the next visit reads them behind the barrier
-#pragma unroll
-    for (int sl = 0; sl < R; ++sl) {
-      const uint32_t qp = w + W * (uint32_t)sl;
-      if (qp < n_res) {
-        const uint32_t it = (uint32_t)__builtin_amdgcn_readfirstlane((int)row[qp]);
-        vstore<NI>(P + (size_t)it * KP + lo, pr[sl]);
-        vstore<NI>(P_ag + (size_t)it * KP + lo, pa[sl]);
-      }
-    }
+    fism_visit_store<NI, R>(pr, pa, row, n_res, w, lo, P, P_ag);
     __builtin_amdgcn_s_waitcnt(WAIT_VM0);
     __syncthreads();
   }

@@ -2158,14 +2158,14 @@ constexpr const char* FISM_NO_LIST = "a FISM handle has no example list and no b
 constexpr const char* FISM_NO_NODE = "a FISM handle has no user node: its hidden row is a sum over the rated set it is given";
 
 // FISM: the loop over users [u_begin, u_end) (cdae_fism_kernels.hpp; a pairwise handle: cdae_fism_pair_kernels.hpp,
-// §8n) — one launch of ONE workgroup per window of users (cdae_fism_host.h fism_windows / fism_pair_windows), all on the training stream
+// §8n) — one launch of ONE workgroup per window of users (cdae_fism_host.h fism_windows), all on the training stream
 int fism_enqueue(cdae_hip* h, uint64_t seed, uint32_t epoch, uint64_t u_begin, uint64_t u_end) {
   using namespace cdae;
   if (u_begin > u_end || u_end > h->U) return fail("bad user range [%llu, %llu)", (unsigned long long)u_begin, (unsigned long long)u_end);
   CHK(join_aux(h));
   const bool pair = h->fism_pair;    // FISMauc: the pair loop (cdae_fism_pair_kernels.hpp, §8n); a window holds FISM_WINDOW_INSTANCES pairs
-  const std::vector<uint64_t> cuts = pair ? fism_pair_windows(h->h_row_ptr.data(), u_begin, u_end, h->hp.num_neg, FISM_WINDOW_INSTANCES)
-                                          : fism_windows(h->h_row_ptr.data(), u_begin, u_end, h->hp.num_neg, FISM_WINDOW_INSTANCES);
+  const uint64_t steps = fism_steps_per_interaction(pair, h->hp.num_neg);
+  const std::vector<uint64_t> cuts = fism_windows(h->h_row_ptr.data(), u_begin, u_end, steps, FISM_WINDOW_INSTANCES);
   const uint32_t res_rows = fism_resident_rows(h->NI, h->fism_resident);
   for (size_t t = 0; t + 1 < cuts.size(); ++t) {
     const uint64_t s0 = cuts[t];
@@ -2175,24 +2175,17 @@ int fism_enqueue(cdae_hip* h, uint64_t seed, uint32_t epoch, uint64_t u_begin, u
     CHK(pr.begin(h, F_DECODE, h->stream));
     dispatch_ni(h->NI, [&](auto ni) {
       constexpr int NI = decltype(ni)::value;
-      auto launch = [&](auto kernel) {
-        hipLaunchKernelGGL(kernel, dim3(1), dim3(FISM_WAVES * WAVE), 0, h->stream, h->hp, h->mf_bias, res_rows, (const int64_t*)h->d_row_ptr,
-                           (const uint32_t*)h->d_col, s0, nb, seed, epoch, (const float*)h->d_fism_scale, h->P(CDAE_P_W), h->P(CDAE_P_W_AG),
-                           h->P(CDAE_P_V), h->P(CDAE_P_V_AG), h->P(CDAE_P_BP), h->P(CDAE_P_BP_AG), h->d_ub.p, h->d_ub_ag.p);
-      };
-      auto launch_pair = [&](auto kernel) {
-        hipLaunchKernelGGL(kernel, dim3(1), dim3(FISM_WAVES * WAVE), 0, h->stream, h->hp, h->mf_bias, res_rows, (const int64_t*)h->d_row_ptr,
-                           (const uint32_t*)h->d_col, s0, nb, seed, epoch, (const float*)h->d_fism_scale, h->P(CDAE_P_W), h->P(CDAE_P_W_AG),
-                           h->P(CDAE_P_V), h->P(CDAE_P_V_AG), h->P(CDAE_P_BP), h->P(CDAE_P_BP_AG));
-      };
-      if (pair) { if (h->hp.adagrad) launch_pair(fism_pair_user_kernel<NI, true>); else launch_pair(fism_pair_user_kernel<NI, false>); }
-      else if (h->hp.adagrad) launch(fism_user_kernel<NI, true>); else launch(fism_user_kernel<NI, false>);
+      // the two loops take the same arguments (a pairwise handle allocates no user bias: its kernel ignores the two null pointers)
+      const auto kernel = pair ? (h->hp.adagrad ? fism_pair_user_kernel<NI, true> : fism_pair_user_kernel<NI, false>)
+                               : (h->hp.adagrad ? fism_user_kernel<NI, true> : fism_user_kernel<NI, false>);
+      hipLaunchKernelGGL(kernel, dim3(1), dim3(FISM_WAVES * WAVE), 0, h->stream, h->hp, h->mf_bias, res_rows, (const int64_t*)h->d_row_ptr,
+                         (const uint32_t*)h->d_col, s0, nb, seed, epoch, (const float*)h->d_fism_scale, h->P(CDAE_P_W), h->P(CDAE_P_W_AG),
+                         h->P(CDAE_P_V), h->P(CDAE_P_V_AG), h->P(CDAE_P_BP), h->P(CDAE_P_BP_AG), h->d_ub.p, h->d_ub_ag.p);
     });
     CHK(pr.end());
     HIPCHK(hipGetLastError());
     h->seq++;
-    h->acc_examples += pair ? fism_pair_count(h->h_row_ptr.data(), s0, s0 + nb, h->hp.num_neg)
-                            : fism_instance_count(h->h_row_ptr.data(), s0, s0 + nb, h->hp.num_neg);
+    h->acc_examples += fism_step_count(h->h_row_ptr.data(), s0, s0 + nb, steps);
     h->acc_batches += 1u; h->acc_users += nb;
   }
   return 0;

@@ -1,8 +1,9 @@
-"""CPU: the host arithmetic of a FISM handle (cdae_amd/csrc/cdae_fism_host.h: the scale table against pow, the residency plan, the launch
-windows, the instance counts) checked by src/fism_check.cpp — a stand-alone program built plain (with libcf::FISM, which must compile and
-link against the library) and, without the library, under the address and undefined-behaviour sanitizers (`make sanitize`) — and the same
-functions against tests/fism_ref.py's constants."""
+"""CPU: the host arithmetic of a FISM handle of either kind (cdae_amd/csrc/cdae_fism_host.h: the scale table against pow, the residency
+plan, the step counts and launch windows in instances and in pairs) checked by src/fism_check.cpp — a stand-alone program built plain
+(with libcf::FISM and libcf::FISMP, which must compile and link against the library) and, without the library, under the address and
+undefined-behaviour sanitizers (`make sanitize`) — and the same functions against tests/fism_ref.py's constants."""
 import os
+import re
 import subprocess
 
 import numpy as np
@@ -18,7 +19,9 @@ def test_fism_check_builds_with_the_libcf_header_and_passes(built):
     run = subprocess.run([os.path.join(ROOT, "build", "fism_check")], capture_output=True, text=True, timeout=120)
     out = run.stdout + run.stderr
     assert run.returncode == 0, out
-    assert "fism check OK (compiled)" in out and "fism_check:" not in out, out
+    assert "fism check OK (compiled)" in out and "fism pair check OK (compiled)" in out and "fism_check:" not in out, out
+    hpp = open(os.path.join(SRC, "model", "recsys", "fism_pair.hpp")).read()
+    assert "class FISMP : public FISM" in hpp and "struct FISMPConfig" in hpp and "cdae_hip_create_fism_pair" in hpp
 
 
 def test_fism_check_under_the_sanitizers():
@@ -27,7 +30,10 @@ def test_fism_check_under_the_sanitizers():
     out = run.stdout + run.stderr
     assert run.returncode == 0, out
     assert "fism check OK (host arithmetic)" in run.stdout and "warp check OK (host arithmetic)" in run.stdout, out
+    assert "fism pair check OK (host arithmetic)" in run.stdout, out
     assert "Sanitizer" not in out and "runtime error" not in out, out
+    mk = open(os.path.join(SRC, "Makefile")).read()
+    assert re.search(r"-fsanitize=address,undefined[^\n]*-DFISM_CHECK_HOST_ONLY[^\n]*fism_check\.cpp", mk)
 
 
 def test_the_reference_states_the_same_plan():
