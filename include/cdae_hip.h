@@ -779,7 +779,10 @@ int cdae_hip_als_gram(cdae_hip_t* h, uint32_t side, float* out, size_t count);
  * loss_type: the five losses of cdae_mf_config (the reference's default is HINGE).  batch_users: 1 (and 0, which selects 1) is the
  * reference loop.  A value above 1 is the block schedule of IMF / BPR in cdae_hip_user_order's activity-grouped order: one wavefront per
  * user of the block searches and steps its user vector against the block-start item rows, then every item row takes its pairs' steps in
- * (user, pair) order.  No block size has been measured for accuracy, so none is a default. */
+ * (user, pair) order.  A block of ONE user (the last of a range whose length is 1 modulo batch_users) runs the reference loop.  No block
+ * size has been measured for accuracy, so none is a default.
+ * The stats of a training call: users = the users of the range; examples = 2 * num_neg * (their train items), the two list places of
+ * every pair whether its search trained it or skipped it; batches = blocks, and under batch_users = 1 one per user. */
 typedef struct cdae_warp_config {
   uint32_t struct_size;      /* sizeof(cdae_warp_config)                                 */
   uint32_t num_dim;          /* WARPConfig::num_dim (10)                                 */
