@@ -28,7 +28,9 @@
 namespace cdae {
 
 // loss.hpp gradients of every loss the two models accept (yelp.cpp:122-165): SQUARE 0, LOGISTIC 1, LOG 2, HINGE 3, CROSS_ENTROPY 5;
-// scores on the +-18 / +-88 grid and HINGE at exactly z = 1: tests/test_gpu_saturation.py::test_mf_from_grid_scores
+// scores on the +-18 / +-88 grid and HINGE at exactly z = 1: tests/test_gpu_saturation.py::test_mf_from_grid_scores (IMF / BPR),
+// tests/test_gpu_model_saturation.py (fism_user_kernel and fism_pair_user_kernel from grid scores), tests/test_gpu_warp.py's
+// "bias100" cases (warp_user_kernel: every loss at yui - score down to -200)
 __device__ __forceinline__ float mf_loss_grad(uint32_t loss_type, float pred, float truth) {
   switch (loss_type) {
     case 0u: return -2.f * (truth - pred);                                             // loss.hpp:54

@@ -59,6 +59,7 @@ def train(st, ptr, col, seed, epoch, users=None, fault=None):
                 if st.bias:
                     d = d + (bii - bij)
                 st.max_abs_pred = max(st.max_abs_pred, abs(float(d)))
+                fr._classify(st, float(d), True)
                 g = dt(loss_grad(st.loss, d, dt(1.0)))
                 if st.bias:
                     st.bi[i], st.bia[i] = _step(st, bii, st.bia[i], g + st.lam * bii)
@@ -141,6 +142,14 @@ def run_free(c):
     st = reference(c[0]) if c[0] in DRIFTS else run(c)
     st32 = run(c, dtype64=False)
     return dict(max_abs_pred=st.max_abs_pred, drift=max(measure(getattr(st32, n), getattr(st, n)) for n in TABLES))
+
+
+@functools.lru_cache(maxsize=None)
+def grid_reference(name):
+    """the fp64 state after EPOCHS epochs of the pair loop from fism_ref's grid fixture (fism_ref.GRID_PAIR_CASES; computed once per
+    session; do not modify)"""
+    K, hyper = fr.GRID_PAIR_CASES[name]
+    return fr.grid_run(train, K, hyper)
 
 
 # CASES-BEGIN (written from tools/fism_pair_cases.py's output; the last number is the measured drift)

@@ -45,6 +45,7 @@ class State:
         self.lam, self.lr, self.loss, self.adagrad, self.bias, self.alpha, self.num_neg = lambda_, learn_rate, loss, adagrad, bias, alpha, num_neg
         self.scale = scale_table(I, alpha)
         self.max_abs_pred = 0.0
+        self.classes = {}                # (positive label?, sign of the prediction) -> instances met beyond +-18 (_classify)
 
     TABLES = ("P", "Pa", "Q", "Qa", "bi", "bu")          # the six the GPU tests compare
     ALL = TABLES + ("bia", "bua", "scale")
@@ -93,8 +94,36 @@ def neg_label(loss):
     return -1.0 if loss in (2, 3) else 0.0
 
 
-def train(st, ptr, col, seed, epoch, users=None):
-    """one epoch over users [0, U) (or the range `users`) in id order -> the number of instances"""
+FAULTS = ("neg_label_0", "exp_sign", "clamp18", "no_bias", "no_s_in_row_step")
+
+
+def _faulty_grad(fault, loss, pred, label):
+    """loss_grad with one of FAULTS written into it: the exponent's argument with the other sign; SQUARE on a prediction clamped to +-18"""
+    if fault == "exp_sign" and loss == 2:
+        return -label / (1.0 + np.exp(-pred * label))
+    if fault == "exp_sign" and loss == 5:
+        return 1.0 / (1.0 + np.exp(pred)) - label
+    if fault == "clamp18" and loss == 0:
+        return loss_grad(loss, min(max(pred, -18.0), 18.0), label)
+    return loss_grad(loss, pred, label)
+
+
+def _classify(st, pred, positive):
+    """counts the saturated instances a run meets: st.classes[(positive label?, sign of pred)] for |pred| > 18"""
+    if abs(pred) > 18.0:
+        key = (bool(positive), 1 if pred > 0 else -1)
+        st.classes[key] = st.classes.get(key, 0) + 1
+
+
+def train(st, ptr, col, seed, epoch, users=None, fault=None):
+    """one epoch over users [0, U) (or the range `users`) in id order -> the number of instances.  fault: one of FAULTS, a way a kernel
+    is likely to get a saturated instance wrong (tests/test_fism_reference.py shows that the grid fixture tells each from the right loop):
+      "neg_label_0"        LOG's (and HINGE's) negative label taken as 0
+      "exp_sign"           the sign of the exponent's argument flipped (LOG, CROSS_ENTROPY)
+      "clamp18"            the prediction clamped to +-18 before SQUARE's gradient
+      "no_bias"            bu + bi left out of the prediction
+      "no_s_in_row_step"   the rows of P step on g Q[item] where the loop has g s Q[item]"""
+    assert fault is None or fault in FAULTS, fault
     ptr = np.asarray(ptr, dtype=np.int64); col = np.asarray(col, dtype=np.int64)
     I = st.P.shape[0]
     dt = st.P.dtype.type
@@ -112,20 +141,21 @@ def train(st, ptr, col, seed, epoch, users=None):
                 rated = k == 0
                 item = i if rated else int(neg[p, k - 1])
                 s = s_pos if rated else s_neg
-                label = dt(1.0 if rated else neg_label(st.loss))
+                label = dt(1.0 if rated else 0.0 if fault == "neg_label_0" else neg_label(st.loss))
                 v = x - st.P[i] if rated else x
                 pred = s * (v @ st.Q[item])
-                if st.bias:
+                if st.bias and fault != "no_bias":
                     pred = pred + (st.bu[u] + st.bi[item])
                 st.max_abs_pred = max(st.max_abs_pred, abs(float(pred)))
-                g = dt(loss_grad(st.loss, pred, label))
+                _classify(st, float(pred), rated)
+                g = dt(_faulty_grad(fault, st.loss, pred, label))
                 if st.bias:
                     st.bu[u], st.bua[u] = _step(st, st.bu[u], st.bua[u], g + st.lam * st.bu[u])
                     st.bi[item], st.bia[item] = _step(st, st.bi[item], st.bia[item], g + st.lam * st.bi[item])
                 idx = np.delete(rows, p) if rated else rows
                 q = st.Q[item].copy()
                 before = st.P[idx]
-                after, st.Pa[idx] = _step(st, before, st.Pa[idx], (g * s) * q[None, :] + st.lam * before)
+                after, st.Pa[idx] = _step(st, before, st.Pa[idx], (g if fault == "no_s_in_row_step" else g * s) * q[None, :] + st.lam * before)
                 st.P[idx] = after
                 st.Q[item], st.Qa[item] = _step(st, q, st.Qa[item], (g * s) * v + st.lam * q)
                 x = x + (after - before).sum(axis=0)
@@ -267,6 +297,117 @@ def run_free(c):
     for ep in range(EPOCHS):
         train(st32, d.train_ptr, d.train_col, c[5], ep)
     return dict(max_abs_pred=st.max_abs_pred, drift=max(measure(getattr(st32, n), getattr(st, n)) for n in State.TABLES))
+
+
+# ---- the grid fixture: predictions on the +-18 / +-88 / +-1000 grid of tests/golden/saturation_kat.npz -------------------------------------
+# tests/test_gpu_model_saturation.py trains FISM and FISMauc from it; tests/test_fism_reference.py and tests/test_fism_pair_reference.py
+# assert its premises on the CPU.  Modelled on tests/test_gpu_saturation.py::test_mf_from_grid_scores:
+#   53 users and 100 items; user u's row is item u and four of the items 53 .. 99 (five items: three of the eight wavefronts own no row);
+#   rows 53 .. 99 of P are 0.25 e_0, rows 0 .. 52 carry 0 in coordinate 0 and N(0, 0.1) elsewhere; coordinate 0 of Q is 2 grid[i] for
+#   i < 53 and 0 beyond, the other coordinates N(0, 0.1); alpha = 0.5, so s_pos = scale[4] = 0.5 exactly; biases 0.
+# For user u's rated item u then x = P[u] + e_0 and v = x - P[u] = e_0 in every arithmetic (each coordinate is one value plus zeros), so
+# s_pos v . Q[u] = 0.5 * 2 grid[u] = grid[u] bit for bit; a drawn negative j < 53 scores about 5^-0.5 * 2 grid[j], saturated as well.
+GRID_BOUND = 1e-3                # the device against fp64, element by element: |gpu - ref| <= GRID_BOUND * (GRID_FLOOR + |ref|)
+GRID_FLOOR = 1e-2                # (test_mf_from_grid_scores' MF_BOUND and FLOOR: fp32 storage, __expf, 1-ulp rcp and sqrt against fp64)
+GRID_DRIFT_MAX = GRID_BOUND / 4  # float32 against float64 on the reference alone, in the same measure
+GRID_SSEED = 2                   # the first stream seed of 1, 2, 3, ... at which every case below meets GRID_DRIFT_MAX and all four classes
+GRID_HYPER = dict(alpha=0.5, lambda_=0.01, learn_rate=2.0 ** -5)
+GRID_SGD = dict(adagrad=False, learn_rate=2.0 ** -10)
+# name -> (num_dim, hyper-parameters beyond GRID_HYPER); num_neg is 5.  SQUARE with plain SGD is left out: on the full grid its fp64
+# reference overflows by itself (a step of lr * 2 * 1000 * 2000 on a row whose prediction it multiplies), at 2^-10 and at 2^-20 alike.
+GRID_CASES = {
+    "sq-ada": (16, dict(loss=0)),
+    "log-ada": (16, dict(loss=2)),
+    "ce-ada": (16, dict(loss=5)),
+    "log-sgd": (16, dict(loss=2, **GRID_SGD)),
+    "ce-sgd": (16, dict(loss=5, **GRID_SGD)),
+    "log-ada-K300": (300, dict(loss=2)),                       # NI = 8
+    "log-ada-nobias": (16, dict(loss=2, bias=False)),
+}
+GRID_PAIR_CASES = {
+    "sq-ada": (16, dict(loss=0)),
+    "log-ada": (16, dict(loss=2)),
+    "log-sgd": (16, dict(loss=2, **GRID_SGD)),
+    "log-ada-K300": (300, dict(loss=2)),
+    "log-ada-nobias": (16, dict(loss=2, bias=False)),
+}
+
+
+@functools.lru_cache(maxsize=None)
+def grid():
+    import os
+    return np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "saturation_kat.npz"))["grid"].astype(np.float32)
+
+
+@functools.lru_cache(maxsize=None)
+def grid_data():
+    """53 users: user u's first (smallest) item is item u, then four of the items 53 .. 99"""
+    import mf_conflict_ref
+    rng = np.random.default_rng(3)
+    n = grid().size
+    return mf_conflict_ref.from_rows([np.r_[u, np.sort(rng.choice(np.arange(n, n + 47), 4, replace=False))] for u in range(n)], n + 47)
+
+
+def grid_tables(K):
+    """-> (P, Q) float32 [100, K]"""
+    g = grid()
+    n, I = g.size, g.size + 47
+    rng = np.random.default_rng(5)
+    P = rng.normal(0.0, 0.1, (I, K)); Q = rng.normal(0.0, 0.1, (I, K))
+    P[:, 0] = 0.0; P[n:] = 0.0; P[n:, 0] = 0.25
+    Q[:, 0] = 0.0; Q[:n, 0] = 2.0 * g.astype(np.float64)
+    return P.astype(np.float32), Q.astype(np.float32)
+
+
+def grid_state(K, hyper, dtype64=True, tables=None):
+    """the state a grid case starts from (tables: (P, Q) read back from a handle; default grid_tables(K))"""
+    d = grid_data()
+    P, Q = tables if tables is not None else grid_tables(K)
+    st = State(P, Q, d.num_users, num_neg=5, **{**GRID_HYPER, **hyper})
+    return st if dtype64 else st.as_float32()
+
+
+def grid_first(st):
+    """the prediction of every user's first instance (FISM), the score of the positive of every user's first pair (FISMauc), in the
+    state's own arithmetic: s_pos (x - P[u]) . Q[u] + bi[u] (+ bu[u], zero at the start)"""
+    d = grid_data()
+    out = []
+    for u in range(d.num_users):
+        rows = d.train_col[d.train_ptr[u]:d.train_ptr[u + 1]].astype(np.int64)
+        assert rows[0] == u and rows.size == 5 < WAVES
+        v = st.P[rows].sum(axis=0) - st.P[u]
+        out.append(st.scale[rows.size - 1] * (v @ st.Q[u]) + (st.bu[u] + st.bi[u]))
+    return np.array(out)
+
+
+def share_beyond(x, t):
+    return float(np.mean(np.abs(np.asarray(x)) > t))
+
+
+def grid_measure(a, b):
+    """max over the elements of |a - b| / (GRID_FLOOR + |b|): a range that includes 2000 would hide the small entries"""
+    a = np.asarray(a, dtype=np.float64); b = np.asarray(b, dtype=np.float64)
+    return float((np.abs(a - b) / (GRID_FLOOR + np.abs(b))).max())
+
+
+def grid_run(train_fn, K, hyper, dtype64=True, fault=None, tables=None):
+    """EPOCHS epochs of train_fn (this module's train or fism_pair_ref's) from the grid start -> the state; every table finite after
+    every epoch"""
+    d = grid_data()
+    st = grid_state(K, hyper, dtype64, tables)
+    for ep in range(EPOCHS):
+        with np.errstate(over="ignore"):                       # exp of a saturated prediction overflows to inf and 1 / inf is 0: meant
+            train_fn(st, d.train_ptr, d.train_col, GRID_SSEED, ep, **({"fault": fault} if fault else {}))
+        for n in State.ALL:
+            assert np.isfinite(getattr(st, n)).all(), (n, ep)
+    return st
+
+
+@functools.lru_cache(maxsize=None)
+def grid_reference(name):
+    """the fp64 state after EPOCHS epochs of the FISM grid case (computed once per session; do not modify)"""
+    K, hyper = GRID_CASES[name]
+    return grid_run(train, K, hyper)
 
 
 # CASES-BEGIN (written from tools/fism_cases.py's output; the last number is the measured drift)

@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 import fism_pair_ref as pr
+import fism_ref as fr
 from test_fism_reference import recall_at_10
 
 
@@ -114,3 +115,41 @@ def test_the_reference_learns_to_rank_held_out_items():
     r_pair = recall_at_10(lambda u: st.Q @ pr.hidden(st, d.train_col[d.train_ptr[u]:d.train_ptr[u + 1]]) + st.bi, d)
     print(f"Recall@10: FISMauc {r_pair:.4f}, popularity {r_pop:.4f}")
     assert r_pair > r_pop
+
+
+# ---- the grid fixture (fism_ref.grid_*): the premises of tests/test_gpu_model_saturation.py for the pair loop --------------------------
+PAIR_CLASSES = ((True, 1), (True, -1))           # a difference beyond +18 and beyond -18 (a pair's label is always 1)
+
+
+def test_the_grid_cases_are_the_ones_the_gpu_test_names():
+    assert set(fr.GRID_PAIR_CASES) == {"sq-ada", "log-ada", "log-sgd", "log-ada-K300", "log-ada-nobias"}
+    assert all(h["loss"] in (0, 2) for _, h in fr.GRID_PAIR_CASES.values())
+
+
+@pytest.mark.parametrize("name", list(fr.GRID_PAIR_CASES))
+def test_the_grid_fixture_scores_the_grid_and_stays_within_the_drift_premise(name):
+    """The positive of every user's first pair scores its grid point bit for bit (s v . Q[u] + bi[u], in float64 and in float32: the pair's
+    difference takes the negative's score off it); over the two epochs the fp64 reference meets differences beyond +18 and beyond -18; and
+    the same loop in float32 ends within GRID_BOUND / 4 of it, element by element."""
+    from test_fism_reference import assert_grid_premises
+    K, hyper = fr.GRID_PAIR_CASES[name]
+    ref = pr.grid_reference(name)
+    for dtype64 in (True, False):
+        assert_grid_premises(fr.grid_first(fr.grid_state(K, hyper, dtype64)), ref.classes, PAIR_CLASSES)
+    st32 = fr.grid_run(pr.train, K, hyper, dtype64=False)
+    drift = {n: fr.grid_measure(getattr(st32, n), getattr(ref, n)) for n in pr.TABLES}
+    print(f"grid pair {name}: max |d| {ref.max_abs_pred:.4g}, classes {ref.classes}, drift " + ", ".join(f"{n} {e:.2e}" for n, e in drift.items()))
+    assert max(drift.values()) <= fr.GRID_DRIFT_MAX, drift
+    assert ref.max_abs_pred >= 1000.0
+
+
+@pytest.mark.parametrize("fault", pr.FAULTS)
+@pytest.mark.parametrize("name", [n for n, (K, _) in fr.GRID_PAIR_CASES.items() if K == 16])
+def test_the_grid_fixture_tells_a_faulty_pair_loop_from_the_right_one(name, fault):
+    """each of fism_pair_ref.FAULTS moves some compared table of the grid fixture by at least 10 x GRID_BOUND, element by element"""
+    K, hyper = fr.GRID_PAIR_CASES[name]
+    right = pr.grid_reference(name)
+    wrong = fr.grid_run(pr.train, K, hyper, fault=fault)
+    dist = {n: fr.grid_measure(getattr(wrong, n), getattr(right, n)) for n in pr.TABLES}
+    print(f"grid pair {name}, {fault}: " + ", ".join(f"{n} {e:.2e}" for n, e in dist.items()))
+    assert max(dist.values()) >= 10 * fr.GRID_BOUND, dist

@@ -194,3 +194,67 @@ def test_the_reference_learns_to_rank_held_out_items():
     r_fism = recall_at_10(lambda u: st.Q @ fr.hidden(st, d.train_col[d.train_ptr[u]:d.train_ptr[u + 1]]) + st.bi, d)
     print(f"Recall@10: FISM {r_fism:.4f}, popularity {r_pop:.4f}")
     assert r_fism > r_pop
+
+
+# ---- the grid fixture (fism_ref.grid_*): the premises of tests/test_gpu_model_saturation.py -------------------------------------------
+def assert_grid_premises(first, classes, want_classes):
+    """the first predictions ARE the grid; 22 and 8 of its 53 points lie beyond +-18 and +-88.5 (test_mf_from_grid_scores' shares); the
+    run has met every class of saturated instance"""
+    np.testing.assert_array_equal(first, fr.grid().astype(first.dtype))
+    assert fr.share_beyond(first, 18) > 0.4 and fr.share_beyond(first, 88.5) > 0.14
+    assert all(classes.get(c, 0) >= 1 for c in want_classes), classes
+
+
+FISM_CLASSES = ((True, 1), (True, -1), (False, 1), (False, -1))          # (positive label?, the sign of a prediction beyond +-18)
+
+
+def test_the_grid_rows_leave_wavefronts_without_a_row():
+    d = fr.grid_data()
+    lens = np.diff(d.train_ptr)
+    assert (d.num_users, d.num_items) == (53, 100) and (lens == 5).all() and 5 < fr.WAVES
+    assert (d.train_col[d.train_ptr[:-1]] == np.arange(53)).all()             # user u's first item is item u
+    assert fr.scale_table(5, 0.5)[4] == 0.5
+    assert set(fr.GRID_CASES) == {"sq-ada", "log-ada", "ce-ada", "log-sgd", "ce-sgd", "log-ada-K300", "log-ada-nobias"}
+    assert fr.resident_rows(300) == fr.WAVES * 8 and fr.GRID_CASES["log-ada-K300"][0] == 300
+
+
+@pytest.mark.parametrize("name", list(fr.GRID_CASES))
+def test_the_grid_fixture_predicts_the_grid_and_stays_within_the_drift_premise(name):
+    """Every user's first instance predicts its grid point bit for bit, in float64 and in float32; over the two epochs the fp64 reference
+    meets a positive and a negative label on either side of +-18; and the same loop in float32 ends within GRID_BOUND / 4 of it, element
+    by element — so GRID_BOUND on the device measures the kernel."""
+    K, hyper = fr.GRID_CASES[name]
+    for dtype64 in (True, False):
+        assert_grid_premises(fr.grid_first(fr.grid_state(K, hyper, dtype64)), fr.grid_reference(name).classes, FISM_CLASSES)
+    ref = fr.grid_reference(name)
+    st32 = fr.grid_run(fr.train, K, hyper, dtype64=False)
+    drift = {n: fr.grid_measure(getattr(st32, n), getattr(ref, n)) for n in fr.State.TABLES}
+    print(f"grid {name}: max |pred| {ref.max_abs_pred:.4g}, classes {ref.classes}, drift " + ", ".join(f"{n} {e:.2e}" for n, e in drift.items()))
+    assert max(drift.values()) <= fr.GRID_DRIFT_MAX, drift
+    assert ref.max_abs_pred >= 1000.0
+
+
+def grid_fault_applies(fault, hyper):
+    loss = hyper["loss"]
+    return {"neg_label_0": loss == 2, "exp_sign": loss in (2, 5), "clamp18": loss == 0, "no_bias": hyper.get("bias", True),
+            "no_s_in_row_step": True}[fault]
+
+
+GRID_FAULT_CASES = [(f, n) for f in fr.FAULTS for n, (K, h) in fr.GRID_CASES.items() if K == 16 and grid_fault_applies(f, h)]
+
+
+@pytest.mark.parametrize("fault,name", GRID_FAULT_CASES)
+def test_the_grid_fixture_tells_a_faulty_saturated_instance_from_the_right_one(fault, name):
+    """The fp64 reference with ONE fault (fism_ref.FAULTS) ends at least 10 x GRID_BOUND from its true self on some compared table, in
+    the measure of the GPU test: on every case the fault can differ on (LOG's negative label on LOG; the exponent's sign on LOG and
+    CROSS_ENTROPY; the clamp on SQUARE; the biases where there are bias terms)."""
+    K, hyper = fr.GRID_CASES[name]
+    right = fr.grid_reference(name)
+    wrong = fr.grid_run(fr.train, K, hyper, fault=fault)
+    dist = {n: fr.grid_measure(getattr(wrong, n), getattr(right, n)) for n in fr.State.TABLES}
+    print(f"grid {name}, {fault}: " + ", ".join(f"{n} {e:.2e}" for n, e in dist.items()))
+    assert max(dist.values()) >= 10 * fr.GRID_BOUND, dist
+
+
+def test_every_fault_is_held_against_some_grid_case():
+    assert {f for f, _ in GRID_FAULT_CASES} == set(fr.FAULTS)

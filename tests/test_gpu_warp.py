@@ -22,6 +22,13 @@ bit for bit and in the recorded choices: P_UB zero against random; one call agai
 256-user launch window, enqueue_users + collect_stats (and the stats of each); a block handle's ranges cut between blocks; a handle
 with user_id_offset 3 against one with three users in front.  tests/test_warp_reference.py shows on the CPU that the 2e-4 bound would
 notice each of nine ways to write the loop wrong.
+
+The saturation pass added the losses that had never run in warp_user_kernel — SQUARE and CROSS_ENTROPY on the loop and on blocks of 8
+(D40, K = 24, the defaults) — and five cases whose item biases start uniform in +-100 (d40-loop-bias100-*: SQUARE, LOGISTIC, LOG, HINGE,
+CROSS_ENTROPY at learn rate 0.03).  Biases take no step, so those scores stay near +-100 and yui - score, what mf_loss_grad sees, goes
+down to -200: three quarters of the trained pairs lie below -18 and a sixth below -88.5, where __expf has overflowed, and SQUARE steps
+on gradients of 400 (tests/test_warp_reference.py asserts and prints the shares).  The method, tol, the cap and the 2e-4 bound are the
+same.  LOGISTIC has no other case: g = -1 / d near d = 0 cannot be pinned from small biases (warp_ref.CASES).
 """
 import numpy as np
 import pytest

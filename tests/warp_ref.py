@@ -131,7 +131,8 @@ class Draws:
 
 # ---- the model ----------------------------------------------------------------------------------------------------------------------
 class State:
-    def __init__(self, uv, uva, iv, iva, ib, *, lambda_=0.1, learn_rate=0.1, loss=3, adagrad=True, acc0=None, ib0=None):   # (acc0, ib0: init_state's)
+    def __init__(self, uv, uva, iv, iva, ib, *, lambda_=0.1, learn_rate=0.1, loss=3, adagrad=True, acc0=None, ib0=None,
+                 saturated=None):   # (acc0, ib0: init_state's; saturated: unmet()'s)
         self.uv, self.uva, self.iv, self.iva = (np.array(a, dtype=np.float64) for a in (uv, uva, iv, iva))
         self.ib = np.array(ib, dtype=np.float64)
         self.lam2, self.lr, self.loss, self.adagrad = 2.0 * lambda_, learn_rate, loss, adagrad
@@ -213,11 +214,12 @@ def train(st, draws, B=1, choices=None, tol=1e-3, positions=None, wrong=None):
     cnt1, cnt2_64, cnt65_499, exhausted, trained, max_abs_score, mixed_blocks (blocks with both a skipped and a trained pair); what the
     steps looked like: rank0, rank1, rank2 (trained pairs of users with one or two items left, by their rank weight l[0], l[1], l[2]),
     positives_twice (positives with two trained pairs), negatives_twice (trained pairs whose j the same user has stepped before),
-    rows_twice (item rows with two steps in one block's phase I), one_user_blocks (blocks of one user under B > 1: they run in place);
+    rows_twice (item rows with two steps in one block's phase I), one_user_blocks (blocks of one user under B > 1: they run in place),
+    pred_lt18, pred_lt88 (trained pairs whose yui - score, what the loss sees, lies below -18 and below -88.5);
     and record = (item, cnt) of the decisions taken, indexed as `choices`."""
     assert wrong is None or wrong in WRONG, wrong
     out = dict(comparisons=0, near=0, disagreements=0, bad=[], cnt1=0, cnt2_64=0, cnt65_499=0, exhausted=0, trained=0, max_abs_score=0.0,
-               mixed_blocks=0, rank0=0, rank1=0, rank2=0, positives_twice=0, negatives_twice=0, rows_twice=0, one_user_blocks=0,
+               mixed_blocks=0, rank0=0, rank1=0, rank2=0, positives_twice=0, negatives_twice=0, rows_twice=0, one_user_blocks=0, pred_lt18=0, pred_lt88=0,
                record=(np.full(draws.col.size * draws.num_neg, NONE, dtype=np.uint32), np.zeros(draws.col.size * draws.num_neg, dtype=np.uint32)))
     U, nn = draws.U, draws.num_neg
     lam2 = st.lam2 / 2.0 if wrong == "lambda-once" else st.lam2
@@ -283,6 +285,8 @@ def train(st, draws, B=1, choices=None, tol=1e-3, positions=None, wrong=None):
                     out["positives_twice"] += steps == 2
                     out["negatives_twice"] += j in before
                     pred = yui - yuj
+                    out["pred_lt18"] += pred < -18.0
+                    out["pred_lt88"] += pred < -88.5
                     if choices is not None and st.loss == 3:
                         # A followed decision says that the device saw a violator: pred < 1 in ITS arithmetic, while this one may be
                         # a hair above (a margin inside the band).  HINGE's gradient jumps from -1 to 0 exactly there: it is taken
@@ -409,6 +413,21 @@ CASES = [(f"d40-loop-K{K}", "d40", 1, K, 5, dict(acc0=a) if a else {}, 11, s)
     # a block handle whose range ends in a block of ONE user: that block runs in place
     ("d40p1-block8", "d40p1", 8, 24, 5, {}, 11, 1),
     ("tiny-block299", "tiny", 299, 24, 5, {}, 11, 1),
+    # The saturation pass.  SQUARE and CROSS_ENTROPY had never run in warp_user_kernel: the loop and blocks of 8 with the defaults.
+    ("d40-loop-square", "d40", 1, 24, 5, dict(loss=0), 11, 2),
+    ("d40-loop-ce", "d40", 1, 24, 5, dict(loss=5), 11, 2),
+    ("d40-block8-square", "d40", 8, 24, 5, dict(loss=0), 11, 1),
+    ("d40-block8-ce", "d40", 8, 24, 5, dict(loss=5), 11, 26),
+] + [
+    # ib0 = "uniform100": item biases uniform in +-100.  Biases are never stepped, so the scores stay near +-100 for the whole run and
+    # yui - score, what mf_loss_grad sees, reaches -200: beyond -18 and beyond -88.5, where __expf has overflowed (a trained pair has
+    # yui - score < 1, so only that side exists).  SQUARE then steps on gradients of 400.  `saturated` exempts exactly these cases from
+    # SCORE_MAX; unmet() asks them for trained pairs below -18 and below -88.5 in its place.  An fp32 score of 100 is still accurate to
+    # 1e-5, a hundredth of TOL.
+    # LOGISTIC's only pin is here: g = -1 / d near d = 0, so from biases of zero or +-0.5 its trajectory cannot be pinned (the float32
+    # reference ends 1.0, respectively 1.7e-3 ... 6.4e-2, from the float64 one); at d near -100 it is as smooth as the others.
+    (f"d40-loop-bias100-{n}", "d40", 1, 24, 5, dict(loss=l, ib0="uniform100", learn_rate=0.03, saturated=True), 11, 1)
+    for n, l in (("square", 0), ("logistic", 1), ("log", 2), ("hinge", 3), ("ce", 5))
 ]
 TOL = 1e-3                       # the band in which an fp32 and an fp64 margin may fall on different sides of 0
 NEAR_SHARE = 1e-3                # ... and the share of comparisons that may lie inside it
@@ -464,7 +483,8 @@ def run_free(case):
     for ep in range(EPOCHS):
         draws = Draws(ptr, col, d.num_items, nn, sseed, ep)
         o = train(st, draws, B)
-        train(st32, draws, B)
+        with np.errstate(over="ignore"):                 # float32: exp of a saturated difference overflows to inf and 1 / inf is 0, as on the device
+            train(st32, draws, B)
         for k, v in o.items():
             if k not in ("bad", "record"):
                 tot[k] = max(tot.get(k, 0.0), v) if k == "max_abs_score" else tot.get(k, 0) + v
@@ -484,8 +504,13 @@ def unmet(case, t):
         (case[2] == 1 or t["mixed_blocks"] >= 1, "no block both skips and trains pairs"),
         (t["near"] < NEAR_SHARE * t["comparisons"], f"near {t['near']} of {t['comparisons']}"),
         (t["drift"] <= DRIFT_MAX, f"drift {t['drift']:.3g}"),     # rounding alone leaves three quarters of the GPU test's bound to the kernel
-        (t["max_abs_score"] <= SCORE_MAX, f"|score| {t['max_abs_score']:.3g}"),
     ]
+    if case[5].get("saturated"):     # scores near +-100 on purpose: what the loss sees must reach both saturated regions
+        checks += [(t["pred_lt18"] >= 1, "no trained pair has yui - score below -18"),
+                   (t["pred_lt88"] >= 1, "no trained pair has yui - score below -88.5"),
+                   (t["max_abs_score"] > 88.5, f"|score| {t['max_abs_score']:.3g} does not leave the middle")]
+    else:
+        checks += [(t["max_abs_score"] <= SCORE_MAX, f"|score| {t['max_abs_score']:.3g}")]
     if case[1] == "d40dense":
         checks += [(t[f"rank{r}"] >= 1, f"no pair steps with the rank weight l[{r}]") for r in range(3)]
     if case[2] > 1 and fixture_data(case[1]).num_users % case[2] == 1:

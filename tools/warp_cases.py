@@ -1,7 +1,8 @@
 #!/usr/bin/env python
 """The search behind the stream seeds of tests/warp_ref.py's CASES: per case the first stream seed of 1, 2, 3, ... at which the
 free-running fp64 reference meets every premise tests/test_warp_reference.py asserts (warp_ref.unmet: every search depth, near-ties
-below NEAR_SHARE, float32 drift at most DRIFT_MAX, |score| at most SCORE_MAX, and what the case's data set adds).  CPU only.
+below NEAR_SHARE, float32 drift at most DRIFT_MAX, |score| at most SCORE_MAX — or, for a case marked `saturated`, trained pairs with
+yui - score below -18 and below -88.5 — and what the case's data set adds).  CPU only.
 Prints one line per case: the seed to write into the case's last field, and what the seeds before it missed.
 
     python tools/warp_cases.py [name ...]        (default: every case whose stream seed is 0, "not chosen yet")
