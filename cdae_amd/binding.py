@@ -95,6 +95,10 @@ EXPORTS = {
     "cdae_hip_als_half_step": (C.c_int, [C.c_void_p, C.c_uint32]),
     "cdae_hip_als_solve_rows": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
     "cdae_hip_als_gram": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t]),
+    "cdae_hip_als_set_confidence": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
+    "cdae_hip_als_solve_rows_weighted": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
+                                                  C.c_void_p]),
+    "cdae_hip_als_objective": (C.c_int, [C.c_void_p, C.c_void_p]),
     "cdae_hip_create_warp": (C.c_int, [C.POINTER(_WarpConfig), C.c_int, C.POINTER(C.c_void_p)]),
     "cdae_hip_warp_search": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]),
     "cdae_hip_warp_record_choices": (C.c_int, [C.c_void_p, C.c_uint32]),
@@ -796,6 +800,14 @@ class WRMF(MF):
     def solve_rows(self, row_ptr, col, x0=None, cg_steps: int = 0) -> np.ndarray:
         """Factors of caller-supplied rows (users outside the training set) against the frozen item table: CSR rows with ascending
         unique items, x0 None (zeros) or [n_rows, num_dim] start vectors -> [n_rows, num_dim].  The handle is not written."""
+        return self._solve_rows(row_ptr, col, x0, cg_steps, None, False)
+
+    def solve_rows_weighted(self, row_ptr, col, weights=None, x0=None, cg_steps: int = 0) -> np.ndarray:
+        """solve_rows with one confidence weight per entry of col — the caller's, not the handle's; None: the bits of solve_rows
+        (cdae_hip_als_solve_rows_weighted with w = NULL)."""
+        return self._solve_rows(row_ptr, col, x0, cg_steps, weights, True)
+
+    def _solve_rows(self, row_ptr, col, x0, cg_steps, weights, weighted_entry):
         rp, rc, _ = self._rows(row_ptr, col, None)
         n, K = rp.size - 1, self.cfg.num_dim
         a = None
@@ -804,9 +816,33 @@ class WRMF(MF):
             if a.shape != (n, K):
                 raise ValueError("x0 must be [n_rows, num_dim]")
         out = np.empty((n, K), dtype=np.float32)
-        _chk(self.lib, self.lib.cdae_hip_als_solve_rows(self.h, n, rp.ctypes.data, rc.ctypes.data, None if a is None else a.ctypes.data,
-                                                        cg_steps, out.ctypes.data))
+        if not weighted_entry:
+            _chk(self.lib, self.lib.cdae_hip_als_solve_rows(self.h, n, rp.ctypes.data, rc.ctypes.data, None if a is None else a.ctypes.data,
+                                                            cg_steps, out.ctypes.data))
+            return out
+        w = None
+        if weights is not None:
+            w = np.ascontiguousarray(weights, dtype=np.float32)
+            if w.shape != rc.shape:
+                raise ValueError("weights must hold one value per entry of col")
+        _chk(self.lib, self.lib.cdae_hip_als_solve_rows_weighted(self.h, n, rp.ctypes.data, rc.ctypes.data, None if w is None else w.ctypes.data,
+                                                                 None if a is None else a.ctypes.data, cg_steps, out.ctypes.data))
         return out
+
+    def set_confidence(self, w):
+        """Per-pair confidence weights: one finite value >= 0 per stored pair in the order of the train CSR's col (confidence
+        1 + scalar * w); None returns the handle to binary.  set_interactions drops them."""
+        if w is None:
+            _chk(self.lib, self.lib.cdae_hip_als_set_confidence(self.h, None, 0))
+            return
+        a = np.ascontiguousarray(w, dtype=np.float32).ravel()
+        _chk(self.lib, self.lib.cdae_hip_als_set_confidence(self.h, a.ctypes.data, a.size))
+
+    def objective(self):
+        """-> (data, penalty): sum over ALL pairs of c (p - x . y)^2 under the current confidences, and lambda (|X|^2 + |Y|^2)"""
+        out = np.zeros(2, dtype=np.float64)
+        _chk(self.lib, self.lib.cdae_hip_als_objective(self.h, out.ctypes.data))
+        return float(out[0]), float(out[1])
 
 
 @dataclass

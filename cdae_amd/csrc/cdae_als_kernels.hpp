@@ -128,11 +128,15 @@ __device__ __forceinline__ float als_dot(const float (&a)[NI], const float (&b)[
 
 // x0 == nullptr: every row starts from zero.  dst may be x0 (the half-step: in place; an empty row is then left as it is) or another
 // table (cdae_hip_als_solve_rows: an empty row receives its start vector).  row_ptr / col: the CSR of the n_rows rows, items < rows of Y.
-template <int NI>
+// WEIGHTED (cdae_hip_als_set_confidence, cdae_hip_als_solve_rows_weighted): w holds one confidence weight per entry of col, the pair's
+// confidence is 1 + alpha * w.  Per interaction the weight is read beside the item id (wavefront-uniform), the dot product y . p is
+// scaled by it before the axpy into sp, and b is accumulated as fmaf(fmaf(alpha, w, 1), y, sb) in CSR order, so the residual is sb - ap.
+// The binary form (WEIGHTED = false: a handle without weights) never reads w: b = (1 + alpha) * sum y.
+template <int NI, bool WEIGHTED = false>
 __global__ void __launch_bounds__(als_waves<NI>() * 64, 2)      // two wavefronts per SIMD: at most 256 registers per lane
 als_solve_kernel(const int64_t* __restrict__ row_ptr, const uint32_t* __restrict__ col, uint64_t n_rows,
                  const float* __restrict__ Y, const float* __restrict__ G, const float* x0, float* dst,
-                 float alpha, float lambda, uint32_t steps) {
+                 float alpha, float lambda, uint32_t steps, const float* __restrict__ w) {
   constexpr int WAVES = als_waves<NI>();
   constexpr int RPW = (int)ALS_BLOCK_ROWS / WAVES;           // rows per wavefront
   constexpr int Kp = 64 * NI;
@@ -230,32 +234,50 @@ als_solve_kernel(const int64_t* __restrict__ row_ptr, const uint32_t* __restrict
           for (int j = 0; j < 4; ++j) als_load_row<NI>(Y + (size_t)col[q + j] * Kp, lane, y[j]);
 #pragma unroll
           for (int j = 0; j < 4; ++j) d[j] = als_dot<NI>(y[j], p[t]);
+          float wq[4];
+          if constexpr (WEIGHTED) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) { wq[j] = w[q + j]; d[j] *= wq[j]; }
+          }
 #pragma unroll
           for (int j = 0; j < 4; ++j) {
 #pragma unroll
             for (int e = 0; e < NI; ++e) sp[e] = fmaf(y[j][e], d[j], sp[e]);
             if (it == 0) {
+              if constexpr (WEIGHTED) {
+                const float c = fmaf(alpha, wq[j], 1.f);
 #pragma unroll
-              for (int e = 0; e < NI; ++e) sb[e] += y[j][e];
+                for (int e = 0; e < NI; ++e) sb[e] = fmaf(c, y[j][e], sb[e]);
+              } else {
+#pragma unroll
+                for (int e = 0; e < NI; ++e) sb[e] += y[j][e];
+              }
             }
           }
         }
         for (; q < q1; ++q) {
           float y[NI];
           als_load_row<NI>(Y + (size_t)col[q] * Kp, lane, y);
-          const float d = als_dot<NI>(y, p[t]);
+          const float wq = WEIGHTED ? w[q] : 1.f;
+          const float d = WEIGHTED ? als_dot<NI>(y, p[t]) * wq : als_dot<NI>(y, p[t]);
 #pragma unroll
           for (int e = 0; e < NI; ++e) sp[e] = fmaf(y[e], d, sp[e]);
           if (it == 0) {
+            if constexpr (WEIGHTED) {
+              const float c = fmaf(alpha, wq, 1.f);
 #pragma unroll
-            for (int e = 0; e < NI; ++e) sb[e] += y[e];
+              for (int e = 0; e < NI; ++e) sb[e] = fmaf(c, y[e], sb[e]);
+            } else {
+#pragma unroll
+              for (int e = 0; e < NI; ++e) sb[e] += y[e];
+            }
           }
         }
 #pragma unroll
         for (int e = 0; e < NI; ++e) ap[e] = ap[e] + alpha * sp[e] + lambda * p[t][e];
         if (it == 0) {
 #pragma unroll
-          for (int e = 0; e < NI; ++e) { r[t][e] = (1.f + alpha) * sb[e] - ap[e]; p[t][e] = r[t][e]; }
+          for (int e = 0; e < NI; ++e) { r[t][e] = (WEIGHTED ? sb[e] : (1.f + alpha) * sb[e]) - ap[e]; p[t][e] = r[t][e]; }
           rs[t] = als_dot<NI>(r[t], r[t]);
         } else {
           const float a = rs[t] / als_dot<NI>(p[t], ap);
@@ -278,6 +300,54 @@ als_solve_kernel(const int64_t* __restrict__ row_ptr, const uint32_t* __restrict
     const uint64_t row = row0 + t;
     if (row < n_rows && (!in_place || row_ptr[row + 1] > row_ptr[row])) als_store_row<NI>(dst + row * Kp, lane, x[t]);
   }
+}
+
+// ---- the objective ---------------------------------------------------------------------------------------------------------------
+// L = sum_{all u,i} c_ui (p_ui - s_ui)^2 + lambda (|X|^2 + |Y|^2), s = x_u . y_i, is never formed densely:
+//   sum over all pairs of s^2 = <X^T X, Y^T Y>_F;   a stored pair adds c (1 - s)^2 - s^2;   the penalty is lambda (tr X^T X + tr Y^T Y).
+// als_objective_kernel: one wavefront per user row; s from the solve's lane layout and wave_sum in fp32, the pair's term accumulated
+// in fp64 in CSR order -> rows[u] (0 for an empty row).  The host adds rows[] in row order.  w == nullptr: every weight is 1.
+// als_objective_gram_kernel: ONE workgroup; the Frobenius product of the two Grams and their traces in fp64, every thread a strided
+// chain in ascending order and a fixed tree over the 256 threads: the same bits on every call.  No atomics anywhere.
+template <int NI>
+__global__ void __launch_bounds__(256)
+als_objective_kernel(const int64_t* __restrict__ row_ptr, const uint32_t* __restrict__ col, const float* __restrict__ w, uint64_t n_rows,
+                     const float* __restrict__ X, const float* __restrict__ Y, float alpha, double* __restrict__ rows) {
+  constexpr int Kp = 64 * NI;
+  const uint32_t lane = threadIdx.x % WAVE, wave = threadIdx.x / WAVE;
+  const uint64_t row = (uint64_t)blockIdx.x * 4u + wave;
+  if (row >= n_rows) return;                                 // (wavefront-uniform)
+  float x[NI];
+  als_load_row<NI>(X + row * Kp, lane, x);
+  double acc = 0.0;
+  const int64_t q1 = row_ptr[row + 1];
+  for (int64_t q = row_ptr[row]; q < q1; ++q) {
+    float y[NI];
+    als_load_row<NI>(Y + (size_t)col[q] * Kp, lane, y);
+    const double s = (double)als_dot<NI>(y, x);
+    const double c = 1.0 + (double)alpha * (double)(w ? w[q] : 1.f);
+    acc += c * (1.0 - s) * (1.0 - s) - s * s;
+  }
+  if (lane == 0) rows[row] = acc;
+}
+
+__global__ void __launch_bounds__(256)
+als_objective_gram_kernel(const float* __restrict__ Gx, const float* __restrict__ Gy, uint32_t Kp, double* __restrict__ out3) {
+  __shared__ double red[3][256];
+  const uint32_t t = threadIdx.x;
+  double f = 0.0, tx = 0.0, ty = 0.0;
+  for (uint32_t i = t; i < Kp * Kp; i += 256u) f += (double)Gx[i] * (double)Gy[i];
+  for (uint32_t i = t; i < Kp; i += 256u) { tx += (double)Gx[(size_t)i * Kp + i]; ty += (double)Gy[(size_t)i * Kp + i]; }
+  red[0][t] = f; red[1][t] = tx; red[2][t] = ty;
+  __syncthreads();
+  for (uint32_t step = 128u; step >= 1u; step >>= 1) {
+    if (t < step) {
+#pragma unroll
+      for (int k = 0; k < 3; ++k) red[k][t] += red[k][t + step];
+    }
+    __syncthreads();
+  }
+  if (t < 3u) out3[t] = red[t][0];
 }
 
 }  // namespace cdae

@@ -253,6 +253,25 @@ inline ItemMajor item_major_csr(uint64_t U, uint64_t I, const int64_t* row_ptr, 
   return t;
 }
 
+// WRMF with per-pair confidence weights (cdae_hip_als_set_confidence): w holds one weight per entry of col; the result holds the same
+// weights in the order of item_major_csr's col — the same counting sort, so entry k of the result belongs to entry k of ItemMajor::col.
+// The column starts are rebuilt from col (the caller need not have kept the plan).
+inline std::vector<float> item_major_weights(uint64_t U, uint64_t I, const int64_t* row_ptr, const uint32_t* col, const float* w) {
+  std::vector<int64_t> cursor(I + 1, 0);
+  for (int64_t p = row_ptr[0]; p < row_ptr[U]; ++p) cursor[col[p] + 1]++;
+  for (uint64_t i = 0; i < I; ++i) cursor[i + 1] += cursor[i];
+  std::vector<float> t(std::max<size_t>((size_t)(row_ptr[U] - row_ptr[0]), 1), 0.f);
+  for (uint64_t u = 0; u < U; ++u)
+    for (int64_t p = row_ptr[u]; p < row_ptr[u + 1]; ++p) t[(size_t)cursor[col[p]]++] = w[p];
+  return t;
+}
+// a weight array as cdae_hip_als_set_confidence accepts it: every value finite and >= 0
+inline std::string check_weights(const float* w, size_t count) {
+  for (size_t p = 0; p < count; ++p)
+    if (!(w[p] >= 0.f) || !(w[p] <= 3.402823466e38f)) return refuse("weight %g at position %zu: a confidence weight must be finite and >= 0", (double)w[p], p);
+  return {};
+}
+
 // the shared (item-side) parameter block: [W | W_ag | (V | V_ag) | bp | bp_ag | b | b_ag], padded element counts
 struct ParamLayout {
   size_t off[CDAE_P_COUNT] = {0}, cnt[CDAE_P_COUNT] = {0};

@@ -295,7 +295,13 @@ struct cdae_hip {
   // start vectors / solutions of one chunk of cdae_hip_als_solve_rows (its CSR shares d_rows_ptr / d_rows_col).  Grow-only.
   DevBuf<int64_t> d_tptr; DevBuf<uint32_t> d_tcol;
   DevBuf<float> d_als_G, d_als_part, d_als_x, d_als_out;
+  // per-pair confidence weights (cdae_hip_als_set_confidence): user-major in the order of d_col, item-major in the order of d_tcol; null
+  // = a binary handle (dropped with the data set).  d_als_rw: the weights of one cdae_hip_als_solve_rows_weighted call.  d_als_G2: the
+  // second Gram of cdae_hip_als_objective; d_als_obj: its per-row terms, then <Gx, Gy>_F and the two traces.
+  DevBuf<float> d_als_w, d_als_tw, d_als_rw, d_als_G2;
+  DevBuf<double> d_als_obj;
   uint32_t als_steps = 0; float als_alpha = 0.f, als_lambda = 0.f;
+  double als_lambda_cfg = 0.;            // lambda as configured (the objective's penalty is formed in fp64)
   // WARP handles (cdae_hip_create_warp, cdae_warp_kernels.hpp): the rank weights l[num_items] (cdae_warp_host.h, filled per data set); the
   // record of the last training calls' choices, [nnz * num_neg] by position, allocated by the first cdae_hip_warp_record_choices(1) and
   // dropped with the data set; the outputs of one chunk of cdae_hip_warp_search (grow-only)
@@ -570,7 +576,7 @@ template <class F> void visit_data_set_bufs(cdae_hip* h, F&& f) {
     h->d_flt_eptr, h->d_flt_ecol, h->d_flt_allow, h->d_flt_pos, h->d_flt_D, h->d_flt_bp,
     h->d_sim_q, h->d_sim_iota, h->d_sim_T, h->d_sim_zero,
     h->d_guest[0], h->d_guest[1], h->d_guest[2], h->d_guest[3], h->d_fold[0], h->d_fold[1], h->d_fold[2], h->d_fold[3],
-    h->d_fold_long, h->d_als_G, h->d_als_part, h->d_als_x, h->d_als_out,
+    h->d_fold_long, h->d_als_G, h->d_als_part, h->d_als_x, h->d_als_out, h->d_als_w, h->d_als_tw, h->d_als_rw, h->d_als_G2, h->d_als_obj,
     h->d_warp_l, h->d_warp_rec_item, h->d_warp_rec_cnt, h->d_warp_out_item, h->d_warp_out_cnt, h->d_warp_out_margin,
     h->d_fism_scale);
 }
@@ -1584,7 +1590,7 @@ int cdae_hip_create_als(const cdae_als_config* ac, int device_id, cdae_hip_t** o
   h->mf = 3u; h->mf_bias = 0u;
   h->mf_seq = true; h->B = MF_SEQ_USERS;
   h->als_steps = ac->cg_steps ? ac->cg_steps : CDAE_ALS_DEFAULT_CG_STEPS;
-  h->als_alpha = (float)ac->alpha; h->als_lambda = (float)ac->lambda;
+  h->als_alpha = (float)ac->alpha; h->als_lambda = (float)ac->lambda; h->als_lambda_cfg = ac->lambda;
   return 0;
 }
 
@@ -3568,25 +3574,33 @@ int cdae_hip_similar_items(cdae_hip_t* h, uint64_t n_queries, const uint32_t* qu
 
 // ---- WRMF by alternating least squares (cdae_als_kernels.hpp) ------------------------------------------------------
 namespace {
-// G = T^T T of `rows` rows into h->d_als_G: per-slice partials, then the fold in slice order
-int als_gram(cdae_hip* h, const float* T, uint64_t rows) {
+// G = T^T T of `rows` rows into G (h->d_als_G; cdae_hip_als_objective's second Gram: h->d_als_G2): per-slice partials, then the fold
+// in slice order
+int als_gram(cdae_hip* h, const float* T, uint64_t rows, DevBuf<float>& G) {
   const uint32_t Kp = h->Kp, slices = cdae::als_gram_slices(rows), tiles = Kp / 32u;
-  CHK(h->d_als_G.ensure((size_t)Kp * Kp));
+  CHK(G.ensure((size_t)Kp * Kp));
   CHK(h->d_als_part.ensure((size_t)cdae::ALS_GRAM_SLICES_MAX * Kp * Kp));
   hipLaunchKernelGGL(cdae::als_gram_kernel, dim3(tiles * tiles, slices), dim3(64), 0, h->stream, T, rows, Kp, (float*)h->d_als_part);
   hipLaunchKernelGGL(cdae::als_gram_fold_kernel, dim3((Kp * Kp + 255u) / 256u), dim3(256), 0, h->stream, (const float*)h->d_als_part, slices,
-                     Kp * Kp, (float*)h->d_als_G);
+                     Kp * Kp, (float*)G);
   HIPCHK(hipGetLastError());
   return 0;
 }
-// n rows of the CSR (ptr, col) solved against the table Y and h->d_als_G, 32 rows per workgroup
-int als_solve(cdae_hip* h, const int64_t* ptr, const uint32_t* col, uint64_t n, const float* Y, const float* x0, float* dst, uint32_t steps) {
+int als_gram(cdae_hip* h, const float* T, uint64_t rows) { return als_gram(h, T, rows, h->d_als_G); }
+// n rows of the CSR (ptr, col) solved against the table Y and h->d_als_G, 32 rows per workgroup; w: one confidence weight per entry
+// of col, or null for the binary kernel
+int als_solve(cdae_hip* h, const int64_t* ptr, const uint32_t* col, const float* w, uint64_t n, const float* Y, const float* x0, float* dst,
+              uint32_t steps) {
   return dispatch_ni(h->NI, [&](auto ni) {
     constexpr int NI = decltype(ni)::value;
     constexpr size_t lds = cdae::als_solve_lds_bytes<NI>();
-    HIPCHK(hipFuncSetAttribute((const void*)cdae::als_solve_kernel<NI>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL((cdae::als_solve_kernel<NI>), dim3((uint32_t)((n + cdae::ALS_BLOCK_ROWS - 1) / cdae::ALS_BLOCK_ROWS)), dim3(cdae::als_waves<NI>() * 64), lds,
-                       h->stream, ptr, col, n, Y, (const float*)h->d_als_G, x0, dst, h->als_alpha, h->als_lambda, steps);
+    const dim3 grid((uint32_t)((n + cdae::ALS_BLOCK_ROWS - 1) / cdae::ALS_BLOCK_ROWS)), block(cdae::als_waves<NI>() * 64);
+    const void* const kernel = w ? (const void*)cdae::als_solve_kernel<NI, true> : (const void*)cdae::als_solve_kernel<NI, false>;
+    HIPCHK(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    if (w) hipLaunchKernelGGL((cdae::als_solve_kernel<NI, true>), grid, block, lds, h->stream, ptr, col, n, Y, (const float*)h->d_als_G, x0, dst,
+                              h->als_alpha, h->als_lambda, steps, w);
+    else hipLaunchKernelGGL((cdae::als_solve_kernel<NI, false>), grid, block, lds, h->stream, ptr, col, n, Y, (const float*)h->d_als_G, x0, dst,
+                            h->als_alpha, h->als_lambda, steps, (const float*)nullptr);
     HIPCHK(hipGetLastError());
     return 0;
   });
@@ -3602,10 +3616,10 @@ int als_half_step(cdae_hip* h, uint32_t side) {
   float* X = h->d_Wu; float* Y = h->P(CDAE_P_W);
   if (side == CDAE_ALS_USERS) {
     CHK(als_gram(h, Y, h->I));
-    return als_solve(h, h->d_row_ptr, h->d_col, h->U, Y, X, X, h->als_steps);
+    return als_solve(h, h->d_row_ptr, h->d_col, h->d_als_w, h->U, Y, X, X, h->als_steps);
   }
   CHK(als_gram(h, X, h->U));
-  return als_solve(h, h->d_tptr, h->d_tcol, h->I, X, Y, Y, h->als_steps);
+  return als_solve(h, h->d_tptr, h->d_tcol, h->d_als_tw, h->I, X, Y, Y, h->als_steps);
 }
 constexpr uint64_t ALS_ROWS_CHUNK = 32768;
 }  // namespace
@@ -3718,17 +3732,25 @@ int cdae_hip_als_gram(cdae_hip_t* h, uint32_t side, float* out, size_t count) {
   return 0;
 }
 
-int cdae_hip_als_solve_rows(cdae_hip_t* h, uint64_t n_rows, const int64_t* row_ptr, const uint32_t* col, const float* x0,
-                            uint32_t cg_steps, float* out_x) {
-  const char* fn = "cdae_hip_als_solve_rows";
+static int als_solve_rows(cdae_hip* h, const char* fn, uint64_t n_rows, const int64_t* row_ptr, const uint32_t* col, const float* w,
+                          const float* x0, uint32_t cg_steps, float* out_x) {
   CHK(als_check(h, fn));
   if (n_rows == 0) return 0;
   CHK(validate_rows_csr("rated", row_ptr, col, n_rows, h->I));
   if (!out_x) return fail("%s: null out_x", fn);
+  const size_t nnz = (size_t)row_ptr[n_rows];
+  if (w) {
+    const std::string refusal = cdae::plan::check_weights(w, nnz);
+    if (!refusal.empty()) return fail("%s: %s", fn, refusal.c_str());
+  }
   HIPCHK(hipSetDevice(h->device));
   const uint32_t steps = cg_steps ? cg_steps : h->als_steps;
   const size_t chunk = (size_t)std::min<uint64_t>(n_rows, ALS_ROWS_CHUNK);
   CHK(upload_csr(h, h->d_rows_ptr, h->d_rows_col, row_ptr, col, n_rows));
+  if (w) {
+    CHK(h->d_als_rw.ensure(std::max<size_t>(nnz, 1)));
+    if (nnz) HIPCHK(hipMemcpyAsync(h->d_als_rw, w, nnz * sizeof(float), hipMemcpyHostToDevice, h->stream));
+  }
   CHK(h->d_als_out.ensure(chunk * h->Kp));
   if (x0) CHK(h->d_als_x.ensure(chunk * h->Kp));
   const float* Y = h->P(CDAE_P_W);
@@ -3740,10 +3762,81 @@ int cdae_hip_als_solve_rows(cdae_hip_t* h, uint64_t n_rows, const int64_t* row_p
       HIPCHK(hipMemsetAsync(h->d_als_x, 0, nu * wKp, h->stream));
       HIPCHK(hipMemcpy2DAsync(h->d_als_x, wKp, x0 + c0 * h->K, wK, wK, nu, hipMemcpyHostToDevice, h->stream));
     }
-    CHK(als_solve(h, h->d_rows_ptr.p + c0, h->d_rows_col.p, nu, Y, x0 ? (const float*)h->d_als_x.p : nullptr, h->d_als_out.p, steps));
+    CHK(als_solve(h, h->d_rows_ptr.p + c0, h->d_rows_col.p, w ? (const float*)h->d_als_rw.p : nullptr, nu, Y,
+                  x0 ? (const float*)h->d_als_x.p : nullptr, h->d_als_out.p, steps));
     HIPCHK(hipMemcpy2DAsync(out_x + c0 * h->K, wK, h->d_als_out, wKp, wK, nu, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));                // the two chunk buffers are the next chunk's too
   }
+  return 0;
+}
+
+int cdae_hip_als_solve_rows(cdae_hip_t* h, uint64_t n_rows, const int64_t* row_ptr, const uint32_t* col, const float* x0,
+                            uint32_t cg_steps, float* out_x) {
+  return als_solve_rows(h, "cdae_hip_als_solve_rows", n_rows, row_ptr, col, nullptr, x0, cg_steps, out_x);
+}
+
+int cdae_hip_als_solve_rows_weighted(cdae_hip_t* h, uint64_t n_rows, const int64_t* row_ptr, const uint32_t* col, const float* w,
+                                     const float* x0, uint32_t cg_steps, float* out_x) {
+  return als_solve_rows(h, "cdae_hip_als_solve_rows_weighted", n_rows, row_ptr, col, w, x0, cg_steps, out_x);
+}
+
+int cdae_hip_als_set_confidence(cdae_hip_t* h, const float* w, size_t count) {
+  const char* fn = "cdae_hip_als_set_confidence";
+  CHK(als_check(h, fn));
+  const size_t nnz = (size_t)h->h_row_ptr[h->U];
+  if (!w && count == 0) {                                   // back to binary
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    CHK(h->d_als_w.drop());
+    return h->d_als_tw.drop();
+  }
+  if (!w) return fail("%s: null weights with count %zu", fn, count);
+  if (count != nnz) return fail("%s: the data set holds %zu interactions, the caller's array %zu weights", fn, nnz, count);
+  const std::string refusal = cdae::plan::check_weights(w, count);
+  if (!refusal.empty()) return fail("%s: %s", fn, refusal.c_str());
+  HIPCHK(hipSetDevice(h->device));
+  HIPCHK(hipStreamSynchronize(h->stream));                  // no half-step is still reading the weights this call replaces
+  std::vector<uint32_t> col(std::max<size_t>(nnz, 1));
+  if (nnz) HIPCHK(hipMemcpy(col.data(), h->d_col, nnz * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  const std::vector<float> tw = cdae::plan::item_major_weights(h->U, h->I, h->h_row_ptr.data(), col.data(), w);
+  // both buffers exist before either is written: a failed allocation leaves the weights the handle had
+  DevBuf<float> uw, iw;
+  CHK(uw.alloc(nnz)); CHK(iw.alloc(nnz));
+  if (nnz) {
+    HIPCHK(hipMemcpy(uw.p, w, nnz * sizeof(float), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(iw.p, tw.data(), nnz * sizeof(float), hipMemcpyHostToDevice));
+  }
+  h->d_als_w = std::move(uw); h->d_als_tw = std::move(iw);
+  return 0;
+}
+
+int cdae_hip_als_objective(cdae_hip_t* h, double* out2) {
+  const char* fn = "cdae_hip_als_objective";
+  CHK(als_check(h, fn));
+  if (!out2) return fail("%s: null out2", fn);
+  HIPCHK(hipSetDevice(h->device));
+  const float* X = h->d_Wu; const float* Y = h->P(CDAE_P_W);
+  const uint64_t U = h->U;
+  CHK(als_gram(h, X, U, h->d_als_G));
+  CHK(als_gram(h, Y, h->I, h->d_als_G2));
+  CHK(h->d_als_obj.ensure((size_t)U + 3));
+  CHK(dispatch_ni(h->NI, [&](auto ni) {
+    constexpr int NI = decltype(ni)::value;
+    hipLaunchKernelGGL((cdae::als_objective_kernel<NI>), dim3((uint32_t)((U + 3) / 4)), dim3(256), 0, h->stream, (const int64_t*)h->d_row_ptr,
+                       (const uint32_t*)h->d_col, (const float*)h->d_als_w, U, X, Y, h->als_alpha, h->d_als_obj.p);
+    HIPCHK(hipGetLastError());
+    return 0;
+  }));
+  hipLaunchKernelGGL(cdae::als_objective_gram_kernel, dim3(1), dim3(256), 0, h->stream, (const float*)h->d_als_G, (const float*)h->d_als_G2, h->Kp,
+                     h->d_als_obj.p + U);
+  HIPCHK(hipGetLastError());
+  std::vector<double> host((size_t)U + 3);
+  HIPCHK(hipMemcpyAsync(host.data(), h->d_als_obj, host.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  double sparse = 0.0;
+  for (uint64_t u = 0; u < U; ++u) sparse += host[u];       // in row order
+  out2[0] = host[U] + sparse;
+  out2[1] = h->als_lambda_cfg * (host[U + 1] + host[U + 2]);
   return 0;
 }
 

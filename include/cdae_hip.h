@@ -97,7 +97,10 @@ extern "C" {
  *     also under 12, the version unchanged (new entry points; nothing existing changed): cdae_fism_config, cdae_hip_create_fism,
  *     cdae_hip_fism_plan, cdae_hip_fism_set_resident — FISM: factored item similarity, the user's rows kept on chip for a visit
  *     also under 12, the version unchanged (a new entry point; nothing existing changed): cdae_hip_create_fism_pair — FISMauc, the
- *     pairwise form of FISM on the FISM handle */
+ *     pairwise form of FISM on the FISM handle
+ *     also under 12, the version unchanged (new entry points; nothing existing changed): cdae_hip_als_set_confidence,
+ *     cdae_hip_als_solve_rows_weighted, cdae_hip_als_objective — per-pair confidence weights for WRMF and the objective its
+ *     half-steps minimise */
 #define CDAE_HIP_ABI_VERSION 12
 
 /* numeric values follow libcf::LossType (/root/reference/src/model/loss.hpp:10-18) */
@@ -757,6 +760,31 @@ int cdae_hip_als_solve_rows(cdae_hip_t* h, uint64_t n_rows, const int64_t* row_p
 /* G = T^T T of the current user (CDAE_ALS_USERS) or item (CDAE_ALS_ITEMS) table as the half-steps compute it, [num_dim x num_dim]
  * row-major: a test hook (the same table gives the same bits on every call). */
 int cdae_hip_als_gram(cdae_hip_t* h, uint32_t side, float* out, size_t count);
+/* Per-pair confidence weights (the paper's c_ui = 1 + alpha * r_ui with r_ui a play count, a dwell time, a log-scaled count).  w is one
+ * fp32 value per stored pair in the order of the train CSR's col, each finite and >= 0.  A stored pair keeps preference 1 and gets
+ * confidence 1 + alpha * w; everything else keeps preference 0 and confidence 1.  The user half-step becomes
+ *     A_u = G + alpha * sum_{i in R_u} w_ui y_i y_i^T + lambda * I,     b_u = sum_{i in R_u} (1 + alpha * w_ui) y_i
+ * with the same CG loop and the same 1e-20 stop; the item half-step is the same over the item-major CSR with the weights carried
+ * through the same permutation.  A pair with w = 0 is legal: it adds y_i to b and nothing to the sparse part of A.  A handle that was
+ * never given weights runs the binary kernel; w = 1 everywhere is the binary model (the same bits wherever the sums are exact).
+ *   count must equal the interaction count of the last cdae_hip_set_interactions; the values are copied.
+ *   w == NULL with count == 0 returns the handle to binary.
+ *   A negative, NaN or infinite value, a wrong count, a handle without a data set or a non-WRMF handle is refused before anything is
+ *   written, and the handle keeps the weights it had.  A new cdae_hip_set_interactions drops the weights: the new data set is binary. */
+int cdae_hip_als_set_confidence(cdae_hip_t* h, const float* w, size_t count);
+/* cdae_hip_als_solve_rows with one weight per entry of col (the CALLER's weights, not the handle's): the same chunks, validation and
+ * zero-row behaviour; a weight that is negative or not finite is refused before a launch.  w == NULL gives exactly the bits of
+ * cdae_hip_als_solve_rows.  The train rows and train weights with x0 = the current user factors return the bits
+ * cdae_hip_als_half_step(CDAE_ALS_USERS) would write. */
+int cdae_hip_als_solve_rows_weighted(cdae_hip_t* h, uint64_t n_rows, const int64_t* row_ptr, const uint32_t* col, const float* w,
+                                     const float* x0, uint32_t cg_steps, float* out_x);
+/* The objective the half-steps minimise, for the current tables under the handle's current confidences (a binary handle: w = 1):
+ *     out2[0] = sum_{all u,i} c_ui (p_ui - x_u . y_i)^2         out2[1] = lambda (|X|^2 + |Y|^2)
+ * It is never formed densely: with s = x_u . y_i, the sum of s^2 over ALL pairs is <X^T X, Y^T Y>_F, a stored pair adds
+ * c (1 - s)^2 - s^2, and the penalty is lambda (trace X^T X + trace Y^T Y).  The Grams are the half-steps' (fp32), s is an fp32 dot
+ * product, everything else is accumulated in fp64 in a fixed order: the same state gives the same bits on every call.  No parameter is
+ * written.  cdae_hip_data_loss and cdae_hip_penalty_loss of a WRMF handle stay 0. */
+int cdae_hip_als_objective(cdae_hip_t* h, double* out2);
 
 /* ---- WARP: rank-weighted pairwise matrix factorisation (Weston, Bengio, Usunier, "WSABIE"; the reference's src/model/recsys/warp.hpp,
  * `class WARP : public IMF`), on the same handle type --------------------------------------------------------------------------------

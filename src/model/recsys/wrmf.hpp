@@ -9,6 +9,10 @@
 //   train_one_iteration (102-109)         cdae_hip_train_epoch: the user half-step, then the item half-step
 //   half_step                             cdae_hip_als_half_step
 //   solve_rows                            cdae_hip_als_solve_rows: factors of rows outside the training set
+//   solve_rows (with weights)             cdae_hip_als_solve_rows_weighted: the same with one confidence weight per item
+//   objective                             cdae_hip_als_objective: the data term and the penalty the half-steps minimise
+// WRMFConfig::use_ratings (not in the reference's struct; wrmf.hpp:76-96 multiplies by rating * scalar_): reset passes the Data labels,
+// in the order of to_csr, to cdae_hip_als_set_confidence — confidence 1 + scalar * label on a stored pair.  The default is binary.
 // The system solved per row is the paper's, G + alpha sum y y^T + lambda I with G = Y^T Y, by cg_steps iterations of conjugate
 // gradients.  The reference's literal train_one_index (66-100) omits the Y^T Y term and is deliberately not offered (cdae_hip.h).
 #ifndef CDAE_HOST_MODEL_RECSYS_WRMF_HPP_
@@ -26,17 +30,18 @@ struct WRMFConfig {
   PenaltyType pt = L2;
   size_t num_dim = 10;
   size_t cg_steps = 3;       // not in the reference: conjugate-gradient iterations per row and half-step
+  bool use_ratings = false;  // not in the reference's struct: the labels are per-pair confidence weights (1 + scalar * label)
 };
 
 class WRMF : public IMF {
  public:
-  explicit WRMF(const WRMFConfig& mcfg) : scalar_(mcfg.scalar), cg_steps_(mcfg.cg_steps) {
+  explicit WRMF(const WRMFConfig& mcfg) : scalar_(mcfg.scalar), cg_steps_(mcfg.cg_steps), use_ratings_(mcfg.use_ratings) {
     lambda_ = mcfg.lambda; num_dim_ = mcfg.num_dim; lt_ = mcfg.lt;
     loss_ = Loss::create(mcfg.lt);
     penalty_ = Penalty::create(mcfg.pt);
     LOG(INFO) << "WRMF Configure (MI355X / HIP): \n"
               << "\t{lambda: " << lambda_ << "}, {Loss: " << loss_->loss_type() << "}, {Penalty: " << penalty_->penalty_type() << "}\n"
-              << "\t{Dim: " << num_dim_ << "}, {Scalar: " << scalar_ << "}, {CG steps: " << cg_steps_ << "}";
+              << "\t{Dim: " << num_dim_ << "}, {Scalar: " << scalar_ << "}, {CG steps: " << cg_steps_ << "}, {Ratings: " << use_ratings_ << "}";
   }
   WRMF() : WRMF(WRMFConfig()) {}
 
@@ -54,6 +59,16 @@ class WRMF : public IMF {
     auto csr = std::make_shared<Csr>();
     data_->to_csr(0, 1, csr->row_ptr, csr->col);
     CDAE_HIP_CHECK(cdae_hip_set_interactions(raw, num_users_, num_items_, csr->row_ptr.data(), csr->col.data()));
+    if (use_ratings_) {                                       // the labels in the order of to_csr (a repeated pair: its first label)
+      const auto labels = data_->get_feature_pair_label_hashtable(0, 1);
+      std::vector<float> w(csr->col.size());
+      for (size_t u = 0; u < num_users_; ++u) {
+        if (csr->row_ptr[u + 1] == csr->row_ptr[u]) continue;
+        const auto& row = labels.at(u);
+        for (int64_t p = csr->row_ptr[u]; p < csr->row_ptr[u + 1]; ++p) w[p] = static_cast<float>(row.at(csr->col[p]));
+      }
+      CDAE_HIP_CHECK(cdae_hip_als_set_confidence(raw, w.data(), w.size()));
+    }
     csr_ = csr;
     train_generation_ = data_->generation();
     test_generation_ = std::make_shared<uint64_t>(0);
@@ -83,15 +98,39 @@ class WRMF : public IMF {
   std::vector<std::vector<float>> solve_rows(const std::vector<std::vector<size_t>>& rows,
                                             const std::vector<std::vector<float>>& start = std::vector<std::vector<float>>(),
                                             size_t cg_steps = 0) const {
+    return solve_rows_impl(rows, nullptr, start, cg_steps);
+  }
+  // ... with per-pair confidence weights: weights[r][k] belongs to rows[r][k] (the caller's weights, not the model's)
+  std::vector<std::vector<float>> solve_rows(const std::vector<std::vector<size_t>>& rows, const std::vector<std::vector<float>>& weights,
+                                            const std::vector<std::vector<float>>& start, size_t cg_steps) const {
+    CHECK_EQ(weights.size(), rows.size());
+    return solve_rows_impl(rows, &weights, start, cg_steps);
+  }
+
+  // {data term, penalty term} of the objective the half-steps minimise, under the model's confidences (cdae_hip_als_objective)
+  std::pair<double, double> objective() const {
+    std::lock_guard<std::mutex> lk(*mu_);
+    CHECK(dev_ != nullptr) << "reset() must be called first";
+    double out[2] = {0., 0.};
+    CDAE_HIP_CHECK(cdae_hip_als_objective(dev_.get(), out));
+    return std::make_pair(out[0], out[1]);
+  }
+
+ protected:
+  std::vector<std::vector<float>> solve_rows_impl(const std::vector<std::vector<size_t>>& rows, const std::vector<std::vector<float>>* weights,
+                                                 const std::vector<std::vector<float>>& start, size_t cg_steps) const {
     std::lock_guard<std::mutex> lk(*mu_);
     CHECK(dev_ != nullptr) << "reset() must be called first";
     CHECK(start.empty() || start.size() == rows.size());
     std::vector<int64_t> ptr(rows.size() + 1, 0);
     std::vector<uint32_t> col;
+    std::vector<float> w;
     for (size_t r = 0; r < rows.size(); ++r) {
-      std::vector<uint32_t> s(rows[r].begin(), rows[r].end());
+      std::vector<std::pair<uint32_t, float>> s(rows[r].size());
+      if (weights) CHECK_EQ((*weights)[r].size(), rows[r].size());
+      for (size_t k = 0; k < s.size(); ++k) s[k] = std::make_pair(static_cast<uint32_t>(rows[r][k]), weights ? (*weights)[r][k] : 1.f);
       std::sort(s.begin(), s.end());
-      col.insert(col.end(), s.begin(), s.end());
+      for (const auto& e : s) { col.push_back(e.first); w.push_back(e.second); }
       ptr[r + 1] = static_cast<int64_t>(col.size());
     }
     std::vector<float> x0, out(rows.size() * num_dim_);
@@ -99,16 +138,20 @@ class WRMF : public IMF {
       CHECK_EQ(v.size(), num_dim_);
       x0.insert(x0.end(), v.begin(), v.end());
     }
-    CDAE_HIP_CHECK(cdae_hip_als_solve_rows(dev_.get(), rows.size(), ptr.data(), col.data(), start.empty() ? nullptr : x0.data(),
-                                           static_cast<uint32_t>(cg_steps), out.data()));
+    if (weights)
+      CDAE_HIP_CHECK(cdae_hip_als_solve_rows_weighted(dev_.get(), rows.size(), ptr.data(), col.data(), w.data(), start.empty() ? nullptr : x0.data(),
+                                                      static_cast<uint32_t>(cg_steps), out.data()));
+    else
+      CDAE_HIP_CHECK(cdae_hip_als_solve_rows(dev_.get(), rows.size(), ptr.data(), col.data(), start.empty() ? nullptr : x0.data(),
+                                             static_cast<uint32_t>(cg_steps), out.data()));
     std::vector<std::vector<float>> ret(rows.size());
     for (size_t r = 0; r < rows.size(); ++r) ret[r].assign(out.begin() + r * num_dim_, out.begin() + (r + 1) * num_dim_);
     return ret;
   }
 
- protected:
   double scalar_ = 40.;
   size_t cg_steps_ = 3;
+  bool use_ratings_ = false;
 };
 
 }  // namespace libcf

@@ -7,6 +7,9 @@
                                                  ... and the report: the timed epoch with its two floors, and the worst half-step
                                                  parity error per K tier from FILE (what tests/test_gpu_als.py appends to the file
                                                  named by CDAE_ALS_MEASURED)
+    python tools/als_bench.py --weighted         the same process also times the epoch with per-pair confidence weights (geometric(0.3) play
+                                                 counts through cdae_hip_als_set_confidence: one 4-byte load more per interaction and product)
+                                                 and one cdae_hip_als_objective call -> "weighted_*" and "objective_seconds" in the JSON line
 The two floors the time can be read against, both from the shapes (estimates, not measurements):
   matrix work   4 (U + I) 2 Kp^2 flops per half-step pair — (cg_steps + 1) = 4 products G p per row of either side, 2 Kp^2 flops each —
                 at the fp32 matrix rate;
@@ -36,8 +39,24 @@ def one_process(a):
         m.train_one_iteration()
     t = [m.train_one_iteration().wall_seconds for _ in range(a.epochs)]
     Kp = int(m.lib.cdae_hip_row_stride(m.h))
-    print(json.dumps({"shape": a.shape, "users": d.num_users, "items": d.num_items, "nnz": int(d.train_ptr[-1]), "num_dim": a.num_dim,
-                      "row_stride": Kp, "cg_steps": a.cg_steps, "epoch_seconds": t, "median_epoch_seconds": statistics.median(t)}))
+    out = {"shape": a.shape, "users": d.num_users, "items": d.num_items, "nnz": int(d.train_ptr[-1]), "num_dim": a.num_dim,
+           "row_stride": Kp, "cg_steps": a.cg_steps, "epoch_seconds": t, "median_epoch_seconds": statistics.median(t)}
+    if a.weighted:
+        import time
+        import numpy as np
+        m.set_confidence(np.random.default_rng(7).geometric(0.3, int(d.train_ptr[-1])).astype(np.float32))
+        for _ in range(a.warmup):
+            m.train_one_iteration()
+        tw = [m.train_one_iteration().wall_seconds for _ in range(a.epochs)]
+        m.objective()                                         # (the second Gram buffer and the per-row terms are allocated here)
+        to = []
+        for _ in range(a.epochs):
+            t0 = time.perf_counter()
+            m.objective()
+            to.append(time.perf_counter() - t0)
+        out.update({"weighted_epoch_seconds": tw, "weighted_median_epoch_seconds": statistics.median(tw),
+                    "objective_seconds": to, "median_objective_seconds": statistics.median(to)})
+    print(json.dumps(out))
 
 
 def parity_lines(path):
@@ -61,6 +80,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--epochs", type=int, default=5)
     ap.add_argument("--processes", type=int, default=0, help="0: measure in this process; N: N fresh processes, one after the other")
+    ap.add_argument("--weighted", action="store_true", help="also time the weighted epoch and one objective call")
     ap.add_argument("--parity", default=None)
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
@@ -70,7 +90,7 @@ def main():
     runs = []
     for _ in range(a.processes):
         out = subprocess.run([sys.executable, os.path.abspath(__file__), "--shape", a.shape, "--num-dim", str(a.num_dim), "--cg-steps", str(a.cg_steps),
-                              "--warmup", str(a.warmup), "--epochs", str(a.epochs)], check=True, capture_output=True, text=True, timeout=600).stdout
+                              "--warmup", str(a.warmup), "--epochs", str(a.epochs)] + (["--weighted"] if a.weighted else []), check=True, capture_output=True, text=True, timeout=600).stdout
         runs.append(json.loads(out.strip().splitlines()[-1]))
     r = runs[0]
     U, I, Kp, prods = r["users"], r["items"], r["row_stride"], r["cg_steps"] + 1
@@ -85,6 +105,13 @@ def main():
              f"floor, matrix work: {prods} (U + I) 2 Kp^2 = {flops / 1e9:.1f} GFLOP -> {flops / (FP32_MATRIX_TFLOPS * 1e12) * 1e3:.3f} ms at {FP32_MATRIX_TFLOPS} TFLOP/s fp32 matrix",
              f"floor, G traffic: {prods} ceil(rows / 32) Kp^2 4 B over both sides = {traffic / 1e9:.2f} GB from L2 -> {traffic / (L2_TBPS * 1e12) * 1e3:.3f} ms at ~{L2_TBPS:.0f} TB/s",
              "(both floors are estimates from the shapes; the sparse part — one wavefront dot product and axpy per interaction and product — is on neither)"]
+    if a.weighted:
+        wmed = statistics.median(x["weighted_median_epoch_seconds"] for x in runs)
+        omed = statistics.median(x["median_objective_seconds"] for x in runs)
+        lines += [f"with per-pair confidence weights (geometric(0.3) play counts), same processes; per-process medians (s): "
+                  + ", ".join(f"{x['weighted_median_epoch_seconds']:.4f}" for x in runs),
+                  f"median weighted epoch: {wmed * 1e3:.2f} ms ({(wmed / med - 1) * 100:+.1f} % against the binary epoch)",
+                  f"one cdae_hip_als_objective call (host wall clock, weighted handle): {omed * 1e3:.2f} ms"]
     if a.parity:
         lines += [""] + parity_lines(a.parity)
     text = "\n".join(lines) + "\n"
